@@ -12,6 +12,10 @@ A "step" = one Lagrangian cycle of the whole cloud (one launch of the fused kern
 plus, when N > 1, the ownership re-cut + hand-off every --rebalance-interval steps).  Inputs are resident in HBM when the
 timed region starts.  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: set-up, device spin-up, W warm-up steps, K timed steps, the outputs of the
+last step if --dump-outputs DIR is given, the line.  --full adds what is measured besides it (the single-GPU extras after the
+timed region and the cpu_baseline).
+
 Layout: `run(args, M)` is the measurement; everything it needs from the machine -- device, context, collectives,
 seeding, the single-GPU extras -- comes from `M` (`GpuMachine`: one MI355X per rank, RCCL).  tests/ drive the same
 `run()` with a CPU stand-in for `M` over gloo to check the N > 1 orchestration and the JSON contract without a GPU;
@@ -33,6 +37,8 @@ if ROOT not in sys.path:
 
 ALGO_BYTES_PER_PARTICLE_STEP = 56      # fp64 SoA: read x,y,z (24) + cell (4), write x,y,z (24) + cell (4)
 HBM_PEAK_GBS = 8000.0                  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_SAMPLE = 1 << 20                  # --dump-outputs: 48 B per sampled particle, 48 MB at most
+DUMP_SEED = 20240607
 
 
 def parse(argv=None):
@@ -129,6 +135,14 @@ def parse(argv=None):
                          "shards) stepped on this ONE GPU, reported as config.strong_anchor_1e8 -- the N = 1 point of "
                          "the strong-scaling curve, never `value`; 0 = skip")
     ap.add_argument("--anchor-steps", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: the single-GPU extras after the timed region (brownian, "
+                         "fused, steady, anchor, the tutorials as run, VertexVelocity, polyhedral) and the cpu_baseline; without "
+                         "it a run sets up, warms up, times the steps and prints the line, the extras' keys null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed -- the cloud in particle-id order as cpf_shard_gather "
+                         "returns it -- for a fixed, seeded sample of at most %d particles: DIR/xyzw.npy (float64 [m][4], w = 1 "
+                         "active), DIR/cell.npy and DIR/particle_id.npy (float64 [m])" % DUMP_SAMPLE)
     a = ap.parse_args(argv)
     if a.scaling is None:
         a.scaling = "weak" if a.gpus == 1 else "strong"
@@ -875,6 +889,20 @@ class GpuMachine:
         self.ctx.close()
 
 
+def dump_outputs(cloud, out_dir, rank):
+    """COLLECTIVE (--dump-outputs): the cloud as the timed steps left it, gathered to rank 0 in particle-id order; rank 0 writes
+    the same seeded sample of ids every run, so that two builds can be compared output for output."""
+    xyzw, cell, _ = cloud.gather(root=0)
+    if rank != 0:
+        return
+    n = cell.shape[0]
+    ids = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "xyzw.npy"), np.ascontiguousarray(xyzw[ids], dtype=np.float64))
+    np.save(os.path.join(out_dir, "cell.npy"), cell[ids].astype(np.float64))
+    np.save(os.path.join(out_dir, "particle_id.npy"), ids.astype(np.float64))
+
+
 def run(args, M):
     """The measurement.  Returns the JSON record on rank 0, None elsewhere."""
     from cudaparticlesfoam_amd.cases import pitzdaily as pz
@@ -1003,10 +1031,12 @@ def run(args, M):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     n_after = cloud.global_count()
+    if args.dump_outputs:
+        dump_outputs(cloud, args.dump_outputs, rank)
 
     brown = fused = steady = anchor = None
     more = {}
-    if world == 1 and not args.force_dist:
+    if args.full and world == 1 and not args.force_dist:
         stage("extras")
         brown, fused, steady, anchor, more = M.extras(cloud, dt, args, full_box)
 
@@ -1085,7 +1115,7 @@ def run(args, M):
                          "kernel": ctx.step_kernel_name(0.0, 0), "kernel_avg_ms": round(avg_kernel_s * 1e3, 4),
                          "launches": launches, "launches_sampled_every": args.timing_stride, "algorithmic_bytes_per_launch": int(ALGO_BYTES_PER_PARTICLE_STEP * per_launch)},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(mesh, centres, U, args.cpu_seconds)
             except Exception as e:          # the checker being absent must not hide the GPU number

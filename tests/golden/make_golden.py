@@ -22,6 +22,9 @@ ConvexPoly build, diffusionCoeff 0):
                                  fuses), plus profiles/r06_fma_sensitivity.json: strict vs contracting build on 400 000
                                  particles (cells that differ, max and 99.99-percentile |dx|/L per checkpoint).  Does NOT
                                  rewrite the files above.
+  vtu_reference.json           : `python tests/golden/make_golden.py vtu` -- SHA-256 of the reference writer's VTU file
+                                 (writeParticles2VTU) and of its inputs for every frame of tests/test_vtu_writer.py's
+                                 REFERENCE_FRAMES, for where oracle/_ref cannot be built.  Does NOT rewrite the files above.
 Usage: python tests/golden/make_golden.py [fma]   (from the repo root, in the container with /root/reference)
 """
 import hashlib
@@ -200,5 +203,25 @@ def main():
     print("goldens written to", HERE)
 
 
+def main_vtu():
+    import json
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_vtu_writer as T
+    O.build()
+    if not O.have_ref():
+        sys.exit("oracle/_ref is not built: cannot generate the VTU digests here")
+    ref, out = O.RefLib(), {}
+    with tempfile.TemporaryDirectory() as d:
+        for key, frame, inputs in T.REFERENCE_FRAMES:
+            xyzw, cell, vel = inputs()
+            with open(ref.write_vtu(d, frame, xyzw, vel, cell, cell), "rb") as f:
+                out[key] = {"frame": frame, "inputs_sha256": T.sha256(xyzw, cell, vel), "sha256": T.sha256(f.read())}
+    with open(os.path.join(HERE, "vtu_reference.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("VTU digests written to", HERE)
+
+
 if __name__ == "__main__":
-    main_fma() if sys.argv[1:] == ["fma"] else main()
+    {"fma": main_fma, "vtu": main_vtu}.get(sys.argv[1] if sys.argv[1:] else "", main)()

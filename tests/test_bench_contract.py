@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,6 +32,20 @@ def _check(line, need_cpu_baseline, scaling="weak"):
     return d
 
 
+def _check_dump(out, n):
+    """--dump-outputs: the whole cloud (n <= the sample size) in particle-id order, float64, every particle live in the domain."""
+    sys.path.insert(0, ROOT)
+    from cudaparticlesfoam_amd.cases import pitzdaily as pz
+    assert sorted(os.listdir(out)) == ["cell.npy", "particle_id.npy", "xyzw.npy"]
+    xyzw, cell, ids = (np.load(os.path.join(out, f)) for f in ("xyzw.npy", "cell.npy", "particle_id.npy"))
+    assert xyzw.dtype == cell.dtype == ids.dtype == np.float64
+    assert xyzw.shape == (n, 4) and cell.shape == ids.shape == (n,) and np.array_equal(ids, np.arange(n))
+    assert (xyzw[:, 3] == 1).all() and (cell >= 0).all() and (cell < 12225).all() and (cell == np.round(cell)).all()
+    lo, hi = pz.pitzdaily_mesh().bounds()
+    assert (xyzw[:, :3] >= lo - 1e-9).all() and (xyzw[:, :3] <= hi + 1e-9).all()
+    return xyzw, cell
+
+
 def test_defaults_follow_the_north_star(monkeypatch):
     """--gpus 1 is the 1e7 single-GPU config (BASELINE configs[2]); --gpus N > 1 is configs[3]: 1e8 particles in
     total over the N ranks, i.e. strong scaling -- unless the caller says otherwise."""
@@ -53,16 +68,17 @@ def test_committed_round_profile_follows_the_contract():
     assert 0.95 < d["roofline"]["traffic"] / d["roofline"]["algorithmic_bytes_per_launch"] < 1.15   # PMC: no wasted re-reads
 
 
-def test_world_2_orchestration_over_gloo_prints_one_strong_scaling_line():
+def test_world_2_orchestration_over_gloo_prints_one_strong_scaling_line(tmp_path):
     """The N > 1 path of bench.run() -- per-slab seeding, re-cut by (pretended) step time, overlapped hand-offs,
-    max-over-ranks clock, rank 0's single JSON line -- with a CPU stand-in for the machine (tests/_bench_worker.py:
-    oracle + gloo).  The figures are not performance; the contract and the bookkeeping are what is checked."""
+    max-over-ranks clock, rank 0's single JSON line, --dump-outputs gathered over the ranks -- with a CPU stand-in for the
+    machine (tests/_bench_worker.py: oracle + gloo).  The figures are not performance; the contract and the bookkeeping are
+    what is checked."""
     import socket
     s_ = socket.socket(); s_.bind(("127.0.0.1", 0)); port = s_.getsockname()[1]; s_.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "tests", "_bench_worker.py"), "--gpus", "2",
            "--particles", "4000", "--steps", "8", "--warmup", "2", "--rebalance-interval", "4", "--overlap-steps", "2",
-           "--sort-interval", "5"]
+           "--sort-interval", "5", "--dump-outputs", str(tmp_path / "out")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env=dict(os.environ, OMP_NUM_THREADS="1", PYTHONPATH=ROOT))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -71,6 +87,7 @@ def test_world_2_orchestration_over_gloo_prints_one_strong_scaling_line():
     d = _check(lines[0], need_cpu_baseline=False, scaling="strong")
     c = d["config"]
     assert d["n_gpus"] == 2 and c["rccl_ranks"] == 2 and "cpu_baseline" not in d
+    _check_dump(tmp_path / "out", 4000)
     assert c["particles_total"] == 4000 and c["particles_after"] == 4000       # every boundary reflects
     assert sum(c["particles_per_rank_at_end"]) == 4000 and min(c["particles_per_rank_at_end"]) > 1000
     assert c["ms_in_handoff"]["handoffs"] == 2 and c["handoff_fraction_per_step"] > 0 and c["balance"] == "measured step time"
@@ -252,6 +269,31 @@ def test_the_drivers_arguments_on_a_one_rank_rccl_group_hold_handoffs():
 
 
 @pytest.mark.gpu
+def test_a_plain_run_is_the_headline_alone_and_dumps_the_same_outputs_every_time(tmp_path):
+    """Without --full: set-up, warm-up, exactly --steps timed launches, the line -- no extras, no cpu_baseline.  Two runs with the
+    same arguments dump the same cloud bit for bit (the inputs are seeded)."""
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("out%d" % k)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--particles", "2e5", "--steps", "6", "--warmup", "2",
+               "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1 and r.stdout.strip() == lines[0]
+        d = _check(lines[0], need_cpu_baseline=False)
+        c = d["config"]
+        assert d["steps"] == 6 and d["warmup"] == 2 and c["particles_total"] == c["particles_after"] == 200_000
+        assert d["roofline"]["launches_sampled_every"] == 1 and d["roofline"]["launches"] == 6     # the timed launches, all stamped
+        assert "cpu_baseline" not in d and "[bench stage] extras" not in r.stderr
+        for key in ("brownian", "extra_fused_cycles", "ms_per_step_steady", "strong_anchor_1e8", "brownian_steady", "analytic_field",
+                    "tjunction_as_run", "vertex_velocity", "polyhedral_as_run"):
+            assert c[key] is None, key
+        dumps.append(_check_dump(out, 200_000))
+    assert all(np.array_equal(a, b) for a, b in zip(*dumps))
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("extra", [[], ["--force-dist"], ["--self-launch", "--force-dist"]])
 def test_bench_runs_and_prints_one_json_line(extra):
     """A small live run (2e5 particles, 6 steps): exit code 0, exactly one JSON line on stdout, contract fields;
@@ -259,7 +301,8 @@ def test_bench_runs_and_prints_one_json_line(extra):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--particles", "2e5", "--steps", "6", "--warmup", "2",
            "--no-cpu-baseline", "--rebalance-interval", "3", "--overlap-steps", "1", "--anchor-particles", "4e5",
            "--anchor-steps", "3", "--brownian-steady-steps", "30", "--analytic-extra", "4", "--tjunction-steps", "30",
-           "--tjunction-particles", "3e5", "--vertex-steps", "3", "--polyhedral-steps", "20", "--polyhedral-particles", "3e5"] + extra
+           "--tjunction-particles", "3e5", "--vertex-steps", "3", "--polyhedral-steps", "20", "--polyhedral-particles", "3e5",
+           "--full"] + extra
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29577")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]

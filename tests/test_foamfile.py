@@ -1,7 +1,7 @@
 """CPU: the case directory as OpenFOAM stores it (cases/foamfile.py) -- the data format on the input side of the path.  The
 reference's solvers get mesh and U from OpenFOAM objects (src/initCuda.H:76-124, src/advect.H:44-57); the Python host reads the
-files: round trips of this repo's synthetic cases bit for bit, hand-written files in OpenFOAM's ASCII style, refusals, and (where
-the reference tree is present) the tutorials' own 0/U."""
+files: round trips of this repo's synthetic cases bit for bit, hand-written files in OpenFOAM's ASCII style, refusals, and the
+tutorials' own 0/U (tests/golden/tutorials)."""
 import os
 
 import numpy as np
@@ -130,8 +130,9 @@ def test_binary_and_compressed_files_are_refused(tmp_path):
         ff.read_faces(str(d / "faces"))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/tutorials"), reason="the reference tree is only present in the build container")
 def test_the_tutorials_own_U_files_parse():
-    for case, n in (("cudaParticlesUncoupledFoam/pitzDaily", 12225), ("cudaParticlesPimpleFoam/TJunction", 248000)):
-        u = ff.read_vector_field(os.path.join("/root/reference/tutorials/incompressible", case, "0", "U"), n)
+    # the two tutorials' 0/U as they ship, stored under tests/golden/tutorials
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tutorials")
+    for case, n in (("pitzDaily", 12225), ("TJunction", 248000)):
+        u = ff.read_vector_field(os.path.join(golden, case, "0", "U"), n)
         assert u.shape == (n, 3) and (u == 0.0).all()              # both start from internalField uniform (0 0 0)

@@ -1,13 +1,67 @@
 """CPU: the output path.  The library's VTU writer against the REFERENCE's own writer
 (writeParticles2VTU, cuda/utils.cpp:144-283, compiled into oracle/_ref from the source where it lies), byte for
-byte, and its printf-free number formatting against correctly rounded formatting on a million doubles."""
+byte, and its printf-free number formatting against correctly rounded formatting on a million doubles.  Where oracle/_ref
+could not be built, the reference's frames are the SHA-256 digests `tests/golden/make_golden.py vtu` stored of them."""
 import ctypes as C
+import hashlib
+import json
 import os
 
 import numpy as np
 import pytest
 
 from cudaparticlesfoam_amd import _lib as L
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "vtu_reference.json")
+
+
+def sha256(*parts):
+    h = hashlib.sha256()
+    for a in parts:
+        h.update(a if isinstance(a, bytes) else np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def small_frame_inputs():
+    """5000 particles over nine decades, every 7th inactive, edge values first; (xyzw, cell, zero velocities, velocities with
+    one NaN row and one zero row)."""
+    rng = np.random.default_rng(3)
+    n = 5000
+    xyzw = np.concatenate([rng.normal(size=(n, 3)) * 10.0 ** rng.integers(-6, 3, size=(n, 1)), np.ones((n, 1))], 1)
+    xyzw[::7, 3] = 0.0                                           # inactive particles (w = 0)
+    xyzw[:4, :3] = [[0.0, -0.0, 1e-300], [0.5e-15, 1.5e-15, 2.5e-15], [-1.0, 123456.789, 1e12], [0.1, 0.2, 0.3]]
+    cell = rng.integers(-3, 12225, size=n).astype(np.int32)
+    vel = np.concatenate([rng.normal(size=(n, 3)) * 3.0, np.zeros((n, 1))], 1)
+    vel[11, 0] = np.nan
+    vel[12, :3] = 0.0
+    return xyzw, cell, np.zeros((n, 4)), vel
+
+
+def large_frame_inputs():
+    rng = np.random.default_rng(17)
+    n = 150_000
+    xyzw = np.concatenate([rng.normal(size=(n, 3)) * 10.0 ** rng.integers(-5, 3, size=(n, 1)), np.ones((n, 1))], 1)
+    xyzw[::11, 3] = 0.0
+    cell = rng.integers(-2, 248000, size=n).astype(np.int32)
+    return xyzw, cell, np.zeros((n, 4))
+
+
+# (key, frame number, inputs) of every reference frame the tests compare with; make_golden.py vtu digests the same list
+REFERENCE_FRAMES = (("zero_velocities", 7, lambda: small_frame_inputs()[:3]),
+                    ("velocities", 8, lambda: small_frame_inputs()[:2] + small_frame_inputs()[3:]),
+                    ("large", 3, large_frame_inputs))
+
+
+def reference_frame(oracle_libs, tmp_path, key, xyzw, cell, vel, expect):
+    """The bytes the reference's writer writes for these particles: its own file where oracle/_ref is built; elsewhere `expect`
+    -- what the caller derives from the library's frame -- once its digest is the one stored of the reference's file."""
+    frame = {k: f for k, f, _ in REFERENCE_FRAMES}[key]
+    if oracle_libs.have_ref():
+        return open(oracle_libs.RefLib().write_vtu(str(tmp_path), frame, xyzw, vel, cell, cell), "rb").read()
+    g = json.load(open(GOLDEN))[key]
+    assert sha256(xyzw, cell, vel) == g["inputs_sha256"], "%s: not the inputs the stored digest was taken of" % key
+    assert sha256(expect) == g["sha256"], "%s: not the reference writer's bytes" % key
+    return expect
 
 
 def _write(path, xyzw, cell, vel):
@@ -36,30 +90,37 @@ def _sections(text):
     return out, skel
 
 
+def _zero_kes(text):
+    """The frame with every line of its KEs array replaced by 0.000000, as the reference prints them."""
+    out, inside = [], False
+    for line in text.split("\n"):
+        if line.startswith("<DataArray"):
+            inside = "Name='KEs'" in line
+        elif line.startswith("</DataArray>"):
+            inside = False
+        elif inside:
+            line = "0.000000"
+        out.append(line)
+    return "\n".join(out)
+
+
 def test_vtu_bytes_equal_the_reference_writer(tmp_path, oracle_libs):
-    ref = oracle_libs.RefLib()
-    rng = np.random.default_rng(3)
-    n = 5000
-    xyzw = np.concatenate([rng.normal(size=(n, 3)) * 10.0 ** rng.integers(-6, 3, size=(n, 1)), np.ones((n, 1))], 1)
-    xyzw[::7, 3] = 0.0                                           # inactive particles (w = 0)
-    xyzw[:4, :3] = [[0.0, -0.0, 1e-300], [0.5e-15, 1.5e-15, 2.5e-15], [-1.0, 123456.789, 1e12], [0.1, 0.2, 0.3]]
-    cell = rng.integers(-3, 12225, size=n).astype(np.int32)
+    xyzw, cell, vel0, vel = small_frame_inputs()
+    n = xyzw.shape[0]
     # (a) velocities zero: the files must be identical down to the last byte
-    vel0 = np.zeros((n, 4))
     mine = tmp_path / "mine.vtu"
     r, ke = _write(mine, xyzw, cell, vel0)
     assert r == 0 and ke == 0.0
-    theirs = ref.write_vtu(str(tmp_path), 7, xyzw, vel0, cell, cell)
-    assert open(mine, "rb").read() == open(theirs, "rb").read()
+    got = open(mine, "rb").read()
+    assert got == reference_frame(oracle_libs, tmp_path, "zero_velocities", xyzw, cell, vel0, expect=got)
     # (b) real velocities (one NaN row -> "0 0 0" like the reference): identical except the KEs array, where the
     # reference prints 0.000000 for every NON-zero energy (utils.cpp:245-248) and this writer prints the energy
-    vel = np.concatenate([rng.normal(size=(n, 3)) * 3.0, np.zeros((n, 1))], 1)
-    vel[11, 0] = np.nan
-    vel[12, :3] = 0.0
     r, ke = _write(mine, xyzw, cell, vel)
-    theirs = ref.write_vtu(str(tmp_path), 8, xyzw, vel, cell, cell)
-    a, askel = _sections(open(mine).read())
-    b, bskel = _sections(open(theirs).read())
+    text = open(mine).read()
+    theirs = reference_frame(oracle_libs, tmp_path, "velocities", xyzw, cell, vel, expect=_zero_kes(text).encode())
+    a, askel = _sections(text)
+    b, bskel = _sections(theirs.decode())
+    assert len(a["KEs"]) == n
     assert askel == bskel and list(a) == list(b)
     for name in a:
         if name != "KEs":
@@ -73,19 +134,12 @@ def test_vtu_bytes_equal_the_reference_writer(tmp_path, oracle_libs):
 def test_a_large_frame_takes_the_parallel_path_and_keeps_the_bytes(tmp_path, oracle_libs):
     """150 000 particles (19 chunks per array): every array of the frame is formatted from a work counter by many threads, each
     chunk into its own string, written in order; the file must still be the reference writer's, byte for byte."""
-    ref = oracle_libs.RefLib()
-    rng = np.random.default_rng(17)
-    n = 150_000
-    xyzw = np.concatenate([rng.normal(size=(n, 3)) * 10.0 ** rng.integers(-5, 3, size=(n, 1)), np.ones((n, 1))], 1)
-    xyzw[::11, 3] = 0.0
-    cell = rng.integers(-2, 248000, size=n).astype(np.int32)
-    vel0 = np.zeros((n, 4))
+    xyzw, cell, vel0 = large_frame_inputs()
     mine = tmp_path / "big.vtu"
     r, ke = _write(mine, xyzw, cell, vel0)
     assert r == 0 and ke == 0.0
-    theirs = ref.write_vtu(str(tmp_path), 3, xyzw, vel0, cell, cell)
     got = open(mine, "rb").read()
-    assert len(got) > 12_000_000 and got == open(theirs, "rb").read()
+    assert len(got) > 12_000_000 and got == reference_frame(oracle_libs, tmp_path, "large", xyzw, cell, vel0, expect=got)
 
 
 def test_number_formatting_is_correctly_rounded(tmp_path):

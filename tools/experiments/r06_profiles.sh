@@ -9,7 +9,7 @@ off() { echo "$OFF" | sed "s/$1 0//"; }
 # the headline alone: the 100 launches of the statistics-off instantiation are exactly the timed steps (raw trace kept)
 tools/pmc.sh r06 -- python3 bench.py --steps 100 --warmup 10 $OFF
 cp $(find gpurun_out/r06/stats -name "*kernel_trace.csv" | head -1) gpurun_out/r06_headline_kernel_trace.csv 2>/dev/null
-tools/pmc.sh r06_brown --sq -- python3 bench.py --steps 20 --warmup 5 $(off --brownian-steady-steps) --brownian-steady-steps 100 --no-fused-tutorial
-tools/pmc.sh r06_vertex -- python3 bench.py --steps 20 --warmup 5 $(off --vertex-steps) --vertex-steps 50
-tools/pmc.sh r06_poly -- python3 bench.py --steps 20 --warmup 5 $(off --polyhedral-steps) --polyhedral-steps 50
-tools/pmc.sh r06_tjrun -- python3 bench.py --steps 20 --warmup 5 $(off --tjunction-steps) --tjunction-steps 100 --no-fused-tutorial
+tools/pmc.sh r06_brown --sq -- python3 bench.py --full --steps 20 --warmup 5 $(off --brownian-steady-steps) --brownian-steady-steps 100 --no-fused-tutorial
+tools/pmc.sh r06_vertex -- python3 bench.py --full --steps 20 --warmup 5 $(off --vertex-steps) --vertex-steps 50
+tools/pmc.sh r06_poly -- python3 bench.py --full --steps 20 --warmup 5 $(off --polyhedral-steps) --polyhedral-steps 50
+tools/pmc.sh r06_tjrun -- python3 bench.py --full --steps 20 --warmup 5 $(off --tjunction-steps) --tjunction-steps 100 --no-fused-tutorial
