@@ -17,6 +17,7 @@ HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), "include", "cpf.h")
 CPF_OK, CPF_ERR_ARG, CPF_ERR_STATE, CPF_ERR_MESH, CPF_ERR_HIP, CPF_ERR_NOMEM, CPF_WARN_NAN = range(7)
 CELL_LOST, CELL_FROZEN = -1, -2
 STEP_DEFAULT, STEP_NO_REFLECT, STEP_STORE_VEL, STEP_FUSE_CYCLES, STEP_VERTEX_VELOCITY = 0, 1, 2, 4, 8
+STEP_Z_SETTLED = 16                     # cpf_step_dev: z is a fixed point of the flat cycle (include/cpf.h)
 HANDOFF_DOUBLES = 5
 MAX_RANKS, COMM_ID_BYTES, COMM_RCCL, COMM_INPROCESS = 64, 128, 1, 2
 

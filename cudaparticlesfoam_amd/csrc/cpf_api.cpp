@@ -76,6 +76,10 @@ struct cpf_context {
     cpf::StreamState streamState;               // chunk counter + tuning of the streaming step kernel
     int64_t lastStepN = -1;                     // particle count of the most recent step launch (cpf_step_kernel_name)
     int lastStepCycles = 1;                     // ... and its cycles per launch
+    // z of the context's own cloud is a fixed point of the flat cycle (CPF_STEP_Z_SETTLED): set behind a flat launch that
+    // streamed z, cleared by everything else that writes x, y, z or cell -- except a sort, which only permutes
+    bool zSettled = false;
+    bool lastStepZSettled = false;              // what the most recent cpf_step_dev left behind on ITS arrays (cpf_shard.cpp)
     // "VertexVelocity" advect only: the tet decomposition and one velocity per tet-mesh vertex
     double* d_tetPos = nullptr; int32_t* d_tets = nullptr; double* d_vertVel = nullptr;
     int64_t nTetVerts = 0, nTets = 0; int tetsPerCell = 0; bool haveVertVel = false;
@@ -188,7 +192,7 @@ void freeMesh(cpf_context* c) {
 void freeCloud(cpf_context* c) {
     freeDev(c->x); freeDev(c->y); freeDev(c->z); freeDev(c->vel); freeDev(c->cell); freeDev(c->gid);
     freeDev(c->x2); freeDev(c->y2); freeDev(c->z2); freeDev(c->cell2); freeDev(c->gid2);
-    c->cap = c->n = 0; c->located = false;
+    c->cap = c->n = 0; c->located = false; c->zSettled = false;
 }
 
 template <typename Label>
@@ -261,6 +265,7 @@ int setMeshImpl(cpf_context* ctx, const double* points, int64_t nPoints, const L
     ctx->meshBytes += (size_t)nCells * (sizeof(double4) + 24);
     ctx->haveMesh = true;
     ctx->located = false;
+    ctx->zSettled = false;
     if (ctx->h_occupied) ctx->h_occupied[0] = ctx->h_occupied[1] = 0;      // (what the last sort counted belonged to the old mesh)
     return CPF_OK;
 }
@@ -280,6 +285,7 @@ void* context_stream(const cpf_context* ctx) { return (void*)ctx->stream; }
 int context_device(const cpf_context* ctx) { return ctx->device; }
 bool context_timing(const cpf_context* ctx) { return ctx->timing; }
 int64_t context_cells(const cpf_context* ctx) { return ctx->haveMesh ? ctx->host.nCells : 0; }
+bool context_step_settled_z(const cpf_context* ctx) { return ctx->lastStepZSettled; }
 }  // namespace cpf
 
 namespace {
@@ -631,7 +637,7 @@ int cpf_seed_box(cpf_context* ctx, int64_t n, const double lower[3], const doubl
     CPF_HIP(ctx, cpf::launch_seed_box(ctx->stream, ctx->x, ctx->y, ctx->z, 0, n, lower, upper, order));
     CPF_HIP(ctx, cpf::launch_iota64(ctx->stream, ctx->gid, n, 0));
     CPF_HIP(ctx, hipMemsetAsync(ctx->cell, 0xFF, (size_t)n * 4, ctx->stream));
-    ctx->n = n; ctx->located = false;
+    ctx->n = n; ctx->located = false; ctx->zSettled = false;
     return CPF_OK;
 }
 
@@ -640,6 +646,7 @@ int cpf_set_particles(cpf_context* ctx, int64_t n, const double* xyz, const int3
     CPF_REQUIRE(ctx, xyz && n > 0, CPF_ERR_ARG, "cpf_set_particles: bad arguments");
     if (ctx->cap < n) { int r = cpf_alloc_particles(ctx, n); if (r) return r; }
     CPF_HIP(ctx, hipSetDevice(ctx->device));
+    ctx->zSettled = false;
     int r = ensureScratch(ctx, (size_t)n * 24);
     if (r) return r;
     CPF_HIP(ctx, hipMemcpyAsync(ctx->scratch, xyz, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
@@ -665,6 +672,7 @@ int cpf_locate_initial_dev(cpf_context* ctx, const double* x, const double* y, c
 int cpf_locate_initial(cpf_context* ctx, int64_t* nOutside) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, ctx->n > 0, CPF_ERR_STATE, "cpf_locate_initial: no particles (seed or set them first)");
+    ctx->zSettled = false;                    // (a frozen particle found inside the mesh is live again, with whatever z it had)
     int r = cpf_locate_initial_dev(ctx, ctx->x, ctx->y, ctx->z, ctx->cell, ctx->n);
     if (r) return r;
     ctx->located = true;
@@ -698,6 +706,11 @@ int cpf_step_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cel
     const cpf::MeshView m = meshView(ctx);
     const bool fuse = (flags & CPF_STEP_FUSE_CYCLES) != 0;
     pollFieldFlag(ctx);
+    // z settled: the caller's word for the first launch; after a launch, what that launch left behind -- settled behind a
+    // flat instantiation (it maps every live particle's z to a fixed point, or was given settled z and left it alone), not
+    // settled behind any other; a launch of zero cycles loads and stores only and changes nothing
+    bool settled = (flags & CPF_STEP_Z_SETTLED) != 0;
+    ctx->lastStepZSettled = false;
     const int nLaunch = fuse ? 1 : nCycles;   // fused with nCycles == 0: load+store only (bandwidth calibration)
     const int cycPerLaunch = fuse ? nCycles : 1;
     for (int c = 0; c < nLaunch; ++c) {
@@ -722,6 +735,8 @@ int cpf_step_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cel
             else CPF_HIP(ctx, hipEventRecord(e0, ctx->stream));
         }
         ctx->lastStepN = n; ctx->lastStepCycles = cycPerLaunch;
+        ctx->streamState.zSettled = settled && ctx->streamState.flatZ != 0;
+        ctx->streamState.lastLookup = -1;
         const hipError_t le = vertexU
             ? cpf::launch_step_vertex(ctx->stream, x, y, z, cell, gid, vel, n, dt, D, step0 + (uint32_t)c, cycPerLaunch, ctx->seed, reflect,
                                       storeVel, m, ctx->stats ? ctx->d_counters : nullptr, ctx->d_tetPos, ctx->d_tets, ctx->tetsPerCell,
@@ -736,7 +751,9 @@ int cpf_step_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cel
             if (e0) ctx->eventPool.push_back(e0);
             if (e1) ctx->eventPool.push_back(e1);
         }
+        ctx->streamState.zSettled = false;
         CPF_HIP(ctx, le);
+        if (n > 0 && cycPerLaunch > 0) settled = !vertexU && (ctx->streamState.lastLookup == 8 || ctx->streamState.lastLookup == 9);
         if (timed) {
             if (!stamped) CPF_HIP(ctx, hipEventRecord(e1, ctx->stream));
             else if (ctx->streamState.evStart != nullptr) {  // (cannot happen: the streaming launcher always takes them)
@@ -746,6 +763,7 @@ int cpf_step_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cel
             ctx->events.emplace_back(e0, e1);
         }
     }
+    ctx->lastStepZSettled = settled;
     return CPF_OK;
 }
 
@@ -760,9 +778,12 @@ int cpf_step(cpf_context* ctx, double dt, double D, int nCycles, unsigned flags)
         CPF_HIP(ctx, hipSetDevice(ctx->device));
         CPF_HIP(ctx, hipMemsetAsync(ctx->vel, 0, (size_t)ctx->n * 24, ctx->stream));
     }
+    const bool settled = ctx->zSettled;
+    ctx->zSettled = false;
     int r = cpf_step_dev(ctx, ctx->x, ctx->y, ctx->z, ctx->cell, ctx->gid, ctx->vel, ctx->n, dt, D, ctx->stepCounter,
-                         nCycles, flags);
+                         nCycles, (flags & ~CPF_STEP_Z_SETTLED) | (settled ? CPF_STEP_Z_SETTLED : 0u));
     if (r != CPF_OK) return r;
+    ctx->zSettled = ctx->lastStepZSettled;
     // a cycle of zero length without a kick moves nothing: it is the frame-0 idiom (velocities of one advect in the
     // first output file, out-of-domain particles frozen; src/initCuda.H:184-201) and not a step of the run, so the
     // counter-based Brownian stream and the sort cadence do not see it
@@ -939,6 +960,11 @@ int cpf_set_option(cpf_context* ctx, const char* key, double value) {
     if (k == "flat_walk") {
         CPF_REQUIRE(ctx, value == 0 || value == 1, CPF_ERR_ARG, "flat_walk must be 0 or 1");
         ctx->streamState.flat = (int)value;
+        return CPF_OK;
+    }
+    if (k == "flat_z") {
+        CPF_REQUIRE(ctx, value == 0 || value == 1, CPF_ERR_ARG, "flat_z must be 0 or 1");
+        ctx->streamState.flatZ = (int)value;
         return CPF_OK;
     }
     if (k == "box_records") {

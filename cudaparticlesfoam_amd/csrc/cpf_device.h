@@ -72,6 +72,12 @@ struct StreamState {
     // out, read back behind it): with MeshView::zSide0 and without the kick the FLAT instantiation runs (cpf_walk.h "flat walk")
     bool flatField = false;
     int flat = 1;             // "flat_walk": 0 = never (diagnostics; bit-identical either way)
+    // set by the caller before a launch: the cloud's z is settled (CPF_STEP_Z_SETTLED) -- the flat instantiations then leave z in
+    // memory alone (StreamArgs::zSettled); "flat_z" 0 keeps this false
+    bool zSettled = false;
+    int flatZ = 1;            // "flat_z": 0 = the flat instantiations always stream z (A/B; bit-identical either way)
+    // set by the streaming launcher: the LOOKUP instantiation it launched (8 / 9: the flat walk), -1 the vertex kernel
+    int lastLookup = -1;
 };
 
 hipError_t launch_step_ahead(hipStream_t st, double* x, double* y, double* z, int32_t* cell, int64_t n, double dt, bool reflect,

@@ -62,6 +62,7 @@ void* context_stream(const cpf_context* ctx);       // the hipStream_t its kerne
 int context_device(const cpf_context* ctx);
 bool context_timing(const cpf_context* ctx);        // cpf_timing_enable state
 int64_t context_cells(const cpf_context* ctx);      // 0: no mesh yet
+bool context_step_settled_z(const cpf_context* ctx); // the most recent cpf_step_dev left z settled on its arrays (CPF_STEP_Z_SETTLED)
 bool vtu_binary(const cpf_context* ctx);            // option "vtu_binary"
 
 }  // namespace cpf

@@ -76,6 +76,7 @@ struct HipDev {
              uint32_t step0, int nCycles, unsigned flags) {
         return api(cpf_step_dev(ctx, x, y, z, cell, gid, vel, n, dt, D, step0, nCycles, flags));
     }
+    bool stepSettledZ() const { return cpf::context_step_settled_z(ctx); }     // (ShardCore: DevReportsZ)
     int pack(double* x, double* y, double* z, int32_t* cell, int64_t* gid, int64_t n, const int32_t* cellLo, int W, int rank,
              double* sendbuf, int64_t sendCap, int64_t* counts, int64_t* nStay) {
         return api(cpf_pack_leavers_dev(ctx, x, y, z, cell, gid, n, cellLo, W, rank, sendbuf, sendCap, counts, nStay));

@@ -17,6 +17,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -25,6 +26,10 @@
 namespace cpf {
 
 constexpr double kCostUnitMs = 2.0e-8;   // ms per particle-step that counts as cost 1 (~ the measured single-GPU rate)
+
+// a device that reports whether its last step left z settled (CPF_STEP_Z_SETTLED); one that does not never gets the flag
+template <class D, class = void> struct DevReportsZ : std::false_type {};
+template <class D> struct DevReportsZ<D, std::void_t<decltype(std::declval<const D&>().stepSettledZ())>> : std::true_type {};
 
 inline double nowMs() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -76,6 +81,10 @@ class ShardCore {
     // state of the step loop
     uint32_t stepIndex = 0;
     bool velValid = false;       // `vel` holds the last cycle's velocities of the particles AS THEY ARE ORDERED NOW (round-5 advisory)
+    // z of every live particle in [0, n) is a fixed point of the flat cycle (CPF_STEP_Z_SETTLED, ORed in at the step launch
+    // only -- argFlags, which the pending hand-off compares, never carries it): set behind a step launch over the whole shard
+    // that the device reports as settled, cleared by every other write of x, y, z or cell; the split and the sort only permute
+    bool zSettled = false;
     struct Pending { bool on = false; uint32_t step = 0; } pending;
     bool sortDue = false, deferSort = false, deferRecut = false, deferExchange = false;
     bool haveArgs = false;
@@ -229,6 +238,7 @@ class ShardCore {
     int grow(int64_t needed, int64_t nKeep) {
         const int64_t c = std::max<int64_t>(needed, (int64_t)((double)cap * 1.5)) + 4096;
         if (c >= ((int64_t)1 << 31)) return fail(CPF_ERR_NOMEM, "sharded cloud: a rank would hold 2^31 particles or more");
+        zSettled = false;
         double *nx = nullptr, *ny = nullptr, *nz = nullptr; int32_t* nc = nullptr; int64_t* ng = nullptr;
         CPF_SH(dev.alloc((void**)&nx, (size_t)c * 8)); CPF_SH(dev.alloc((void**)&ny, (size_t)c * 8));
         CPF_SH(dev.alloc((void**)&nz, (size_t)c * 8)); CPF_SH(dev.alloc((void**)&nc, (size_t)c * 4));
@@ -285,6 +295,7 @@ class ShardCore {
         if (count < 0 || (count > 0 && (!sx || !sy || !sz))) return fail(CPF_ERR_ARG, "cpf_shard_set_particles_dev: bad arguments");
         CPF_SH(finishExchange());
         velValid = false;
+        zSettled = false;
         if (count > cap) CPF_SH(grow(count, 0));
         Stream s = dev.compute();
         if (count > 0) {
@@ -303,6 +314,7 @@ class ShardCore {
         const int64_t first = nTotal * rank / W, last = nTotal * (rank + 1) / W;      // (nTotal < 2^37, W <= 64: no overflow)
         const int64_t count = last - first;
         velValid = false;
+        zSettled = false;
         if (count > cap) CPF_SH(grow(count, 0));
         if (count > 0) {
             CPF_SH(dev.seed(x, y, z, first, count, lower, upper, order));
@@ -349,6 +361,7 @@ class ShardCore {
     // ---------------------------------------------------------------------------------------------- the hot loop
     int step(double dt, double D, int nCycles, unsigned flags) {
         if (nCycles < 0) return fail(CPF_ERR_ARG, "cpf_shard_step: negative cycle count");
+        flags &= ~CPF_STEP_Z_SETTLED;                     // (the shard knows better than its caller)
         if (pending.on && haveArgs && !(argDt == dt && argD == D && argFlags == flags))
             CPF_SH(finishExchange());                     // the catch-up replays the window with ONE set of arguments
         argDt = dt; argD = D; argFlags = flags; haveArgs = true;
@@ -389,7 +402,10 @@ class ShardCore {
                 if (dist && exchangeInterval) run = std::min<int64_t>(run, exchangeInterval - (int64_t)(stepIndex % (uint32_t)exchangeInterval));
                 run = std::max<int64_t>(run, 1);
             }
-            CPF_SH(dev.step(x, y, z, cell, gid, storeVel ? vel : nullptr, n, dt, D, stepIndex, (int)run, flags));
+            const unsigned zFlag = zSettled ? CPF_STEP_Z_SETTLED : 0u;
+            zSettled = false;
+            CPF_SH(dev.step(x, y, z, cell, gid, storeVel ? vel : nullptr, n, dt, D, stepIndex, (int)run, flags | zFlag));
+            if constexpr (DevReportsZ<Dev>::value) zSettled = dev.stepSettledZ();
             c += (int)run;
             if (frameZero) continue;
             stepIndex += (uint32_t)run;
@@ -534,6 +550,7 @@ class ShardCore {
         const int64_t missed = (int64_t)stepIndex - (int64_t)splitStep;
         if (!repacked[(size_t)rank]) particleSteps -= (n - nStay) * missed;      // the inactive tail was not real work
         if (nStay + nRecv > cap) CPF_SH(grow(nStay + nRecv, nStay));
+        zSettled = false;                                              // the arrivals' z has not been through this shard's flat cycle
         CPF_SH(dev.unpack(x, y, z, cell, gid, nStay, recvbuf, nRecv));
         if (missed > 0 && nRecv > 0) {
             // arrivals sit in source-rank order; those from a rank that split again at the current step are current, the

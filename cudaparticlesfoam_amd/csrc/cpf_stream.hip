@@ -119,6 +119,12 @@ constexpr int kKernArgStep0 = (int)offsetof(StreamKernArgs, step0), kKernArgSeed
 #ifndef CPF_STREAM_FLAT_ZERO_SKIP
 #define CPF_STREAM_FLAT_ZERO_SKIP 0
 #endif
+// the flat walk on a cloud whose z is settled (StreamArgs::zSettled, cpf_walk.h "flat walk"): z is neither loaded nor stored --
+// 40 of the 56 bytes per particle-step.  0 = always stream z (A/B builds).  (Skipping the z parts of the LDS traffic as well --
+// sE[2], a wave-uniform branch per write -- measured no faster: docs/experiments.md, round 7)
+#ifndef CPF_STREAM_FLAT_Z
+#define CPF_STREAM_FLAT_Z 1
+#endif
 #ifndef CPF_STREAM_SLOTS_BOX
 #define CPF_STREAM_SLOTS_BOX 9
 #endif
@@ -231,6 +237,9 @@ __device__ __forceinline__ void stream_body(
     constexpr bool LOOKUP_FIXED = LOOKUP != 0 && LOOKUP != 5 && LOOKUP != 8;
     //   9 = as 1 with the flat walk (a 2-D mesh with fewer than 128 particles per cell: refined 2-D cases)
     constexpr bool FLAT = LOOKUP == 8 || LOOKUP == 9;
+    // (FLAT) z of every live particle is a fixed point of the flat cycle: the launch leaves z in memory alone.  Wave-uniform;
+    // the landing zone is then x[64] | y[64] | cell[64], and no z is loaded or stored (the z the walk carries in registers is dead)
+    const bool zKeep = FLAT && CPF_STREAM_FLAT_Z != 0 && sa.zSettled != 0;
     constexpr bool mixed = LOOKUP == 2 || LOOKUP == 3 || LOOKUP == 5 || LOOKUP == 11;
     constexpr bool bigCells = LOOKUP == 2;
     constexpr int kGatherAhead = LOOKUP == 4 ? 3 : 0;
@@ -298,7 +307,9 @@ __device__ __forceinline__ void stream_body(
         if (t < nFull) {
             const char* s1 = (ul < 32u ? reinterpret_cast<const char*>(x + b) : reinterpret_cast<const char*>(y + b)) + (ul & 31u) * 16u;
             glds16(s1, preBase);                                               // x -> [0, 512), y -> [512, 1024)
-            if (ul < 48u) {
+            if (zKeep) {
+                if (ul < 16u) glds16(reinterpret_cast<const char*>(cell + b) + ul * 16u, preBase + 1024u);      // cell -> [1024, 1280)
+            } else if (ul < 48u) {
                 const char* s2 = ul < 32u ? reinterpret_cast<const char*>(z + b) + ul * 16u
                                           : reinterpret_cast<const char*>(cell + b) + (ul - 32u) * 16u;
                 glds16(s2, preBase + 1024u);                                   // z -> [1024, 1536), cell -> [1536, 1792)
@@ -314,10 +325,17 @@ __device__ __forceinline__ void stream_body(
         }
         const unsigned lim = nTail - 1u;
         const unsigned l = ul < lim ? ul : lim;
+        if (zKeep) {
+            const double vx = (x + b)[l], vy = (y + b)[l];
+            const int vc = (cell + b)[l];
+            sPre[ul] = vx; sPre[64 + ul] = vy;
+            reinterpret_cast<int*>(sPre + 128)[ul] = vc;
+        } else {
         const double vx = (x + b)[l], vy = (y + b)[l], vz = (z + b)[l];
         const int vc = (cell + b)[l];
         sPre[ul] = vx; sPre[64 + ul] = vy; sPre[128 + ul] = vz;
         reinterpret_cast<int*>(sPre + 192)[ul] = vc;
+        }
         if (BROWNIAN) {
             const int64_t* const g = CPF_STREAM_BROWN_KERNARG ? static_cast<const int64_t*>(kernarg_pointer<kKernArgGid>()) : gid;
             if (g != nullptr) reinterpret_cast<int64_t*>(sPre + 224)[ul] = (g + b)[l];
@@ -352,8 +370,10 @@ __device__ __forceinline__ void stream_body(
             tile = uniform32(tile);
             // ---- take the tile out of the landing zone
             const unsigned plim = tile < nFull ? 63u : nTail - 1u;      // last lane with a particle slot
-            double px = sPre[ul], py = sPre[64 + ul], pz = sPre[128 + ul];
-            int pc = reinterpret_cast<const int*>(sPre + 192)[ul];
+            double px = sPre[ul], py = sPre[64 + ul], pz = 0.0;
+            int pc;
+            if (zKeep) pc = reinterpret_cast<const int*>(sPre + 128)[ul];
+            else { pz = sPre[128 + ul]; pc = reinterpret_cast<const int*>(sPre + 192)[ul]; }
             uint64_t pid = 0;
             if (BROWNIAN) {
                 const bool haveIds = (CPF_STREAM_BROWN_KERNARG ? kernarg_pointer<kKernArgGid>() : (void*)gid) != nullptr;
@@ -410,10 +430,11 @@ __device__ __forceinline__ void stream_body(
                         async_store(vv, ul * 24u, rvx); async_store(vv + 1, ul * 24u, rvy); async_store(vv + 2, ul * 24u, rvz);
                     }
                     if (ul <= rlim) {
-                        async_store(x + b, ul * 8u, prev.x); async_store(y + b, ul * 8u, prev.y); async_store(z + b, ul * 8u, prev.z);
+                        async_store(x + b, ul * 8u, prev.x); async_store(y + b, ul * 8u, prev.y);
+                        if (!zKeep) async_store(z + b, ul * 8u, prev.z);
                         async_store(cell + b, ul * 4u, rc);
                     }
-                    younger += 4;
+                    younger += zKeep ? 3 : 4;
                 }
                 if (ntilesLeft > 0 && !(sa.debug & 2)) younger += prefetch(ntile, cp);
                 __builtin_amdgcn_sched_barrier(0);
@@ -637,7 +658,9 @@ __device__ __forceinline__ void stream_body(
                     // the requested records are older than everything the hook issued: wait for exactly them
                     if (younger >= 7) wait_vmcnt<7>();
                     else if (younger == 6) wait_vmcnt<6>();
+                    else if (younger == 5) wait_vmcnt<5>();                 // (settled z: three stores + the prefetch)
                     else if (younger >= 4) wait_vmcnt<4>();
+                    else if (younger == 3) wait_vmcnt<3>();
                     else if (younger >= 2) wait_vmcnt<2>();
                     else wait_vmcnt<0>();
 #ifdef CPF_STREAM_TIMELINE
@@ -939,7 +962,11 @@ __device__ __forceinline__ void stream_body(
             const CloudPtrs cp = kernarg_cloud_ptrs();
             double* const x = cp.x; double* const y = cp.y; double* const z = cp.z; int32_t* const cell = cp.cell;
             const double rx = sE[0][lane], ry = sE[1][lane], rz = sE[2][lane];
-            if (ul <= rlim) { (x + b)[ul] = rx; (y + b)[ul] = ry; (z + b)[ul] = rz; (cell + b)[ul] = rc; }
+            if (ul <= rlim) {
+                (x + b)[ul] = rx; (y + b)[ul] = ry;
+                if (!zKeep) (z + b)[ul] = rz;
+                (cell + b)[ul] = rc;
+            }
             if (STORE_VEL && ralive) {
                 double* vv = vel + 3 * b;
                 vv[3 * ul] = rvx; vv[3 * ul + 1] = rvy; vv[3 * ul + 2] = rvz;
@@ -1017,7 +1044,10 @@ static hipError_t launch_stream_inst(hipStream_t st, double* x, double* y, doubl
     unsigned* nxt = ss.d_grab + (size_t)((ss.parity & 1) ^ 1) * kStreamGroups * kStreamCounterStride;
     if (R * kStreamGroups > ss.hitSpillWaves) R = ss.hitSpillWaves / kStreamGroups;      // (never: the area is sized for the chip)
     if (R < 1 || ss.d_hitSpill == nullptr) return hipErrorInvalidValue;
-    StreamArgs sa = {cur, nxt, (int)R, tpc, (unsigned)bigChunks, ss.debug, ss.d_hitSpill};
+    // (the flat instantiations only: every other one streams z whatever the caller says)
+    const bool zSettled = (LF == 8 || LF == 9) && !VX && ss.zSettled;
+    StreamArgs sa = {cur, nxt, (int)R, tpc, (unsigned)bigChunks, ss.debug, ss.d_hitSpill, zSettled ? 1 : 0};
+    ss.lastLookup = VX ? -1 : LF;
     if constexpr (VX) {
         if (vf == nullptr) return hipErrorInvalidValue;
         if (ss.evStart != nullptr && ss.evStop != nullptr) {

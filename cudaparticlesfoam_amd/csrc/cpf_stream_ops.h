@@ -116,6 +116,8 @@ struct StreamArgs {
                            // each other (measured with 4-tile chunks throughout: the last wave 20 us after the median)
     int debug;             // diagnostics only (results are wrong): 1 = no stores, 2 = no loads after a wave's first tile
     double* hitSpill;      // kStreamHitSpillDoubles per workgroup: wall hit points beyond the wave's LDS pool
+    int zSettled;          // (flat walk only) z of every live particle is already a fixed point of the flat cycle: z is neither
+                           // loaded nor stored (cpf_walk.h "flat walk"; CPF_STEP_Z_SETTLED)
 };
 
 // After a streaming launch: the launch zeroed the OTHER counter set for its successor, so the sets swap roles -- but only

@@ -331,6 +331,26 @@ __device__ __forceinline__ void face_test_flat(const double4& p, int bs, const D
     }
 }
 // (S.z is left alone: fma(dT, +-0, P0.z) is P0.z)
+//
+// SETTLED Z (CPF_STEP_Z_SETTLED, StreamArgs::zSettled).  What one flat cycle does to a live particle's z is a function f of z
+// alone: the advect gives Pn.z = z + dt * u.z with u.z == +-0 and dt finite (cpf_step_dev refuses any other), disp.z = Pn.z - z,
+// E.z = z + disp.z; the walk never moves S.z; a mirror about a side wall adds -2 sd * nz with nz == +-0 (a wall is only ever a
+// side face here, and sd is finite: a lane with a non-finite x or y never meets a face, dT = fd / den is then NaN or infinite);
+// the move gives E.z, or hit.z + (E.z - hit.z) with hit.z == z.  Case by case, in round-to-nearest:
+//   * z finite and non-zero: every zero added is exact and z + (+0) == z -- f(z) = z, the same bits;
+//   * z == +0: +0 + (+-0) == +0 -- f(+0) = +0;  z == -0: disp.z = (+-0) - (-0) = +0 and -0 + (+0) == +0 -- f(-0) = +0;
+//   * z == +-inf: disp.z = inf - inf is NaN -- f(+-inf) = NaN;  z NaN: f(z) is NaN.
+// So f(f(z)) == f(z) for every z but NaN, and for a NaN as well provided the ALU maps a NaN operand to the same NaN every time
+// -- it either propagates the (quieted) operand or returns the default NaN, both idempotent -- which is all the NaN case needs:
+// no comparison of the walk reads z, x, y and the cell do not depend on it, and the argument only requires that a second
+// application give the bits the first one gave.  Lanes that are frozen or lost (cell < 0) store what they loaded, so they
+// keep their z whichever way; a lane lost DURING a cycle (no-reflect wall, five bounces) gets the move first, i.e. f(z), then
+// is frozen for good.  Hence: after one flat launch of at least one cycle that streamed z, every particle's z in memory is a
+// fixed point of f (or belongs to a particle no flat cycle steps again), and every later flat launch may leave z in memory as
+// it is -- the bits a streaming launch would have written.  What ends it: anything that writes x, y, z or cell other than a
+// sort (a sort only permutes) -- a particle set or seeded anew, a frozen particle revived by cpf_locate_initial, hand-off
+// arrivals -- and any launch that is not the flat walk (the kick, a field with a z component, the vertex advect).  Only -0 and
+// +-inf are rewritten by the first cycle; NaN needs the idempotence above, finite non-zero z needs nothing.
 template <bool ZERO_SKIP>
 __device__ __forceinline__ int trace_lds4_flat(D3& S, const D3& E, int cur, const double4* rec, int token, int& outSlot) {
     const D3 P0 = S;

@@ -61,6 +61,13 @@ typedef enum cpf_status {
                                      (cudaAdvect(..., "VertexVelocity"), cuda/particles.cu:244-313, 428-437) instead of the
                                      cell-constant one: needs cpf_set_tets + cpf_set_vertex_velocity; the same five stages in
                                      one launch of the generic walk, equal to the staged calls bit for bit */
+#define CPF_STEP_Z_SETTLED 16u    /* cpf_step_dev only (cpf_step and cpf_shard_step track it themselves and ignore the caller's):
+                                     PRECONDITION -- the arrays were last written by a cpf_step_dev call that ran the flat walk
+                                     (option "flat_walk") with at least one cycle, and nothing but a sort has written x, y, z or
+                                     cell since.  Every live particle's z is then a fixed point of the flat cycle, so a launch
+                                     that runs the flat walk neither loads nor stores z (40 instead of 56 bytes per particle);
+                                     any other launch ignores the flag.  Results are the same bits with or without it when the
+                                     precondition holds (csrc/cpf_walk.h "flat walk") */
 
 /* ---------------------------------------------------------------------------------------------
  * context
@@ -255,6 +262,8 @@ int cpf_set_seed(cpf_context* ctx, uint32_t seed);
  *                   laid out; after cpf_set_velocity_dev the note arrives asynchronously and the field counts as having one
  *                   until it has), D == 0, at least 8 particles per cell -- runs kernel 4's FLAT instantiations: four side faces with two-term dot products, no z faces, no z in the
  *                   walk.  0 = never.  Bit-identical either way (csrc/cpf_walk.h "flat walk", tests/test_gpu_parity.py)
+ *   "flat_z"        (1) the flat walk on a cloud whose z is settled (CPF_STEP_Z_SETTLED) leaves z in memory alone; 0 = it
+ *                   always loads and stores z (A/B).  Bit-identical either way
  *   "box_records"   (1) on a mesh whose cells are ALL axis-aligned boxes (cpf_mesh_box_records_host; 2:1-refined boxes with their
  *                   face groups included) kernel 4 walks 128-byte box
  *                   records -- three candidate faces per visit instead of six -- at every cloud density (measured faster than
