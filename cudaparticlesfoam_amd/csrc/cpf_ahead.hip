@@ -9,7 +9,7 @@
 // registers for the wave's tile boundary -- the moment no lane is on the current tile any more -- where the tile is
 // stored with four coalesced stores as before.  A lane can be at most one tile ahead: one that also finishes the next
 // tile's particle parks until the boundary.  Same arithmetic per particle, same record cache, same chunk dealing;
-// one cycle per launch, no Brownian kick, no stored velocity (launch_step uses step_kernel_stream for those).
+// one cycle per launch, no Brownian kick, no stored velocity (plan_step picks step_kernel_stream for those).
 //
 // Lane states: A walking the current tile's particle | B done with it (result in r*), no next particle yet |
 //              C done, walking the NEXT tile's particle ("ahead") | D done, next tile's particle finished too (parked).
@@ -385,12 +385,10 @@ static hipError_t launch_ahead_inst(hipStream_t st, double* x, double* y, double
 }
 
 // dbg: diagnostic builds (-DCPF_STREAM_TIMELINE) write per-wave times there (the caller's unused `vel` array)
-hipError_t launch_step_ahead(hipStream_t st, double* x, double* y, double* z, int32_t* cell, int64_t n, double dt, bool reflect,
+hipError_t launch_step_ahead(const StepPlan& p, hipStream_t st, double* x, double* y, double* z, int32_t* cell, int64_t n, double dt,
                              const MeshView& m, unsigned long long* counters, StreamState& ss, double* dbg) {
-    if (reflect) return counters ? launch_ahead_inst<true, true>(st, x, y, z, cell, n, dt, m, counters, ss, dbg)
-                                 : launch_ahead_inst<true, false>(st, x, y, z, cell, n, dt, m, counters, ss, dbg);
-    return counters ? launch_ahead_inst<false, true>(st, x, y, z, cell, n, dt, m, counters, ss, dbg)
-                    : launch_ahead_inst<false, false>(st, x, y, z, cell, n, dt, m, counters, ss, dbg);
+    return with_bools([&](auto R, auto ST) { return launch_ahead_inst<R, ST>(st, x, y, z, cell, n, dt, m, counters, ss, dbg); },
+                      p.reflect, p.stats);
 }
 
 }  // namespace cpf

@@ -16,6 +16,7 @@
 #include "cpf.h"
 #include "cpf_device.h"
 #include "cpf_internal.h"
+#include "cpf_walk.h"      // VertexField
 
 struct cpf_context {
     int device = 0;
@@ -688,6 +689,17 @@ int cpf_locate_initial(cpf_context* ctx, int64_t* nOutside) {
     return CPF_OK;
 }
 
+// the "VertexVelocity" cycle's tables (the cone-locate records only with "vertex_fast")
+static cpf::VertexField vertexField(const cpf_context* ctx) {
+    return {ctx->d_tetPos, ctx->d_tets, ctx->d_vertVel, ctx->tetsPerCell, ctx->vertexFast ? ctx->d_vertCone : nullptr,
+            reinterpret_cast<const double4*>(ctx->d_vertApex)};
+}
+
+// (device-scope release is all a time stamp needs; measured against the default flags: no difference)
+#ifndef CPF_TIMING_EVENT_FLAGS
+#define CPF_TIMING_EVENT_FLAGS hipEventReleaseToDevice
+#endif
+
 int cpf_step_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cell, const int64_t* gid, double* vel,
                  int64_t n, double dt, double D, uint32_t step0, int nCycles, unsigned flags) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
@@ -696,14 +708,13 @@ int cpf_step_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cel
     CPF_REQUIRE(ctx, n >= 0 && nCycles >= 0, CPF_ERR_ARG, "cpf_step: negative count");
     CPF_REQUIRE(ctx, n == 0 || (x && y && z && cell), CPF_ERR_ARG, "cpf_step: null particle array");
     CPF_REQUIRE(ctx, std::isfinite(dt) && std::isfinite(D) && D >= 0.0, CPF_ERR_ARG, "cpf_step: dt/D not finite or D < 0");
-    const bool storeVel = (flags & CPF_STEP_STORE_VEL) != 0;
-    CPF_REQUIRE(ctx, !storeVel || vel, CPF_ERR_ARG, "cpf_step: CPF_STEP_STORE_VEL needs a vel array");
+    CPF_REQUIRE(ctx, !(flags & CPF_STEP_STORE_VEL) || vel, CPF_ERR_ARG, "cpf_step: CPF_STEP_STORE_VEL needs a vel array");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
-    const bool reflect = (flags & CPF_STEP_NO_REFLECT) == 0;
     const bool vertexU = (flags & CPF_STEP_VERTEX_VELOCITY) != 0;
     CPF_REQUIRE(ctx, !vertexU || (ctx->haveVertVel && ctx->nTets == (int64_t)ctx->tetsPerCell * ctx->host.nCells), CPF_ERR_STATE,
                 "cpf_step: CPF_STEP_VERTEX_VELOCITY needs cpf_set_tets and cpf_set_vertex_velocity for the current mesh");
     const cpf::MeshView m = meshView(ctx);
+    const cpf::VertexField vf = vertexField(ctx);
     const bool fuse = (flags & CPF_STEP_FUSE_CYCLES) != 0;
     pollFieldFlag(ctx);
     // z settled: the caller's word for the first launch; after a launch, what that launch left behind -- settled behind a
@@ -714,52 +725,35 @@ int cpf_step_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cel
     const int nLaunch = fuse ? 1 : nCycles;   // fused with nCycles == 0: load+store only (bandwidth calibration)
     const int cycPerLaunch = fuse ? nCycles : 1;
     for (int c = 0; c < nLaunch; ++c) {
+        const cpf::StepPlan plan = cpf::plan_step(m, ctx->streamState, ctx->stepVariant, vertexU ? &vf : nullptr, n, cycPerLaunch, D,
+                                                  flags, ctx->stats);
         hipEvent_t e0 = nullptr, e1 = nullptr;
-        bool stamped = false;
         const bool timed = ctx->timing && (ctx->timingLaunch++ % (uint64_t)ctx->timingStride) == 0;
+        // the streaming kernels stamp the events with the dispatch's own begin / end (StepPlan::stamped); any other kernel,
+        // and a launch without particles (nothing is dispatched), is bracketed by two event records
+        const bool stamped = timed && n > 0 && plan.stamped();
         if (timed) {
             auto take = [&](hipEvent_t& ev) -> hipError_t {
                 if (!ctx->eventPool.empty()) { ev = ctx->eventPool.back(); ctx->eventPool.pop_back(); return hipSuccess; }
-                // (device-scope release is all a time stamp needs; measured against the default flags: no difference)
-#ifndef CPF_TIMING_EVENT_FLAGS
-#define CPF_TIMING_EVENT_FLAGS hipEventReleaseToDevice
-#endif
                 return hipEventCreateWithFlags(&ev, CPF_TIMING_EVENT_FLAGS);
             };
             CPF_HIP(ctx, take(e0)); CPF_HIP(ctx, take(e1));
-            // the streaming launcher stamps the events with the dispatch's own begin / end (cpf_device.h, StreamState);
-            // any other kernel is bracketed by two event records
-            stamped = vertexU ? cpf::step_vertex_streams(m, ctx->vertexFast ? ctx->d_vertCone : nullptr, ctx->tetsPerCell, ctx->stepVariant, &ctx->streamState, cycPerLaunch)
-                              : cpf::effective_step_variant(ctx->stepVariant, m, true, cycPerLaunch, ctx->streamState.coopMaxCells) == 4;
-            if (stamped) { ctx->streamState.evStart = e0; ctx->streamState.evStop = e1; }
-            else CPF_HIP(ctx, hipEventRecord(e0, ctx->stream));
+            if (!stamped) CPF_HIP(ctx, hipEventRecord(e0, ctx->stream));
         }
         ctx->lastStepN = n; ctx->lastStepCycles = cycPerLaunch;
-        ctx->streamState.zSettled = settled && ctx->streamState.flatZ != 0;
-        ctx->streamState.lastLookup = -1;
-        const hipError_t le = vertexU
-            ? cpf::launch_step_vertex(ctx->stream, x, y, z, cell, gid, vel, n, dt, D, step0 + (uint32_t)c, cycPerLaunch, ctx->seed, reflect,
-                                      storeVel, m, ctx->stats ? ctx->d_counters : nullptr, ctx->d_tetPos, ctx->d_tets, ctx->tetsPerCell,
-                                      ctx->d_vertVel, ctx->vertexFast ? ctx->d_vertCone : nullptr, ctx->d_vertApex, ctx->stepVariant, &ctx->streamState)
-            : cpf::launch_step(ctx->stream, x, y, z, cell, gid, vel, n, dt, D, step0 + (uint32_t)c, cycPerLaunch, ctx->seed,
-                               reflect, storeVel, m, ctx->stats ? ctx->d_counters : nullptr, ctx->stepVariant,
-                               &ctx->streamState);
+        const hipError_t le = cpf::launch_step(plan, ctx->stream, x, y, z, cell, gid, vel, n, dt, D, step0 + (uint32_t)c, cycPerLaunch,
+                                               ctx->seed, m, ctx->stats ? ctx->d_counters : nullptr, vertexU ? &vf : nullptr,
+                                               ctx->streamState, settled, stamped ? e0 : nullptr, stamped ? e1 : nullptr);
         if (le != hipSuccess) {
-            // a launch that did not go out (occupancy query, tile count, missing spill area): its time stamps must not be
-            // left for the next, unrelated launch to take, and the two events go back to the pool instead of leaking
-            ctx->streamState.evStart = ctx->streamState.evStop = nullptr;
+            // a launch that did not go out (occupancy query, tile count, missing spill area): the two events go back to the
+            // pool instead of leaking
             if (e0) ctx->eventPool.push_back(e0);
             if (e1) ctx->eventPool.push_back(e1);
         }
-        ctx->streamState.zSettled = false;
         CPF_HIP(ctx, le);
-        if (n > 0 && cycPerLaunch > 0) settled = !vertexU && (ctx->streamState.lastLookup == 8 || ctx->streamState.lastLookup == 9);
+        if (n > 0 && cycPerLaunch > 0) settled = plan.flat();
         if (timed) {
             if (!stamped) CPF_HIP(ctx, hipEventRecord(e1, ctx->stream));
-            else if (ctx->streamState.evStart != nullptr) {  // (cannot happen: the streaming launcher always takes them)
-                ctx->streamState.evStart = ctx->streamState.evStop = nullptr;
-                CPF_HIP(ctx, hipEventRecord(e0, ctx->stream)); CPF_HIP(ctx, hipEventRecord(e1, ctx->stream));
-            }
             ctx->events.emplace_back(e0, e1);
         }
     }
@@ -1067,30 +1061,30 @@ int cpf_step_kernel_name(cpf_context* ctx, double D, unsigned flags, char* buf, 
     CPF_REQUIRE(ctx, ctx && buf && bufBytes > 0, CPF_ERR_ARG, "null argument");
     CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_step_kernel_name: call cpf_set_mesh first");
     const cpf::MeshView m = meshView(ctx);
+    const cpf::VertexField vf = vertexField(ctx);
     pollFieldFlag(ctx);
-    // (a fused launch's kernel depends on how many cycles it fuses: the most recent launch's count stands in)
-    const int v = cpf::effective_step_variant(ctx->stepVariant, m, true, (flags & CPF_STEP_FUSE_CYCLES) ? ctx->lastStepCycles : 1,
-                                              ctx->streamState.coopMaxCells);
+    // the plan of a launch with these flags.  A fused launch's kernel depends on how many cycles it fuses, the streaming
+    // kernels' record lookup on the particle count: the most recent launch's stand in, else the owned cloud's (the
+    // "VertexVelocity" cycle's also after a launch without particles)
+    const bool vertexU = (flags & CPF_STEP_VERTEX_VELOCITY) != 0;
+    const int64_t n = (vertexU ? ctx->lastStepN > 0 : ctx->lastStepN >= 0) ? ctx->lastStepN : ctx->n;
+    const cpf::StepPlan p = cpf::plan_step(m, ctx->streamState, ctx->stepVariant, vertexU ? &vf : nullptr, n,
+                                           (flags & CPF_STEP_FUSE_CYCLES) ? ctx->lastStepCycles : 1, D, flags, ctx->stats);
     const char* b[2] = {"false", "true"};
-    const bool brown = D > 0.0, reflect = (flags & CPF_STEP_NO_REFLECT) == 0, sv = (flags & CPF_STEP_STORE_VEL) != 0;
     char tmp[192];
-    if ((flags & CPF_STEP_VERTEX_VELOCITY) &&
-        cpf::step_vertex_streams(m, ctx->vertexFast ? ctx->d_vertCone : nullptr, ctx->tetsPerCell, ctx->stepVariant, &ctx->streamState,
-                                 (flags & CPF_STEP_FUSE_CYCLES) ? ctx->lastStepCycles : 1))
-        snprintf(tmp, sizeof tmp, "cpf::step_kernel_stream_vertex<%s, %s, %s, %s, %d> (cone locate)", b[brown], b[reflect], b[sv],
-                 b[ctx->stats ? 1 : 0], cpf::stream_vertex_lookup_mode(ctx->lastStepN > 0 ? ctx->lastStepN : ctx->n, m, ctx->streamState));
-    else if (flags & CPF_STEP_VERTEX_VELOCITY)
-        snprintf(tmp, sizeof tmp, "cpf::step_kernel_vertex<%s, %s, %s> (%s)", b[brown], b[reflect], b[sv],
-                 (ctx->vertexFast && ctx->d_vertCone) ? "cone locate" : (ctx->d_vertCone || ctx->vertConeWhy.empty() ? "all tets" : ("all tets: " + ctx->vertConeWhy).c_str()));
-    else if (v == 5 && !brown && !sv && !(flags & CPF_STEP_FUSE_CYCLES))
-        snprintf(tmp, sizeof tmp, "cpf::step_kernel_ahead<%s, %s>", b[reflect], b[ctx->stats]);
-    else if (v == 4 || v == 5) {
-        // (the record lookup is picked per launch from the particle count: the most recent launch's, else the owned cloud's)
-        const int lf = cpf::stream_lookup_mode(ctx->lastStepN >= 0 ? ctx->lastStepN : ctx->n, m, ctx->streamState, brown);
-        snprintf(tmp, sizeof tmp, "cpf::step_kernel_stream<%s, %s, %s, %s, %d>", b[brown], b[reflect], b[sv], b[ctx->stats], lf);
-    }
-    else if (v == 3) snprintf(tmp, sizeof tmp, "cpf::step_kernel_coop<%s, %s, %s, %s>", b[brown], b[reflect], b[sv], b[ctx->stats]);
-    else snprintf(tmp, sizeof tmp, "cpf::step_kernel<%d, %s, %s, %s>", v, b[brown], b[reflect], b[sv]);
+    if (p.kernel == cpf::StepPlan::kStreamVertex)
+        snprintf(tmp, sizeof tmp, "cpf::step_kernel_stream_vertex<%s, %s, %s, %s, %d> (cone locate)", b[p.brown], b[p.reflect],
+                 b[p.storeVel], b[p.stats], p.lookup);
+    else if (p.kernel == cpf::StepPlan::kVertex)
+        snprintf(tmp, sizeof tmp, "cpf::step_kernel_vertex<%s, %s, %s> (%s)", b[p.brown], b[p.reflect], b[p.storeVel],
+                 p.cone ? "cone locate" : (ctx->d_vertCone || ctx->vertConeWhy.empty() ? "all tets" : ("all tets: " + ctx->vertConeWhy).c_str()));
+    else if (p.kernel == cpf::StepPlan::kAhead)
+        snprintf(tmp, sizeof tmp, "cpf::step_kernel_ahead<%s, %s>", b[p.reflect], b[p.stats]);
+    else if (p.kernel == cpf::StepPlan::kStream)
+        snprintf(tmp, sizeof tmp, "cpf::step_kernel_stream<%s, %s, %s, %s, %d>", b[p.brown], b[p.reflect], b[p.storeVel], b[p.stats], p.lookup);
+    else if (p.kernel == cpf::StepPlan::kCoop)
+        snprintf(tmp, sizeof tmp, "cpf::step_kernel_coop<%s, %s, %s, %s>", b[p.brown], b[p.reflect], b[p.storeVel], b[p.stats]);
+    else snprintf(tmp, sizeof tmp, "cpf::step_kernel<%d, %s, %s, %s>", (int)p.kernel, b[p.brown], b[p.reflect], b[p.storeVel]);
     snprintf(buf, bufBytes, "%s", tmp);
     return CPF_OK;
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "cpf.h"
 #include "cpf_internal.h"   // kGroupBase
@@ -43,11 +44,6 @@ constexpr size_t kStreamGrabBytes = 2 * 256 * 16 * sizeof(unsigned);
 constexpr int kStreamHitSpillDoubles = 3 * 64;          // x[64] | y[64] | z[64] per wave
 struct StreamState {
     unsigned* d_grab = nullptr;
-    // timing of ONE launch (cpf_timing_enable): set by the caller before launch_step, taken (and cleared) by the streaming
-    // launcher, which hands them to hipExtLaunchKernelGGL -- start and stop are then the dispatch's own begin / end time
-    // stamps, what rocprofv3's kernel trace reports, instead of events recorded around the launch (which also time the gap
-    // an event record puts between two otherwise back-to-back kernels: 5 % on a 0.12 ms kernel)
-    hipEvent_t evStart = nullptr, evStop = nullptr;
     double* d_hitSpill = nullptr;   // wall hit points that do not fit a wave's LDS pool: kStreamHitSpillDoubles per wave slot (cpf_stream.hip)
     int hitSpillWaves = 0;          // wave slots d_hitSpill has room for (the launcher never starts more single-wave workgroups)
     int parity = 0;
@@ -72,47 +68,59 @@ struct StreamState {
     // out, read back behind it): with MeshView::zSide0 and without the kick the FLAT instantiation runs (cpf_walk.h "flat walk")
     bool flatField = false;
     int flat = 1;             // "flat_walk": 0 = never (diagnostics; bit-identical either way)
-    // set by the caller before a launch: the cloud's z is settled (CPF_STEP_Z_SETTLED) -- the flat instantiations then leave z in
-    // memory alone (StreamArgs::zSettled); "flat_z" 0 keeps this false
-    bool zSettled = false;
     int flatZ = 1;            // "flat_z": 0 = the flat instantiations always stream z (A/B; bit-identical either way)
-    // set by the streaming launcher: the LOOKUP instantiation it launched (8 / 9: the flat walk), -1 the vertex kernel
-    int lastLookup = -1;
 };
 
-hipError_t launch_step_ahead(hipStream_t st, double* x, double* y, double* z, int32_t* cell, int64_t n, double dt, bool reflect,
-                             const MeshView& m, unsigned long long* counters, StreamState& ss, double* dbg);
-int stream_lookup_mode(int64_t n, const MeshView& m, const StreamState& ss, bool brown = true);    // 0 loop, 1 fixed compare, 4 fixed compare for sparse clouds, 2 / 3 fixed compare + mixed records with / without header records, 5 loop + mixed records, 6 fixed compare + box records
-// the variant launch_step really runs for a requested one (non-hex meshes: generic; record-offset limits)
-int effective_step_variant(int variant, const MeshView& m, bool haveStream, int cyclesPerLaunch, int coopMaxCells);
+constexpr int kCoopMaxCells = 1 << 24;     // 32-bit record byte offsets in step_kernel_coop (plan_step falls back above that)
 constexpr int kFusedCoopCycles = 1 << 30;  // fused launches of this many cycles or more run the wave-cooperative kernel: never since round 4
                                           // (round 3, 8: the streaming kernel was 4 % faster per cycle at 3 fused cycles, 2 % slower at 8; with
-                                          // the flat walk and box records it is 5-30 % faster at 8 and 16 -- cpf_kernels.hip, effective_step_variant)
-// ss == nullptr: the streaming variant is not available (falls back to the wave-cooperative kernel)
-hipError_t launch_step(hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid,
-                       double* vel, int64_t n, double dt, double D, uint32_t step0, int nCyc, uint32_t seed,
-                       bool reflect, bool storeVel, const MeshView& m, unsigned long long* counters, int variant,
-                       StreamState* ss);
-// the fused cycle with the "VertexVelocity" advect mode (generic walk; CPF_STEP_VERTEX_VELOCITY)
-hipError_t launch_step_vertex(hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid,
-                              double* vel, int64_t n, double dt, double D, uint32_t step0, int nCyc, uint32_t seed,
-                              bool reflect, bool storeVel, const MeshView& m, unsigned long long* counters,
-                              const double* pos, const int32_t* tets, int tetsPerCell, const double* vertVel, const double* cone,
-                              const double* apex, int variant, StreamState* ss);
-// does launch_step_vertex stream (step_kernel_stream_vertex) or run step_kernel_vertex, for these arguments?
-bool step_vertex_streams(const MeshView& m, const double* cone, int tetsPerCell, int variant, const StreamState* ss, int nCyc);
+                                          // the flat walk and box records it is 5-30 % faster at 8 and 16 -- cpf_stream.hip, plan_step)
 struct VertexField;                  // cpf_walk.h
-// the "VertexVelocity" cycle on the streaming kernel (all-hex meshes with cone-locate tables; else launch_step_vertex's own kernel)
-bool stream_vertex_capable(const MeshView& m);
-int stream_vertex_lookup_mode(int64_t n, const MeshView& m, const StreamState& ss);
-hipError_t launch_step_stream_vertex(hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid,
-                                     double* vel, int64_t n, double dt, double sigma, uint32_t step0, int nCyc, uint32_t seed,
-                                     bool brown, bool reflect, bool storeVel, const MeshView& m, unsigned long long* counters,
-                                     StreamState& ss, const VertexField& vf);
-hipError_t launch_step_stream(hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid,
+
+// What one step launch runs: plan_step (cpf_stream.hip) decides, launch_step runs it, cpf_step_dev times it and learns from
+// it whether the launch settles z, cpf_step_kernel_name prints it.
+struct StepPlan {
+    // kGeneric .. kAhead: the kernels of the step variants (cpf_walk.h kVariant*, "step_variant"); kVertex, kStreamVertex: the
+    // "VertexVelocity" cycle (CPF_STEP_VERTEX_VELOCITY) on step_kernel_vertex / step_kernel_stream_vertex
+    enum Kernel { kGeneric = 0, kFixed = 1, kFixedScalar = 2, kCoop = 3, kStream = 4, kAhead = 5, kVertex, kStreamVertex };
+    Kernel kernel = kGeneric;
+    bool brown = false, reflect = false, storeVel = false, stats = false;   // the template flags
+    // the streaming kernels' LOOKUP: 0 loop, 1 fixed compare, 4 fixed compare for sparse clouds, 2 / 3 fixed compare + mixed records
+    // with / without header records, 5 loop + mixed records, 6 fixed compare + box records, 11 box records + face groups, 8 / 9 flat walk
+    int lookup = -1;
+    bool cone = false;    // the vertex kernels: cone locate (else all tets)
+    // timed, the streaming kernels take the events to hipExtLaunchKernelGGL -- start and stop are then the dispatch's own begin
+    // / end time stamps, what rocprofv3's kernel trace reports, instead of events recorded around the launch (which also time
+    // the gap an event record puts between two otherwise back-to-back kernels: 5 % on a 0.12 ms kernel)
+    bool stamped() const { return kernel == kStream || kernel == kStreamVertex; }
+    // the flat walk: every live particle's z is settled behind it (CPF_STEP_Z_SETTLED)
+    bool flat() const { return kernel == kStream && (lookup == 8 || lookup == 9); }
+};
+// vf: the "VertexVelocity" cycle's tables (null: the cell-constant cycle); stats: statistics counters are on
+StepPlan plan_step(const MeshView& m, const StreamState& ss, int variant, const VertexField* vf, int64_t n, int nCyc, double D,
+                   unsigned flags, bool stats);
+// zSettled: the cloud's z is settled (CPF_STEP_Z_SETTLED; the flat instantiations then leave z in memory alone, StreamArgs::zSettled);
+// evStart / evStop: the time stamps of a plan.stamped() launch (null: untimed)
+hipError_t launch_step(const StepPlan& p, hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid,
+                       double* vel, int64_t n, double dt, double D, uint32_t step0, int nCyc, uint32_t seed, const MeshView& m,
+                       unsigned long long* counters, const VertexField* vf, StreamState& ss, bool zSettled, hipEvent_t evStart,
+                       hipEvent_t evStop);
+// launch_step's kernels in the other translation units
+hipError_t launch_step_stream(const StepPlan& p, hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid,
                               double* vel, int64_t n, double dt, double sigma, uint32_t step0, int nCyc, uint32_t seed,
-                              bool brown, bool reflect, bool storeVel, const MeshView& m, unsigned long long* counters,
-                              StreamState& ss);
+                              const MeshView& m, unsigned long long* counters, const VertexField* vf, StreamState& ss, bool zSettled,
+                              hipEvent_t evStart, hipEvent_t evStop);
+hipError_t launch_step_ahead(const StepPlan& p, hipStream_t st, double* x, double* y, double* z, int32_t* cell, int64_t n, double dt,
+                             const MeshView& m, unsigned long long* counters, StreamState& ss, double* dbg);
+// f(std::bool_constant<b>{}...) for the run-time bools b...: a launcher's flags as template arguments, one instantiation per combination
+template <class F>
+decltype(auto) with_bools(F&& f) { return f(); }
+template <class F, class... Bs>
+decltype(auto) with_bools(F&& f, bool b, Bs... bs) {
+    if (b) return with_bools([&](auto... c) -> decltype(auto) { return f(std::true_type{}, c...); }, bs...);
+    return with_bools([&](auto... c) -> decltype(auto) { return f(std::false_type{}, c...); }, bs...);
+}
+
 hipError_t launch_locate_initial(hipStream_t st, const double* x, const double* y, const double* z, int32_t* cell,
                                  int64_t n, const MeshView& m, const GridView& g);
 hipError_t launch_seed_box(hipStream_t st, double* x, double* y, double* z, int64_t first, int64_t n,

@@ -160,7 +160,6 @@ __global__ __launch_bounds__(kBlock) void step_kernel_vertex(double* __restrict_
 // nest of particle_cycles (<= 50 hops per segment, <= 5 reflections), in the same arithmetic order.
 // ------------------------------------------------------------------------------------------------
 constexpr int kCoopSlots = 4;
-constexpr int kCoopMaxCells = 1 << 24;       // 32-bit record byte offsets in step_kernel_coop (launch_step falls back above that)
 #ifndef CPF_COOP_BLOCK
 #define CPF_COOP_BLOCK 128
 #endif
@@ -353,149 +352,44 @@ __global__ __launch_bounds__(kCoopBlock, (CoopOccupancy<BROWNIAN, STORE_VEL, STA
     if (STATS) flush_stats(st, counters, sCnt);
 }
 
-template <int V, bool B, bool R>
-static void launch_step_sv(bool storeVel, dim3 grid, hipStream_t st, double* x, double* y, double* z, int32_t* cell,
-                           const int64_t* gid, double* vel, int64_t n, double dt, double sigma, uint32_t step0,
-                           int nCyc, uint32_t seed, const MeshView& m, unsigned long long* counters) {
-    if (storeVel)
-        hipLaunchKernelGGL((step_kernel<V, B, R, true>), grid, dim3(kBlock), 0, st, x, y, z, cell, gid, vel, n, dt,
-                           sigma, step0, nCyc, seed, m, counters);
-    else
-        hipLaunchKernelGGL((step_kernel<V, B, R, false>), grid, dim3(kBlock), 0, st, x, y, z, cell, gid, vel, n, dt,
-                           sigma, step0, nCyc, seed, m, counters);
-}
-
-template <bool B, bool R>
-static void launch_step_coop_sv(bool storeVel, dim3 grid, hipStream_t st, double* x, double* y, double* z,
-                                int32_t* cell, const int64_t* gid, double* vel, int64_t n, double dt, double sigma,
-                                uint32_t step0, int nCyc, uint32_t seed, const MeshView& m,
-                                unsigned long long* counters) {
-    const dim3 cgrid((unsigned)((n + kCoopBlock - 1) / kCoopBlock));
-    (void)grid;
-    // statistics are a template flag here: the four per-lane counters cost registers, and registers are waves
-#define CPF_LAUNCH_COOP(SV, ST)                                                                                       \
-    hipLaunchKernelGGL((step_kernel_coop<B, R, SV, ST>), cgrid, dim3(kCoopBlock), 0, st, x, y, z, cell, gid, vel, n, dt, \
-                       sigma, step0, nCyc, seed, m, counters)
-    if (storeVel) { if (counters) CPF_LAUNCH_COOP(true, true); else CPF_LAUNCH_COOP(true, false); }
-    else { if (counters) CPF_LAUNCH_COOP(false, true); else CPF_LAUNCH_COOP(false, false); }
-#undef CPF_LAUNCH_COOP
-}
-
-template <int V>
-static void launch_step_v(bool brown, bool reflect, bool storeVel, dim3 grid, hipStream_t st, double* x, double* y,
-                          double* z, int32_t* cell, const int64_t* gid, double* vel, int64_t n, double dt,
-                          double sigma, uint32_t step0, int nCyc, uint32_t seed, const MeshView& m,
-                          unsigned long long* counters) {
-    if (brown) {
-        if (reflect) launch_step_sv<V, true, true>(storeVel, grid, st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters);
-        else launch_step_sv<V, true, false>(storeVel, grid, st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters);
-    } else {
-        if (reflect) launch_step_sv<V, false, true>(storeVel, grid, st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters);
-        else launch_step_sv<V, false, false>(storeVel, grid, st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters);
-    }
-}
-
-int effective_step_variant(int variant, const MeshView& m, bool haveStream, int cyclesPerLaunch, int coopMaxCells) {
-    if (coopMaxCells <= 0 || coopMaxCells > kCoopMaxCells) coopMaxCells = kCoopMaxCells;
-    if (!m.allHex) {
-        // not all-hex: the streaming kernel where the mesh layer built mixed records for it (few cells with more than six
-        // faces: they take the CSR walk inside the kernel), else the generic CSR walk; the other variants need 6 faces per cell
-        const bool wantsStream = variant == kVariantAuto || variant == kVariantStream || variant == kVariantCoop;
-        return (m.mixed && m.cellRec && haveStream && wantsStream) ? kVariantStream : kVariantGeneric;
-    }
-    // Several cycles fused into one launch (CPF_STEP_FUSE_CYCLES: what advect.H does between two output points): the
-    // particle stream is loaded and stored once per launch, so hiding it behind the walk buys nothing, and the
-    // wave-cooperative kernel's 8 waves per SIMD (the streaming kernel: 7) win -- by less since round 3, measured per
-    // cycle on pitzDaily: 3 cycles per launch the streaming kernel is 4 % FASTER (0.0982 vs 0.1026 ms; with the Brownian
-    // kick 0.181 vs 0.190), 8 cycles 2 % slower (0.0930 vs 0.0911; kick: equal).  Round 2: 5 % slower at 3, 10 % at 8.
-    // (Final build of round 3, exact face normals: 8 cycles 0.0865 vs 0.0846 ms per cycle, with the kick 0.167 vs 0.172.)
-    // Round 4: the streaming kernel's flat walk and box records turned that around -- 8 cycles per launch, pitzDaily 0.0799 vs
-    // 0.0863 ms per cycle (16 cycles: 0.0783 vs 0.0822), with the kick 0.159 vs 0.169, TJunction 0.0855 vs 0.1216 -- and
-    // kFusedCoopCycles went up to "never" (the switch stays for builds without the streaming kernel).
-    if (variant == kVariantAuto)
-        variant = (haveStream && !(cyclesPerLaunch >= kFusedCoopCycles && m.nCells <= coopMaxCells)) ? kVariantStream : kVariantCoop;
-    if ((variant == kVariantStream || variant == kVariantAhead) && !haveStream) variant = kVariantCoop;
-    // the wave-cooperative kernel addresses records with a 32-bit byte offset (256 B x 2^24 cells)
-    if (variant == kVariantCoop && m.nCells > coopMaxCells) variant = haveStream ? kVariantStream : kVariantGeneric;
-#ifndef CPF_EXPERIMENTS
-    // (variants 1, 2 and 5 are not in this build: cpf_set_option refuses them; belt and braces)
-    if (variant == kVariantFixed || variant == kVariantFixedScalar) variant = kVariantCoop;
-    if (variant == kVariantAhead) variant = haveStream ? kVariantStream : kVariantCoop;
-#endif
-    return variant;
-}
-
-hipError_t launch_step(hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid,
-                       double* vel, int64_t n, double dt, double D, uint32_t step0, int nCyc, uint32_t seed,
-                       bool reflect, bool storeVel, const MeshView& m, unsigned long long* counters, int variant,
-                       StreamState* ss) {
+hipError_t launch_step(const StepPlan& p, hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid,
+                       double* vel, int64_t n, double dt, double D, uint32_t step0, int nCyc, uint32_t seed, const MeshView& m,
+                       unsigned long long* counters, const VertexField* vf, StreamState& ss, bool zSettled, hipEvent_t evStart,
+                       hipEvent_t evStop) {
     if (n <= 0) return hipSuccess;
+    const double sigma = p.brown ? sqrt(2.00 * D * dt) : 0.0;   // particles.cu:564
+    if (p.kernel == StepPlan::kStream || p.kernel == StepPlan::kStreamVertex)
+        return launch_step_stream(p, st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, vf, ss, zSettled,
+                                  evStart, evStop);
+    if (p.kernel == StepPlan::kVertex && vf == nullptr) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-    const bool brown = D > 0.0;
-    const double sigma = brown ? sqrt(2.00 * D * dt) : 0.0;   // particles.cu:564
-    variant = effective_step_variant(variant, m, ss != nullptr, nCyc, ss ? ss->coopMaxCells : 0);
-    switch (variant) {
+    const auto walk = [&](auto V) {
+        with_bools([&](auto B, auto R, auto SV) {
+            hipLaunchKernelGGL((step_kernel<V, B, R, SV>), grid, dim3(kBlock), 0, st, x, y, z, cell, gid, vel, n, dt, sigma, step0,
+                               nCyc, seed, m, counters);
+        }, p.brown, p.reflect, p.storeVel);
+    };
+    switch (p.kernel) {
 #ifdef CPF_EXPERIMENTS
-        case kVariantAhead:
-            // lanes that run ahead into the next tile: one plain cycle per launch only; everything else streams
-            if (!brown && !storeVel && nCyc == 1) return launch_step_ahead(st, x, y, z, cell, n, dt, reflect, m, counters, *ss, vel);
-            [[fallthrough]];
+        case StepPlan::kAhead: return launch_step_ahead(p, st, x, y, z, cell, n, dt, m, counters, ss, vel);
+        case StepPlan::kFixed: walk(std::integral_constant<int, kVariantFixed>{}); break;
+        case StepPlan::kFixedScalar: walk(std::integral_constant<int, kVariantFixedScalar>{}); break;
 #endif
-        case kVariantStream:
-            return launch_step_stream(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, brown, reflect, storeVel, m,
-                                      counters, *ss);
-#ifdef CPF_EXPERIMENTS
-        case kVariantFixed:
-            launch_step_v<kVariantFixed>(brown, reflect, storeVel, grid, st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters);
+        case StepPlan::kCoop:
+            // statistics are a template flag here: the four per-lane counters cost registers, and registers are waves
+            with_bools([&](auto B, auto R, auto SV, auto ST) {
+                hipLaunchKernelGGL((step_kernel_coop<B, R, SV, ST>), dim3((unsigned)((n + kCoopBlock - 1) / kCoopBlock)),
+                                   dim3(kCoopBlock), 0, st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters);
+            }, p.brown, p.reflect, p.storeVel, p.stats);
             break;
-        case kVariantFixedScalar:
-            launch_step_v<kVariantFixedScalar>(brown, reflect, storeVel, grid, st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters);
+        case StepPlan::kVertex:
+            with_bools([&](auto B, auto R, auto SV) {
+                hipLaunchKernelGGL((step_kernel_vertex<B, R, SV>), grid, dim3(kBlock), 0, st, x, y, z, cell, gid, vel, n, dt, sigma,
+                                   step0, nCyc, seed, m, *vf, counters);
+            }, p.brown, p.reflect, p.storeVel);
             break;
-#endif
-        case kVariantCoop:
-            if (brown) {
-                if (reflect) launch_step_coop_sv<true, true>(storeVel, grid, st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters);
-                else launch_step_coop_sv<true, false>(storeVel, grid, st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters);
-            } else {
-                if (reflect) launch_step_coop_sv<false, true>(storeVel, grid, st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters);
-                else launch_step_coop_sv<false, false>(storeVel, grid, st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters);
-            }
-            break;
-        default:
-            launch_step_v<kVariantGeneric>(brown, reflect, storeVel, grid, st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters);
+        default: walk(std::integral_constant<int, kVariantGeneric>{});
     }
-    return hipGetLastError();
-}
-
-// the streaming kernel takes the cycle where it would take the cell-constant one (variant 4: -1 on a mesh with cell records),
-// the decomposition is admitted to the cone locate (its advect never fails there) and the mesh is all-hex
-// (twelve tets a cell -- the reference's only decomposition, src/initCuda.H:64 -- is what the kernel's staged locate is built for)
-bool step_vertex_streams(const MeshView& m, const double* cone, int tetsPerCell, int variant, const StreamState* ss, int nCyc) {
-    return cone != nullptr && tetsPerCell == 12 && ss != nullptr && stream_vertex_capable(m) &&
-           effective_step_variant(variant, m, true, nCyc, ss->coopMaxCells) == kVariantStream;
-}
-
-hipError_t launch_step_vertex(hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid,
-                              double* vel, int64_t n, double dt, double D, uint32_t step0, int nCyc, uint32_t seed,
-                              bool reflect, bool storeVel, const MeshView& m, unsigned long long* counters,
-                              const double* pos, const int32_t* tets, int tetsPerCell, const double* vertVel, const double* cone,
-                              const double* apex, int variant, StreamState* ss) {
-    if (n <= 0) return hipSuccess;
-    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-    const bool brown = D > 0.0;
-    const double sigma = brown ? sqrt(2.00 * D * dt) : 0.0;   // particles.cu:564
-    const VertexField vf{pos, tets, vertVel, tetsPerCell, cone, reinterpret_cast<const double4*>(apex)};
-    if (step_vertex_streams(m, cone, tetsPerCell, variant, ss, nCyc))
-        return launch_step_stream_vertex(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, brown, reflect, storeVel, m, counters, *ss, vf);
-#define CPF_VTX(B, R, SV) hipLaunchKernelGGL((step_kernel_vertex<B, R, SV>), grid, dim3(kBlock), 0, st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, vf, counters)
-    if (brown) {
-        if (reflect) { if (storeVel) CPF_VTX(true, true, true); else CPF_VTX(true, true, false); }
-        else { if (storeVel) CPF_VTX(true, false, true); else CPF_VTX(true, false, false); }
-    } else {
-        if (reflect) { if (storeVel) CPF_VTX(false, true, true); else CPF_VTX(false, true, false); }
-        else { if (storeVel) CPF_VTX(false, false, true); else CPF_VTX(false, false, false); }
-    }
-#undef CPF_VTX
     return hipGetLastError();
 }
 

@@ -1011,7 +1011,7 @@ template <bool B, bool R_, bool SV, bool ST, int LF, bool VX = false>
 static hipError_t launch_stream_inst(hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid,
                                      double* vel, int64_t n, double dt, double sigma, uint32_t step0, int nCyc,
                                      uint32_t seed, const MeshView& m, unsigned long long* counters, StreamState& ss,
-                                     const VertexField* vf = nullptr) {
+                                     const VertexField* vf, bool settled, hipEvent_t evStart, hipEvent_t evStop) {
     static int wavesPerCU = 0;                       // per instantiation; benign race (same value)
     if (wavesPerCU == 0) {
         int nb = 0;
@@ -1044,40 +1044,43 @@ static hipError_t launch_stream_inst(hipStream_t st, double* x, double* y, doubl
     unsigned* nxt = ss.d_grab + (size_t)((ss.parity & 1) ^ 1) * kStreamGroups * kStreamCounterStride;
     if (R * kStreamGroups > ss.hitSpillWaves) R = ss.hitSpillWaves / kStreamGroups;      // (never: the area is sized for the chip)
     if (R < 1 || ss.d_hitSpill == nullptr) return hipErrorInvalidValue;
-    // (the flat instantiations only: every other one streams z whatever the caller says)
-    const bool zSettled = (LF == 8 || LF == 9) && !VX && ss.zSettled;
+    // (the flat instantiations only: every other one streams z whatever the caller says; "flat_z" 0: they stream it too)
+    const bool zSettled = (LF == 8 || LF == 9) && !VX && settled && ss.flatZ != 0;
     StreamArgs sa = {cur, nxt, (int)R, tpc, (unsigned)bigChunks, ss.debug, ss.d_hitSpill, zSettled ? 1 : 0};
-    ss.lastLookup = VX ? -1 : LF;
     if constexpr (VX) {
         if (vf == nullptr) return hipErrorInvalidValue;
-        if (ss.evStart != nullptr && ss.evStop != nullptr) {
-            hipExtLaunchKernelGGL((step_kernel_stream_vertex<B, R_, SV, ST, LF>), dim3((unsigned)(R * kStreamGroups)), dim3(64), 0, st, ss.evStart,
-                                  ss.evStop, 0, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa, *vf);
-            ss.evStart = ss.evStop = nullptr;
-        } else
+        if (evStart != nullptr && evStop != nullptr)
+            hipExtLaunchKernelGGL((step_kernel_stream_vertex<B, R_, SV, ST, LF>), dim3((unsigned)(R * kStreamGroups)), dim3(64), 0, st, evStart,
+                                  evStop, 0, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa, *vf);
+        else
         hipLaunchKernelGGL((step_kernel_stream_vertex<B, R_, SV, ST, LF>), dim3((unsigned)(R * kStreamGroups)), dim3(64), 0, st, x, y, z, cell,
                            gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa, *vf);
         return stream_launch_done(st, ss);
     } else {
-    if (ss.evStart != nullptr && ss.evStop != nullptr) {
-        hipExtLaunchKernelGGL((step_kernel_stream<B, R_, SV, ST, LF>), dim3((unsigned)(R * kStreamGroups)), dim3(64), 0, st, ss.evStart,
-                              ss.evStop, 0, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa);
-        ss.evStart = ss.evStop = nullptr;                    // taken
-    } else
+    if (evStart != nullptr && evStop != nullptr)
+        hipExtLaunchKernelGGL((step_kernel_stream<B, R_, SV, ST, LF>), dim3((unsigned)(R * kStreamGroups)), dim3(64), 0, st, evStart,
+                              evStop, 0, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa);
+    else
     hipLaunchKernelGGL((step_kernel_stream<B, R_, SV, ST, LF>), dim3((unsigned)(R * kStreamGroups)), dim3(64), 0, st, x, y, z, cell,
                        gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa);
     return stream_launch_done(st, ss);
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// which step kernel a launch runs (StepPlan, cpf_device.h)
+// ------------------------------------------------------------------------------------------------
 // few particles per cell => many distinct cells per 64-particle tile => the fixed tag compare
-int stream_lookup_mode(int64_t n, const MeshView& m, const StreamState& ss, bool brown) {
+static int stream_lookup_mode(int64_t n, const MeshView& m, const StreamState& ss, bool brown, bool vertex) {
     // particles per cell that HOLDS particles, if the last sort counted them for a cloud of about this size (StreamState)
     int64_t cells = m.nCells;
     if (ss.densityLookup && ss.occupiedHost != nullptr) {
         const int64_t occ = (int64_t)ss.occupiedHost[0], live = (int64_t)ss.occupiedHost[1];
         if (occ > 0 && occ <= cells && live > 0 && live <= 2 * n && n <= 2 * live) cells = occ;
     }
+    // the "VertexVelocity" cycle: the loop or the fixed lookup on the 256-byte records (no flat walk: the interpolated velocity
+    // may have a z component whatever the cell field says)
+    if (vertex) return n < 128 * cells ? 1 : 0;
     // not all-hex: with / without big cells (more than six slots); without them and with many particles per cell, the loop lookup
     // (every cell a box although the mesh has face groups -- 2:1-refined boxes: box records with group slots, 11)
     if (m.mixed == 1 && m.boxRec != nullptr && m.zThin == 0 && ss.lookup < 0) return 11;
@@ -1095,66 +1098,82 @@ int stream_lookup_mode(int64_t n, const MeshView& m, const StreamState& ss, bool
     return flat ? 8 : 0;
 }
 
-// the "VertexVelocity" cycle streams on all-hex meshes with the loop or the fixed lookup on the 256-byte records (no flat walk:
-// the interpolated velocity may have a z component whatever the cell field says; mixed meshes keep step_kernel_vertex)
-bool stream_vertex_capable(const MeshView& m) { return m.mixed == 0 && m.cellRec != nullptr; }
-int stream_vertex_lookup_mode(int64_t n, const MeshView& m, const StreamState& ss) {
-    int64_t cells = m.nCells;
-    if (ss.densityLookup && ss.occupiedHost != nullptr) {
-        const int64_t occ = (int64_t)ss.occupiedHost[0], live = (int64_t)ss.occupiedHost[1];
-        if (occ > 0 && occ <= cells && live > 0 && live <= 2 * n && n <= 2 * live) cells = occ;
+StepPlan plan_step(const MeshView& m, const StreamState& ss, int variant, const VertexField* vf, int64_t n, int nCyc, double D,
+                   unsigned flags, bool stats) {
+    StepPlan p;
+    p.brown = D > 0.0;
+    p.reflect = (flags & CPF_STEP_NO_REFLECT) == 0;
+    p.storeVel = (flags & CPF_STEP_STORE_VEL) != 0;
+    p.stats = stats;
+    // the variant that runs for the requested one (non-hex meshes: generic; record-offset limits)
+    const int coopMaxCells = (ss.coopMaxCells <= 0 || ss.coopMaxCells > kCoopMaxCells) ? kCoopMaxCells : ss.coopMaxCells;
+    if (!m.allHex) {
+        // not all-hex: the streaming kernel where the mesh layer built mixed records for it (few cells with more than six
+        // faces: they take the CSR walk inside the kernel), else the generic CSR walk; the other variants need 6 faces per cell
+        const bool wantsStream = variant == kVariantAuto || variant == kVariantStream || variant == kVariantCoop;
+        variant = (m.mixed && m.cellRec && wantsStream) ? kVariantStream : kVariantGeneric;
+    } else {
+        // Several cycles fused into one launch (CPF_STEP_FUSE_CYCLES: what advect.H does between two output points): the
+        // particle stream is loaded and stored once per launch, so hiding it behind the walk buys nothing, and the
+        // wave-cooperative kernel's 8 waves per SIMD (the streaming kernel: 7) win -- by less since round 3, measured per
+        // cycle on pitzDaily: 3 cycles per launch the streaming kernel is 4 % FASTER (0.0982 vs 0.1026 ms; with the Brownian
+        // kick 0.181 vs 0.190), 8 cycles 2 % slower (0.0930 vs 0.0911; kick: equal).  Round 2: 5 % slower at 3, 10 % at 8.
+        // (Final build of round 3, exact face normals: 8 cycles 0.0865 vs 0.0846 ms per cycle, with the kick 0.167 vs 0.172.)
+        // Round 4: the streaming kernel's flat walk and box records turned that around -- 8 cycles per launch, pitzDaily 0.0799 vs
+        // 0.0863 ms per cycle (16 cycles: 0.0783 vs 0.0822), with the kick 0.159 vs 0.169, TJunction 0.0855 vs 0.1216 -- and
+        // kFusedCoopCycles went up to "never" (the switch stays for builds without the streaming kernel).
+        if (variant == kVariantAuto)
+            variant = !(nCyc >= kFusedCoopCycles && m.nCells <= coopMaxCells) ? kVariantStream : kVariantCoop;
+        // the wave-cooperative kernel addresses records with a 32-bit byte offset (256 B x 2^24 cells)
+        if (variant == kVariantCoop && m.nCells > coopMaxCells) variant = kVariantStream;
+#ifndef CPF_EXPERIMENTS
+        // (variants 1, 2 and 5 are not in this build: cpf_set_option refuses them; belt and braces)
+        if (variant == kVariantFixed || variant == kVariantFixedScalar) variant = kVariantCoop;
+        if (variant == kVariantAhead) variant = kVariantStream;
+#endif
     }
-    return n < 128 * cells ? 1 : 0;
+    if (vf != nullptr) {
+        // the "VertexVelocity" cycle streams where the cell-constant one would (variant 4: -1 on a mesh with cell records), the
+        // decomposition is admitted to the cone locate (its advect never fails there) and the mesh is all-hex (twelve tets a
+        // cell -- the reference's only decomposition, src/initCuda.H:64 -- is what the kernel's staged locate is built for);
+        // mixed meshes keep step_kernel_vertex
+        p.cone = vf->cone != nullptr;
+        const bool streams = p.cone && vf->tetsPerCell == 12 && m.mixed == 0 && m.cellRec != nullptr && variant == kVariantStream;
+        p.kernel = streams ? StepPlan::kStreamVertex : StepPlan::kVertex;
+        if (streams) p.lookup = stream_lookup_mode(n, m, ss, p.brown, true);
+        return p;
+    }
+    // lanes that run ahead into the next tile: one plain cycle per launch only; everything else streams
+    if (variant == kVariantAhead && (p.brown || p.storeVel || nCyc != 1)) variant = kVariantStream;
+    p.kernel = (StepPlan::Kernel)variant;
+    if (variant == kVariantStream) p.lookup = stream_lookup_mode(n, m, ss, p.brown, false);
+    return p;
 }
 
-hipError_t launch_step_stream_vertex(hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid,
-                                     double* vel, int64_t n, double dt, double sigma, uint32_t step0, int nCyc, uint32_t seed,
-                                     bool brown, bool reflect, bool storeVel, const MeshView& m, unsigned long long* counters,
-                                     StreamState& ss, const VertexField& vf) {
-    const int lf = stream_vertex_lookup_mode(n, m, ss);
-#define CPF_STREAM_VGO(B, R, SV, ST)                                                                                         \
-    do {                                                                                                                     \
-        if (lf == 1) return launch_stream_inst<B, R, SV, ST, 1, true>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, ss, &vf);  \
-        return launch_stream_inst<B, R, SV, ST, 0, true>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, ss, &vf);               \
-    } while (0)
-#define CPF_STREAM_VSV(B, R)                                                                     \
-    do {                                                                                        \
-        if (storeVel) { if (counters) CPF_STREAM_VGO(B, R, true, true); else CPF_STREAM_VGO(B, R, true, false); } \
-        else { if (counters) CPF_STREAM_VGO(B, R, false, true); else CPF_STREAM_VGO(B, R, false, false); }        \
-    } while (0)
-    if (brown) { if (reflect) CPF_STREAM_VSV(true, true); else CPF_STREAM_VSV(true, false); }
-    else { if (reflect) CPF_STREAM_VSV(false, true); else CPF_STREAM_VSV(false, false); }
-#undef CPF_STREAM_VSV
-#undef CPF_STREAM_VGO
+// the streaming kernels' instantiations: step_kernel_stream with every LOOKUP (the flat walk, 8 and 9, without the kick only),
+// step_kernel_stream_vertex with 0 and 1
+template <int... L, class F>
+static hipError_t with_lookup(int lookup, F&& f) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((lookup == L && ((e = f(std::integral_constant<int, L>{})), true)) || ...);
+    return e;
 }
-
-hipError_t launch_step_stream(hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid,
+hipError_t launch_step_stream(const StepPlan& p, hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid,
                               double* vel, int64_t n, double dt, double sigma, uint32_t step0, int nCyc, uint32_t seed,
-                              bool brown, bool reflect, bool storeVel, const MeshView& m, unsigned long long* counters,
-                              StreamState& ss) {
-    const int lf = stream_lookup_mode(n, m, ss, brown);
-#define CPF_STREAM_GO(B, R, SV, ST)                                                                                          \
-    do {                                                                                                                     \
-        if (lf == 8) { if (!B) return launch_stream_inst<false, R, SV, ST, 8>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, ss); return hipErrorInvalidValue; } \
-        if (lf == 11) return launch_stream_inst<B, R, SV, ST, 11>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, ss);  \
-        if (lf == 9) { if (!B) return launch_stream_inst<false, R, SV, ST, 9>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, ss); return hipErrorInvalidValue; } \
-        if (lf == 6) return launch_stream_inst<B, R, SV, ST, 6>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, ss);  \
-        if (lf == 5) return launch_stream_inst<B, R, SV, ST, 5>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, ss);  \
-        if (lf == 4) return launch_stream_inst<B, R, SV, ST, 4>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, ss);  \
-        if (lf == 3) return launch_stream_inst<B, R, SV, ST, 3>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, ss);  \
-        if (lf == 2) return launch_stream_inst<B, R, SV, ST, 2>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, ss);  \
-        if (lf == 1) return launch_stream_inst<B, R, SV, ST, 1>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, ss);  \
-        return launch_stream_inst<B, R, SV, ST, 0>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, ss);         \
-    } while (0)
-#define CPF_STREAM_SV(B, R)                                                                     \
-    do {                                                                                        \
-        if (storeVel) { if (counters) CPF_STREAM_GO(B, R, true, true); else CPF_STREAM_GO(B, R, true, false); } \
-        else { if (counters) CPF_STREAM_GO(B, R, false, true); else CPF_STREAM_GO(B, R, false, false); }        \
-    } while (0)
-    if (brown) { if (reflect) CPF_STREAM_SV(true, true); else CPF_STREAM_SV(true, false); }
-    else { if (reflect) CPF_STREAM_SV(false, true); else CPF_STREAM_SV(false, false); }
-#undef CPF_STREAM_SV
-#undef CPF_STREAM_GO
+                              const MeshView& m, unsigned long long* counters, const VertexField* vf, StreamState& ss, bool zSettled,
+                              hipEvent_t evStart, hipEvent_t evStop) {
+    return with_bools([&](auto B, auto R, auto SV, auto ST) {
+        if (p.kernel == StepPlan::kStreamVertex)
+            return with_lookup<0, 1>(p.lookup, [&](auto LF) {
+                return launch_stream_inst<B, R, SV, ST, LF, true>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m,
+                                                                  counters, ss, vf, zSettled, evStart, evStop);
+            });
+        return with_lookup<0, 1, 2, 3, 4, 5, 6, 8, 9, 11>(p.lookup, [&](auto LF) {
+            if constexpr (B && (LF == 8 || LF == 9)) return hipErrorInvalidValue;
+            else return launch_stream_inst<B, R, SV, ST, LF>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters,
+                                                             ss, vf, zSettled, evStart, evStop);
+        });
+    }, p.brown, p.reflect, p.storeVel, p.stats);
 }
 
 }  // namespace cpf
