@@ -55,6 +55,15 @@ class Comm(C.Structure):
                 ("last_error", COMM_ERROR_FN)]
 
 
+class MeshQuality(C.Structure):
+    """cpf_mesh_quality (include/cpf.h)"""
+    _fields_ = [("maxNonPlanarity", _dbl), ("worstFace", _i64), ("maxNonConvexity", _dbl), ("worstCell", _i64), ("nCells", _i64),
+                ("nFlaggedCells", _i64), ("nBadCells", _i64), ("nDerivedCells", _i64), ("tol", _dbl)]
+
+
+NONPLANAR_TOL = 1e-11                   # default of option "nonplanar_tol" (include/cpf.h)
+
+
 class ShardStats(C.Structure):
     """cpf_shard_stats (include/cpf.h)"""
     _fields_ = [("n", _i64), ("capacity", _i64), ("stepIndex", _i64), ("particleSteps", _i64), ("handedOff", _i64),
@@ -127,6 +136,10 @@ SIGNATURES = {
     "cpf_mesh_flags_host": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cpf_mesh_box_records_host": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, C.POINTER(C.c_int32), _vp]),
+    "cpf_get_mesh_quality": (_int, [_ctx, C.POINTER(MeshQuality)]),
+    "cpf_mesh_quality_host": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _dbl, _int, C.POINTER(MeshQuality)]),
+    "cpf_build_derived_mesh_host": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cpf_cells_to_parent_dev": (_int, [_ctx, _vp, _vp, _i64]),
     "cpf_set_velocity": (_int, [_ctx, _vp, _i64]),
     "cpf_set_velocity_dev": (_int, [_ctx, _vp, _i64]),
     "cpf_alloc_particles": (_int, [_ctx, _i64]),

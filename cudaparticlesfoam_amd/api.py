@@ -213,6 +213,17 @@ class Context:
         self._ck(self.lib.cpf_pack_leavers_dev(self.h, x, y, z, cell, gid, n, cell_lo, n_ranks, my_rank, sendbuf,
                                                send_cap, counts, n_stay))
 
+    def mesh_quality(self) -> Dict[str, float]:
+        """Quality of the mesh as given (cpf_get_mesh_quality): max_eta / worst_face (face non-planarity), max_xi / worst_cell
+        (cell non-convexity), n_cells, n_flagged, n_bad (flagged but left whole), n_derived (cells the walk runs on), tol."""
+        q = L.MeshQuality()
+        self._ck(self.lib.cpf_get_mesh_quality(self.h, C.byref(q)))
+        return _quality_dict(q)
+
+    def cells_to_parent_dev(self, cell_in, cell_out, n):
+        """Derived cell ids (device int32) -> parent ids (cpf_cells_to_parent_dev); in and out may alias."""
+        self._ck(self.lib.cpf_cells_to_parent_dev(self.h, cell_in, cell_out, n))
+
     def cell_histogram_dev(self, cell, n, scale, weights):
         self._ck(self.lib.cpf_cell_histogram_dev(self.h, cell, n, scale, weights))
 
@@ -310,6 +321,52 @@ def mesh_box_records_host(mesh):
     if st != L.CPF_OK:
         raise L.CpfError(st, "cpf_mesh_box_records_host")
     return rec if is_box.value else None
+
+
+def _quality_dict(q):
+    return dict(max_eta=q.maxNonPlanarity, worst_face=q.worstFace, max_xi=q.maxNonConvexity, worst_cell=q.worstCell,
+                n_cells=q.nCells, n_flagged=q.nFlaggedCells, n_bad=q.nBadCells, n_derived=q.nDerivedCells, tol=q.tol)
+
+
+def _mesh_args(mesh):
+    return [np.ascontiguousarray(mesh.points, dtype=np.float64), np.ascontiguousarray(mesh.face_offsets, dtype=np.int32),
+            np.ascontiguousarray(mesh.face_verts, dtype=np.int32), np.ascontiguousarray(mesh.owner, dtype=np.int32),
+            np.ascontiguousarray(mesh.neighbour, dtype=np.int32)]
+
+
+def mesh_quality_host(mesh, tol: float = L.NONPLANAR_TOL, split: bool = True):
+    """What ``Context.mesh_quality()`` would report after ``set_mesh(mesh)`` with option "nonplanar_tol" = tol (and
+    "split_nonplanar" = split), on the host alone (cpf_mesh_quality_host)."""
+    lib = L.load()
+    a = _mesh_args(mesh)
+    q = L.MeshQuality()
+    st = lib.cpf_mesh_quality_host(_ptr(a[0]), mesh.n_points, _ptr(a[1]), _ptr(a[2]), mesh.n_faces, _ptr(a[3]), _ptr(a[4]),
+                                   mesh.n_internal, mesh.n_cells, float(tol), 1 if split else 0, C.byref(q))
+    if st != L.CPF_OK:
+        raise L.CpfError(st, "cpf_mesh_quality_host")
+    return _quality_dict(q)
+
+
+def build_derived_mesh_host(mesh, tol: float = L.NONPLANAR_TOL):
+    """The mesh ``Context.set_mesh(mesh)`` walks (cpf_build_derived_mesh_host): (PolyMesh of the derived mesh, first
+    [n_cells + 1] -- the derived cells of parent c are first[c] .. first[c+1] --, apex points [n_decomposed][3])."""
+    from .cases.polymesh import PolyMesh
+    lib = L.load()
+    a = _mesh_args(mesh)
+    sizes = np.zeros(5, np.int64)
+
+    def call(*out):
+        st = lib.cpf_build_derived_mesh_host(_ptr(a[0]), mesh.n_points, _ptr(a[1]), _ptr(a[2]), mesh.n_faces, _ptr(a[3]), _ptr(a[4]),
+                                             mesh.n_internal, mesh.n_cells, float(tol), _ptr(sizes), *out)
+        if st != L.CPF_OK:
+            raise L.CpfError(st, "cpf_build_derived_mesh_host")
+    call(None, None, None, None, None, None)
+    n_p, n_f, n_v, n_i, n_c = (int(v) for v in sizes)
+    pts = np.empty((n_p, 3)); fo = np.empty(n_f + 1, np.int32); fv = np.empty(n_v, np.int32)
+    ow = np.empty(n_f, np.int32); ne = np.empty(max(n_i, 1), np.int32); first = np.empty(mesh.n_cells + 1, np.int32)
+    call(_ptr(pts), _ptr(fo), _ptr(fv), _ptr(ow), _ptr(ne), _ptr(first))
+    derived = PolyMesh(pts, fo, fv, ow, ne[:n_i].copy(), n_c)
+    return derived, first, pts[mesh.n_points:].copy()
 
 
 def pack_mesh_parts(parts):

@@ -74,6 +74,14 @@ struct cpf_context {
     int stepVariant = -1;                       // cpf_set_option("step_variant"), see include/cpf.h: -1 = choose per launch
     bool vtuBinary = false;                     // cpf_set_option("vtu_binary"): frames with raw appended arrays instead of the reference's ASCII
     bool mixedRecords = true;                   // cpf_set_option("mixed_records"): build cell records for hex-dominant meshes too (before cpf_set_mesh)
+    // warped / concave cells (cpf_mesh.cpp: measure_mesh, derive_mesh; DESIGN.md "Warped cells")
+    double nonplanarTol = cpf::kNonPlanarTolDefault;    // "nonplanar_tol" (before cpf_set_mesh)
+    bool splitNonplanar = true;                         // "split_nonplanar" (before cpf_set_mesh): 0 = one plane per face everywhere
+    cpf_mesh_quality quality{};                         // of the mesh as the caller gave it
+    int64_t nParent = 0;                                // cells of the mesh as given: == host.nCells unless cells were decomposed
+    std::vector<int32_t> first;                         // [nParent+1] derived cells of parent c: first[c] .. first[c+1] (decomposed meshes only)
+    int32_t* d_parentOf = nullptr;                      // [host.nCells] parent of every derived cell; null: no cell decomposed
+    double* d_Uparent = nullptr;                        // [nParent][3] staging of cpf_set_velocity on a decomposed mesh
     cpf::StreamState streamState;               // chunk counter + tuning of the streaming step kernel
     int64_t lastStepN = -1;                     // particle count of the most recent step launch (cpf_step_kernel_name)
     int lastStepCycles = 1;                     // ... and its cycles per launch
@@ -185,6 +193,8 @@ void freeMesh(cpf_context* c) {
     freeDev(c->d_binOff); freeDev(c->d_binCells);
     c->haveMesh = c->haveU = false; c->meshBytes = 0;
     c->nSecondRecords = 0;
+    freeDev(c->d_parentOf); freeDev(c->d_Uparent);
+    c->first.clear(); c->nParent = 0; c->quality = cpf_mesh_quality{};
     // the tet decomposition of the "VertexVelocity" mode belongs to the mesh it was made for (cpf_set_tets checks it against
     // that mesh's cell count): a new mesh starts without one
     freeDev(c->d_tetPos); freeDev(c->d_tets); freeDev(c->d_vertVel);
@@ -196,6 +206,15 @@ void freeCloud(cpf_context* c) {
     c->cap = c->n = 0; c->located = false; c->zSettled = false;
 }
 
+cpf_mesh_quality toQuality(const cpf::MeshQuality& q, int64_t nDerived) {
+    cpf_mesh_quality r{};
+    r.maxNonPlanarity = q.maxEta; r.worstFace = q.worstFace;
+    r.maxNonConvexity = q.maxXi; r.worstCell = q.worstCell;
+    r.nCells = q.nCells; r.nFlaggedCells = q.nFlagged; r.nBadCells = q.nBad; r.nDerivedCells = nDerived;
+    r.tol = q.tol;
+    return r;
+}
+
 template <typename Label>
 int setMeshImpl(cpf_context* ctx, const double* points, int64_t nPoints, const Label* faceOffsets,
                 const Label* faceVerts, int64_t nFaces, const Label* owner, const Label* neighbour,
@@ -203,15 +222,40 @@ int setMeshImpl(cpf_context* ctx, const double* points, int64_t nPoints, const L
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, points && faceOffsets && faceVerts && owner && (neighbour || nInternal == 0), CPF_ERR_ARG,
                 "cpf_set_mesh: null array");
+    // warped faces and concave cells: measured on every mesh; where some cell needs it (and "split_nonplanar" is on) the walk
+    // runs on the derived mesh, those cells replaced by their fans of tets -- otherwise on the mesh as given, exactly as before
+    cpf::MeshQuality q;
+    std::string why = cpf::measure_mesh<Label>(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal,
+                                               nCells, ctx->nonplanarTol, q);
+    if (!why.empty()) return fail(ctx, CPF_ERR_MESH, "cpf_set_mesh: " + why);
+    bool derive = ctx->splitNonplanar && q.decompose();
+    cpf::DerivedMesh dm;
     cpf::HostTables t;
-    std::string why = cpf::build_tables<Label>(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour,
-                                               nInternal, nCells, t);
+    if (derive) {
+        why = cpf::derive_mesh<Label>(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal, nCells, q, dm);
+        if (why.empty())
+            why = cpf::build_tables<int64_t>(dm.points.data(), dm.nPoints, dm.faceOff.data(), dm.faceVerts.data(), dm.nFaces,
+                                             dm.owner.data(), dm.neighbour.data(), dm.nInternal, dm.nCells, t);
+        // a whole cell must see each face it shares with a decomposed cell as ONE slot (its triangles merged into a face
+        // group): else a segment could leave it through the wrong triangle.  Where that fails, keep the one-plane model.
+        for (int64_t c = 0; c < nCells && why.empty() && derive; ++c)
+            if (dm.first[(size_t)c + 1] - dm.first[(size_t)c] == 1) {
+                const int32_t d = dm.first[(size_t)c];
+                if (t.cellOff[(size_t)d + 1] - t.cellOff[(size_t)d] > q.cellOff[(size_t)c + 1] - q.cellOff[(size_t)c]) derive = false;
+            }
+    }
+    if (!derive) {
+        why = cpf::build_tables<Label>(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal, nCells, t);
+    }
     if (!why.empty()) return fail(ctx, CPF_ERR_MESH, "cpf_set_mesh: " + why);
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     freeMesh(ctx);
     ctx->streamState.flatField = false;
     ctx->host = std::move(t);
+    ctx->nParent = nCells;
+    ctx->quality = toQuality(q, ctx->host.nCells);
+    nCells = ctx->host.nCells;                         // from here on: the cells the walk runs on
     const cpf::HostTables& h = ctx->host;
     auto up = [&](auto*& dptr, const void* src, size_t bytes) -> hipError_t {
         hipError_t e = hipMalloc((void**)&dptr, std::max<size_t>(bytes, 16));
@@ -228,6 +272,12 @@ int setMeshImpl(cpf_context* ctx, const double* points, int64_t nPoints, const L
     CPF_HIP(ctx, up(ctx->d_binCells, h.binCells.data(), h.binCells.size() * 4));
     CPF_HIP(ctx, up(ctx->d_cellBox, h.cellBox.data(), h.cellBox.size() * 4));
     CPF_HIP(ctx, up(ctx->d_curveRank, h.curveRank.data(), h.curveRank.size() * 4));
+    if (derive) {
+        ctx->first = std::move(dm.first);
+        CPF_HIP(ctx, up(ctx->d_parentOf, dm.parent.data(), dm.parent.size() * 4));
+        CPF_HIP(ctx, hipMalloc((void**)&ctx->d_Uparent, (size_t)ctx->nParent * 3 * sizeof(double)));
+        ctx->meshBytes += (size_t)ctx->nParent * 24;
+    }
     CPF_HIP(ctx, hipMalloc((void**)&ctx->d_U, (size_t)nCells * sizeof(double4)));
     CPF_HIP(ctx, hipMalloc((void**)&ctx->d_U3, (size_t)nCells * 3 * sizeof(double)));
     CPF_HIP(ctx, hipMemset(ctx->d_U, 0, (size_t)nCells * sizeof(double4)));
@@ -282,6 +332,7 @@ WriterRegistry::~WriterRegistry() {
 
 namespace cpf {
 bool vtu_binary(const cpf_context* ctx) { return ctx && ctx->vtuBinary; }
+bool context_derived(const cpf_context* ctx) { return ctx && ctx->d_parentOf != nullptr; }
 void* context_stream(const cpf_context* ctx) { return (void*)ctx->stream; }
 int context_device(const cpf_context* ctx) { return ctx->device; }
 bool context_timing(const cpf_context* ctx) { return ctx->timing; }
@@ -360,6 +411,32 @@ hipError_t layOutField(cpf_context* ctx, const double* dU3, int64_t nCells) {
         ctx->fieldFlagPending = e == hipSuccess;
     }
     return e;
+}
+// Sub-cell resolve of cpf_set_particles on a decomposed mesh: parent cell c -> the lowest derived cell of first[c] .. first[c+1]
+// whose every plane has the point within kTol on its inner side (the walk's face test, cpf_walk.h plane_dist), or else the one
+// whose worst plane distance is smallest.  Negative codes pass through.
+std::string resolveSubCells(const cpf_context* ctx, int64_t n, const double* xyz, const int32_t* cell, std::vector<int32_t>& out) {
+    const cpf::HostTables& h = ctx->host;
+    out.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t c = cell[i];
+        if (c < 0) { out[(size_t)i] = c; continue; }
+        if (c >= ctx->nParent) return "cell[" + std::to_string(i) + "] = " + std::to_string(c) + " is not a cell of the mesh";
+        const double px = xyz[3 * i], py = xyz[3 * i + 1], pz = xyz[3 * i + 2];
+        int32_t pick = ctx->first[(size_t)c];
+        double pickWorst = HUGE_VAL;
+        for (int32_t d = ctx->first[(size_t)c]; d < ctx->first[(size_t)c + 1]; ++d) {
+            double worst = -HUGE_VAL;
+            for (int32_t s = h.cellOff[(size_t)d]; s < h.cellOff[(size_t)d + 1]; ++s) {
+                const double* pl = &h.planes[4 * (size_t)s];
+                worst = std::max(worst, std::fma(-pl[2], pz, std::fma(-pl[1], py, std::fma(-pl[0], px, pl[3]))));
+            }
+            if (worst < cpf::kTol) { pick = d; break; }
+            if (worst < pickWorst) { pickWorst = worst; pick = d; }
+        }
+        out[(size_t)i] = pick;
+    }
+    return std::string();
 }
 // the read-back is known to be complete (after a synchronise, or its event has been seen): take the note
 void fieldFlagArrived(cpf_context* ctx) {
@@ -546,6 +623,69 @@ int cpf_mesh_box_records_host(const double* points, int64_t nPoints, const int32
     return CPF_OK;
 }
 
+int cpf_mesh_quality_host(const double* points, int64_t nPoints, const int32_t* faceOffsets, const int32_t* faceVerts,
+                          int64_t nFaces, const int32_t* owner, const int32_t* neighbour, int64_t nInternal, int64_t nCells,
+                          double tol, int split, cpf_mesh_quality* out) {
+    if (!points || !faceOffsets || !faceVerts || !owner || (!neighbour && nInternal != 0) || !out || !(tol > 0.0)) return CPF_ERR_ARG;
+    try {
+        cpf::MeshQuality q;
+        if (!cpf::measure_mesh<int32_t>(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal, nCells, tol, q).empty())
+            return CPF_ERR_MESH;
+        int64_t nDerived = nCells;
+        if (split && q.decompose()) {
+            cpf::DerivedMesh dm;
+            if (!cpf::derive_mesh<int32_t>(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal, nCells, q, dm).empty())
+                return CPF_ERR_MESH;
+            nDerived = dm.nCells;
+        }
+        *out = toQuality(q, nDerived);
+    } catch (const std::bad_alloc&) {
+        return CPF_ERR_NOMEM;
+    }
+    return CPF_OK;
+}
+
+int cpf_build_derived_mesh_host(const double* points, int64_t nPoints, const int32_t* faceOffsets, const int32_t* faceVerts,
+                                int64_t nFaces, const int32_t* owner, const int32_t* neighbour, int64_t nInternal, int64_t nCells,
+                                double tol, int64_t sizes[5], double* pointsOut, int32_t* faceOffOut, int32_t* faceVertsOut,
+                                int32_t* ownerOut, int32_t* neighbourOut, int32_t* first) {
+    if (!points || !faceOffsets || !faceVerts || !owner || (!neighbour && nInternal != 0) || !sizes || !(tol > 0.0)) return CPF_ERR_ARG;
+    try {
+        cpf::MeshQuality q;
+        if (!cpf::measure_mesh<int32_t>(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal, nCells, tol, q).empty())
+            return CPF_ERR_MESH;
+        cpf::DerivedMesh dm;     // (no cell to decompose: the derived mesh is the mesh as given)
+        if (!cpf::derive_mesh<int32_t>(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal, nCells, q, dm).empty())
+            return CPF_ERR_MESH;
+        if (dm.faceVerts.size() > (size_t)INT32_MAX) return CPF_ERR_MESH;
+        sizes[0] = dm.nPoints; sizes[1] = dm.nFaces; sizes[2] = (int64_t)dm.faceVerts.size(); sizes[3] = dm.nInternal; sizes[4] = dm.nCells;
+        auto narrow = [](const std::vector<int64_t>& v, int32_t* o) { if (o) for (size_t i = 0; i < v.size(); ++i) o[i] = (int32_t)v[i]; };
+        if (pointsOut) std::memcpy(pointsOut, dm.points.data(), dm.points.size() * 8);
+        narrow(dm.faceOff, faceOffOut); narrow(dm.faceVerts, faceVertsOut); narrow(dm.owner, ownerOut); narrow(dm.neighbour, neighbourOut);
+        if (first) std::memcpy(first, dm.first.data(), dm.first.size() * 4);
+    } catch (const std::bad_alloc&) {
+        return CPF_ERR_NOMEM;
+    }
+    return CPF_OK;
+}
+
+int cpf_get_mesh_quality(const cpf_context* ctx, cpf_mesh_quality* out) {
+    CPF_REQUIRE(ctx, ctx && out, CPF_ERR_ARG, "null argument");
+    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_get_mesh_quality: call cpf_set_mesh first");
+    *out = ctx->quality;
+    return CPF_OK;
+}
+
+int cpf_cells_to_parent_dev(cpf_context* ctx, const int32_t* in, int32_t* out, int64_t n) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_cells_to_parent_dev: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, n >= 0 && (n == 0 || (in && out)), CPF_ERR_ARG, "cpf_cells_to_parent_dev: bad arguments");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->d_parentOf) CPF_HIP(ctx, cpf::launch_cells_to_parent(ctx->stream, in, out, ctx->d_parentOf, n, ctx->host.nCells));
+    else if (n > 0 && in != out) CPF_HIP(ctx, hipMemcpyAsync(out, in, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    return CPF_OK;
+}
+
 int cpf_mesh_info(const cpf_context* ctx, int64_t* nCells, int64_t* nSlots, int64_t* deviceBytes) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_mesh_info: no mesh set");
@@ -591,10 +731,15 @@ int cpf_get_mesh_flags(const cpf_context* ctx, int32_t* allHex, int32_t* zLayere
 int cpf_set_velocity(cpf_context* ctx, const double* U, int64_t nCells) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_set_velocity: call cpf_set_mesh first");
-    CPF_REQUIRE(ctx, U && nCells == ctx->host.nCells, CPF_ERR_ARG, "cpf_set_velocity: U is null or nCells differs from the mesh");
+    CPF_REQUIRE(ctx, U && nCells == ctx->nParent, CPF_ERR_ARG, "cpf_set_velocity: U is null or nCells differs from the mesh");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(ctx->d_U3, U, (size_t)nCells * 24, hipMemcpyHostToDevice, ctx->stream));
-    CPF_HIP(ctx, layOutField(ctx, ctx->d_U3, nCells));
+    if (ctx->d_parentOf) {                             // per parent cell -> every derived cell of it
+        CPF_HIP(ctx, hipMemcpyAsync(ctx->d_Uparent, U, (size_t)nCells * 24, hipMemcpyHostToDevice, ctx->stream));
+        CPF_HIP(ctx, cpf::launch_gather_parent_u3(ctx->stream, ctx->d_Uparent, ctx->d_parentOf, ctx->d_U3, ctx->host.nCells));
+    } else {
+        CPF_HIP(ctx, hipMemcpyAsync(ctx->d_U3, U, (size_t)nCells * 24, hipMemcpyHostToDevice, ctx->stream));
+    }
+    CPF_HIP(ctx, layOutField(ctx, ctx->d_U3, ctx->host.nCells));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));   // U may be pageable host memory owned by the caller
     fieldFlagArrived(ctx);
     ctx->haveU = true;
@@ -604,9 +749,13 @@ int cpf_set_velocity(cpf_context* ctx, const double* U, int64_t nCells) {
 int cpf_set_velocity_dev(cpf_context* ctx, const double* dU, int64_t nCells) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_set_velocity_dev: call cpf_set_mesh first");
-    CPF_REQUIRE(ctx, dU && nCells == ctx->host.nCells, CPF_ERR_ARG, "cpf_set_velocity_dev: bad arguments");
+    CPF_REQUIRE(ctx, dU && nCells == ctx->nParent, CPF_ERR_ARG, "cpf_set_velocity_dev: bad arguments");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, layOutField(ctx, dU, nCells));        // (asynchronous: the flat walk waits until the flag has been seen to arrive)
+    if (ctx->d_parentOf) {                             // per parent cell -> every derived cell of it
+        CPF_HIP(ctx, cpf::launch_gather_parent_u3(ctx->stream, dU, ctx->d_parentOf, ctx->d_U3, ctx->host.nCells));
+        dU = ctx->d_U3;
+    }
+    CPF_HIP(ctx, layOutField(ctx, dU, ctx->host.nCells));   // (asynchronous: the flat walk waits until the flag has been seen to arrive)
     ctx->haveU = true;
     return CPF_OK;
 }
@@ -653,6 +802,12 @@ int cpf_set_particles(cpf_context* ctx, int64_t n, const double* xyz, const int3
     CPF_HIP(ctx, hipMemcpyAsync(ctx->scratch, xyz, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
     CPF_HIP(ctx, cpf::launch_unpack_xyz(ctx->stream, (const double*)ctx->scratch, ctx->x, ctx->y, ctx->z, n));
     CPF_HIP(ctx, cpf::launch_iota64(ctx->stream, ctx->gid, n, 0));
+    std::vector<int32_t> sub;
+    if (cell && ctx->d_parentOf) {                     // parent cells -> the derived cell of each that holds the point
+        std::string why = resolveSubCells(ctx, n, xyz, cell, sub);
+        if (!why.empty()) { (void)hipStreamSynchronize(ctx->stream); return fail(ctx, CPF_ERR_ARG, "cpf_set_particles: " + why); }
+        cell = sub.data();
+    }
     if (cell) CPF_HIP(ctx, hipMemcpyAsync(ctx->cell, cell, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     else CPF_HIP(ctx, hipMemsetAsync(ctx->cell, 0xFF, (size_t)n * 4, ctx->stream));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -903,6 +1058,7 @@ int cpf_get_particles(cpf_context* ctx, double* xyzw, int32_t* cell, double* vel
     double* dV = (double*)p;
     CPF_HIP(ctx, cpf::launch_pack_by_gid(ctx->stream, ctx->x, ctx->y, ctx->z, ctx->cell, ctx->gid, ctx->vel,
                                          xyzw ? dX : nullptr, cell ? dC : nullptr, vel ? dV : nullptr, ctx->n));
+    if (cell && ctx->d_parentOf) CPF_HIP(ctx, cpf::launch_cells_to_parent(ctx->stream, dC, dC, ctx->d_parentOf, ctx->n, ctx->host.nCells));
     if (xyzw) CPF_HIP(ctx, hipMemcpyAsync(xyzw, dX, n * 32, hipMemcpyDeviceToHost, ctx->stream));
     if (cell) CPF_HIP(ctx, hipMemcpyAsync(cell, dC, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (vel) CPF_HIP(ctx, hipMemcpyAsync(vel, dV, n * 32, hipMemcpyDeviceToHost, ctx->stream));
@@ -1046,6 +1202,16 @@ int cpf_set_option(cpf_context* ctx, const char* key, double value) {
         ctx->stats = value != 0;
         return CPF_OK;
     }
+    if (k == "nonplanar_tol") {
+        CPF_REQUIRE(ctx, value > 0.0 && std::isfinite(value), CPF_ERR_ARG, "nonplanar_tol must be a positive number");
+        ctx->nonplanarTol = value;
+        return CPF_OK;
+    }
+    if (k == "split_nonplanar") {
+        CPF_REQUIRE(ctx, value == 0 || value == 1, CPF_ERR_ARG, "split_nonplanar must be 0 or 1");
+        ctx->splitNonplanar = value != 0;
+        return CPF_OK;
+    }
     return fail(ctx, CPF_ERR_ARG, "cpf_set_option: unknown key '" + k + "'");
 }
 
@@ -1103,6 +1269,8 @@ int cpf_pack_leavers_dev(cpf_context* ctx, double* x, double* y, double* z, int3
                 CPF_ERR_ARG, "cpf_pack_leavers_dev: bad sizes (1 .. CPF_MAX_RANKS ranks)");
     CPF_REQUIRE(ctx, cellLo_dev && counts_dev && nStay_dev && (sendbuf || sendCapacity == 0) && (n == 0 || (x && y && z && cell)),
                 CPF_ERR_ARG, "cpf_pack_leavers_dev: null array");
+    CPF_REQUIRE(ctx, !ctx->d_parentOf, CPF_ERR_MESH, "cpf_pack_leavers_dev: the mesh has cells decomposed into tets "
+                "(cpf_get_mesh_quality): ownership ranges are parent ids, the cloud's cells derived ids");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     int r = ensureScratch(ctx, cpf::handoff_scratch_bytes(n, nRanks));
     if (r) return r;
@@ -1116,6 +1284,16 @@ int cpf_cell_histogram_dev(cpf_context* ctx, const int32_t* cell, int64_t n, dou
     CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_cell_histogram_dev: call cpf_set_mesh first");
     CPF_REQUIRE(ctx, n >= 0 && weights_dev && (cell || n == 0), CPF_ERR_ARG, "cpf_cell_histogram_dev: bad arguments");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->d_parentOf) {                             // weights per PARENT cell: the ids are mapped first, into the scratch's head
+        const size_t head = ((size_t)n * 4 + 255) & ~(size_t)255;
+        int r = ensureScratch(ctx, head + cpf::histogram_scratch_bytes(ctx->nParent));
+        if (r != CPF_OK) return r;
+        int32_t* parent = (int32_t*)ctx->scratch;
+        CPF_HIP(ctx, cpf::launch_cells_to_parent(ctx->stream, cell, parent, ctx->d_parentOf, n, ctx->host.nCells));
+        CPF_HIP(ctx, cpf::cell_histogram(ctx->stream, parent, n, ctx->nParent, scale, weights_dev, (char*)ctx->scratch + head,
+                                         ctx->scratchBytes - head));
+        return CPF_OK;
+    }
     int r = ensureScratch(ctx, cpf::histogram_scratch_bytes(ctx->host.nCells));
     if (r != CPF_OK) return r;
     CPF_HIP(ctx, cpf::cell_histogram(ctx->stream, cell, n, ctx->host.nCells, scale, weights_dev, ctx->scratch,
@@ -1129,7 +1307,7 @@ int cpf_cell_ranges_dev(cpf_context* ctx, const double* weights_dev, int nRanks,
     CPF_REQUIRE(ctx, weights_dev && cellLo_dev && nRanks >= 1 && nRanks <= CPF_MAX_RANKS, CPF_ERR_ARG,
                 "cpf_cell_ranges_dev: bad arguments (1 <= nRanks <= CPF_MAX_RANKS)");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, cpf::cell_ranges(ctx->stream, weights_dev, ctx->host.nCells, nRanks, cellLo_dev));
+    CPF_HIP(ctx, cpf::cell_ranges(ctx->stream, weights_dev, ctx->nParent, nRanks, cellLo_dev));   // (weights: per parent cell)
     return CPF_OK;
 }
 
@@ -1195,6 +1373,8 @@ int cpf_copy_dev(cpf_context* ctx, void* dst, const void* src, size_t bytes) {
 #define CPF_STAGE_PRE(name, needU)                                                                      \
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");                                                 \
     CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, name ": call cpf_set_mesh first");                   \
+    CPF_REQUIRE(ctx, !ctx->d_parentOf, CPF_ERR_MESH, name ": the mesh has warped or concave cells decomposed " \
+                "into tets (cpf_get_mesh_quality); the reference-layout stages take the mesh's own cells only"); \
     CPF_REQUIRE(ctx, !(needU) || ctx->haveU, CPF_ERR_STATE, name ": call cpf_set_velocity first");      \
     CPF_REQUIRE(ctx, n >= 0, CPF_ERR_ARG, name ": negative particle count");                            \
     CPF_HIP(ctx, hipSetDevice(ctx->device))
@@ -1251,6 +1431,8 @@ int cpf_set_tets(cpf_context* ctx, const double* positions, int64_t nVerts, cons
                  int tetsPerCell) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_set_tets: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, !ctx->d_parentOf, CPF_ERR_MESH, "cpf_set_tets: the mesh has warped or concave cells decomposed into tets "
+                "(cpf_get_mesh_quality); the \"VertexVelocity\" mode needs the mesh's own cells (set option \"split_nonplanar\" 0)");
     CPF_REQUIRE(ctx, positions && tets && nVerts > 0 && tetsPerCell > 0, CPF_ERR_ARG, "cpf_set_tets: bad arguments");
     CPF_REQUIRE(ctx, nTets == (int64_t)tetsPerCell * ctx->host.nCells, CPF_ERR_MESH,
                 "cpf_set_tets: nTets must be tetsPerCell x nCells (tets in cell order, src/initCuda.H:99-105)");
@@ -1374,6 +1556,9 @@ int cpf_write_vtu_async(cpf_context* ctx, const char* path, double* totalKE) {
     char* d = (char*)ctx->snapDev;
     CPF_HIP(ctx, cpf::launch_pack_by_gid(ctx->stream, ctx->x, ctx->y, ctx->z, ctx->cell, ctx->gid, ctx->vel, (double*)d, (int32_t*)(d + offC),
                                          (double*)(d + offV), ctx->n));
+    if (ctx->d_parentOf)
+        CPF_HIP(ctx, cpf::launch_cells_to_parent(ctx->stream, (const int32_t*)(d + offC), (int32_t*)(d + offC), ctx->d_parentOf, ctx->n,
+                                                 ctx->host.nCells));
     CPF_HIP(ctx, hipEventRecord(ctx->evSnap, ctx->stream));
     CPF_HIP(ctx, hipStreamWaitEvent(ctx->ioStream, ctx->evSnap, 0));
     CPF_HIP(ctx, hipMemcpyAsync(ctx->snapHost, ctx->snapDev, need, hipMemcpyDeviceToHost, ctx->ioStream));

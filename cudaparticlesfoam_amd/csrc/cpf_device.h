@@ -137,6 +137,9 @@ hipError_t launch_build_cell_records_mixed(hipStream_t st, const int32_t* cellOf
                                            const double4* U, const int32_t* recB, double4* rec, int64_t nCells);
 hipError_t launch_update_record_velocity(hipStream_t st, const double4* U, double4* rec, double* box, int64_t nCells);
 hipError_t launch_u3_to_u4(hipStream_t st, const double* u3, double4* u4, int64_t nCells, unsigned long long* zFlag = nullptr);
+// meshes with decomposed cells (cpf_parent.hip): per-parent U -> per-derived U[3]; derived -> parent cell ids (negative codes kept)
+hipError_t launch_gather_parent_u3(hipStream_t st, const double* uParent, const int32_t* parentOf, double* uDerived, int64_t nDerived);
+hipError_t launch_cells_to_parent(hipStream_t st, const int32_t* in, int32_t* out, const int32_t* parentOf, int64_t n, int64_t nDerived);
 
 // stage-by-stage kernels on the reference's AoS layouts
 hipError_t launch_stage_advect(hipStream_t st, double* P, const int32_t* ids, double* vels, double* disps, double dt,

@@ -55,6 +55,48 @@ extern template std::string build_tables<int32_t>(const double*, int64_t, const 
 extern template std::string build_tables<int64_t>(const double*, int64_t, const int64_t*, const int64_t*, int64_t,
                                                   const int64_t*, const int64_t*, int64_t, int64_t, HostTables&);
 
+// Face non-planarity and cell non-convexity of a polyMesh, and which cells the walk cannot model with one plane per face
+// (cpf_mesh.cpp, DESIGN.md "Warped cells").  flagged[c]: 0 = fine, 1 = flagged but its fan has a tet of non-positive volume
+// (left as it is: a "bad" cell), 2 = flagged and decomposed into tets.
+struct MeshQuality {
+    double maxEta = 0.0, maxXi = 0.0, tol = 0.0;
+    int64_t worstFace = -1, worstCell = -1, nCells = 0, nFlagged = 0, nBad = 0;
+    std::vector<char> flagged;          // [nCells]
+    std::vector<double> centre;         // [nCells][3]  OpenFOAM's cell centres (the apexes)
+    std::vector<int64_t> cellOff, cellFaces;   // mesh.cells(): owned faces ascending, then neighbour faces ascending
+    int64_t nSplit() const { return nFlagged - nBad; }
+    // Decompose only when EVERY flagged cell has a positive fan: a flagged cell left whole next to decomposed ones would see
+    // their warped shared faces as separate, non-coplanar triangle slots and let segments leave through the wrong one (a
+    // warped chamfered box: more particles outside the domain than with no decomposition at all).  With a bad cell the whole
+    // mesh keeps the one-plane model, exactly as with "split_nonplanar" 0, and the report says so (nBadCells > 0).
+    bool decompose() const { return nSplit() > 0 && nBad == 0; }
+};
+// The derived polyMesh: every cell with flagged == 2 replaced by its fan of tets, numbered contiguously in parent order
+struct DerivedMesh {
+    std::vector<double> points;         // points ++ the apexes of the split cells, ascending
+    std::vector<int64_t> faceOff, faceVerts, owner, neighbour;
+    int64_t nPoints = 0, nFaces = 0, nInternal = 0, nCells = 0;
+    std::vector<int32_t> first;         // [nParent+1]  derived cells of parent c: first[c] .. first[c+1]
+    std::vector<int32_t> parent;        // [nCells]     parent of every derived cell
+};
+template <typename Label>
+std::string measure_mesh(const double* points, int64_t nPoints, const Label* faceOff, const Label* faceVerts, int64_t nFaces,
+                         const Label* owner, const Label* neighbour, int64_t nInternal, int64_t nCells, double tol,
+                         MeshQuality& q);
+template <typename Label>
+std::string derive_mesh(const double* points, int64_t nPoints, const Label* faceOff, const Label* faceVerts, int64_t nFaces,
+                        const Label* owner, const Label* neighbour, int64_t nInternal, int64_t nCells, const MeshQuality& q,
+                        DerivedMesh& out);
+#define CPF_NONPLANAR_EXTERN(L)                                                                                               \
+    extern template std::string measure_mesh<L>(const double*, int64_t, const L*, const L*, int64_t, const L*, const L*,    \
+                                                int64_t, int64_t, double, MeshQuality&);                                  \
+    extern template std::string derive_mesh<L>(const double*, int64_t, const L*, const L*, int64_t, const L*, const L*,     \
+                                               int64_t, int64_t, const MeshQuality&, DerivedMesh&);
+CPF_NONPLANAR_EXTERN(int32_t)
+CPF_NONPLANAR_EXTERN(int64_t)
+#undef CPF_NONPLANAR_EXTERN
+constexpr double kNonPlanarTolDefault = 1e-11;  // option "nonplanar_tol" (docs/experiments.md, "Warped cells")
+
 // stores `message` as the context's last error (cpf_last_error); for entry points implemented outside cpf_api.cpp
 void set_context_error(cpf_context* ctx, const char* message);
 // what the sharded-cloud layer (cpf_shard.cpp) needs to know about a context it borrows
@@ -64,5 +106,6 @@ bool context_timing(const cpf_context* ctx);        // cpf_timing_enable state
 int64_t context_cells(const cpf_context* ctx);      // 0: no mesh yet
 bool context_step_settled_z(const cpf_context* ctx); // the most recent cpf_step_dev left z settled on its arrays (CPF_STEP_Z_SETTLED)
 bool vtu_binary(const cpf_context* ctx);            // option "vtu_binary"
+bool context_derived(const cpf_context* ctx);       // the mesh has cells decomposed into tets (cpf_get_mesh_quality)
 
 }  // namespace cpf

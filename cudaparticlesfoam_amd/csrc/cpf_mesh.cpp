@@ -28,7 +28,7 @@ inline Vec at(const double* p, int64_t i) { return {p[3 * i], p[3 * i + 1], p[3 
 // average, area-weighted centre (the scheme of OpenFOAM's face centres/areas; exact for planar
 // faces, best-fit plane through the centre otherwise).
 template <typename Label>
-bool face_plane(const double* pts, const Label* verts, int nv, Vec& n, Vec& centre) {
+bool face_plane(const double* pts, const Label* verts, int nv, Vec& n, Vec& centre, double* area = nullptr) {
     Vec est{0, 0, 0};
     for (int i = 0; i < nv; ++i) est = est + at(pts, verts[i]);
     est = {est.x / nv, est.y / nv, est.z / nv};
@@ -45,6 +45,7 @@ bool face_plane(const double* pts, const Label* verts, int nv, Vec& n, Vec& cent
     }
     centre = sumA > 0.0 ? Vec{sumAc.x / (3.0 * sumA), sumAc.y / (3.0 * sumA), sumAc.z / (3.0 * sumA)} : est;
     double len = std::sqrt(dot(sumN, sumN));
+    if (area) *area = 0.5 * len;
     if (!(len > 0.0)) return false;
     n = {sumN.x / len, sumN.y / len, sumN.z / len};
     // Components that are rounding noise (|n_k| <= 1e-12 of a unit normal: the cross products of a face that lies in a
@@ -431,5 +432,316 @@ template std::string build_tables<int32_t>(const double*, int64_t, const int32_t
                                            const int32_t*, const int32_t*, int64_t, int64_t, HostTables&);
 template std::string build_tables<int64_t>(const double*, int64_t, const int64_t*, const int64_t*, int64_t,
                                            const int64_t*, const int64_t*, int64_t, int64_t, HostTables&);
+
+
+// ---- warped and concave cells (DESIGN.md "Warped cells").  The walk's one plane per face is exact only where faces are planar
+// and cells convex.  measure_mesh scores every face and cell; derive_mesh rewrites the cells that fail into the fan of tets the
+// reference walks (oracle/tetmesh.py, poly_to_tets: apex = the cell centre, one tet per face triangle (f[0], f[k], f[k+1])),
+// and build_tables then sees an ordinary mixed tet / polyhedron mesh with face groups.
+namespace {
+
+// OpenFOAM's face centre and area vector (primitiveMeshFaceCentresAndAreas), in the order cases/polymesh.py states it
+template <typename Label>
+void of_face(const double* pts, const Label* v, int nv, Vec& ctr, Vec& area) {
+    if (nv == 3) {
+        const Vec p0 = at(pts, v[0]), p1 = at(pts, v[1]), p2 = at(pts, v[2]);
+        const Vec s = (p0 + p1) + p2;
+        ctr = {(1.0 / 3.0) * s.x, (1.0 / 3.0) * s.y, (1.0 / 3.0) * s.z};
+        const Vec c = cross(p1 - p0, p2 - p0);
+        area = {0.5 * c.x, 0.5 * c.y, 0.5 * c.z};
+        return;
+    }
+    Vec est{0, 0, 0};
+    for (int i = 0; i < nv; ++i) est = est + at(pts, v[i]);
+    est = {est.x / nv, est.y / nv, est.z / nv};
+    Vec sumN{0, 0, 0}, sumAc{0, 0, 0};
+    double sumA = 0.0;
+    for (int i = 0; i < nv; ++i) {
+        const Vec p = at(pts, v[i]), q = at(pts, v[i + 1 == nv ? 0 : i + 1]);
+        const Vec c = (p + q) + est;
+        const Vec nrm = cross(q - p, est - p);
+        const double a = std::sqrt(dot(nrm, nrm));
+        sumN = sumN + nrm;
+        sumA += a;
+        sumAc = sumAc + Vec{a * c.x, a * c.y, a * c.z};
+    }
+    if (sumA > 0.0) {
+        const double m = std::max(sumA, 1e-300);
+        ctr = {(1.0 / 3.0) * sumAc.x / m, (1.0 / 3.0) * sumAc.y / m, (1.0 / 3.0) * sumAc.z / m};
+    } else {
+        ctr = est;
+    }
+    area = {0.5 * sumN.x, 0.5 * sumN.y, 0.5 * sumN.z};
+}
+
+}  // namespace
+
+template <typename Label>
+std::string measure_mesh(const double* points, int64_t nPoints, const Label* faceOff, const Label* faceVerts, int64_t nFaces,
+                         const Label* owner, const Label* neighbour, int64_t nInternal, int64_t nCells, double tol,
+                         MeshQuality& q) {
+    // (the same index checks as build_tables: everything below trusts the arrays)
+    HostTables probe;
+    if (nCells <= 0 || nFaces <= 0 || nPoints <= 0 || nInternal < 0 || nInternal > nFaces || faceOff[0] != 0)
+        return build_tables<Label>(points, nPoints, faceOff, faceVerts, nFaces, owner, neighbour, nInternal, nCells, probe);
+    for (int64_t f = 0; f < nFaces; ++f) {
+        if (faceOff[f + 1] - faceOff[f] < 3 || owner[f] < 0 || owner[f] >= nCells ||
+            (f < nInternal && (neighbour[f] < 0 || neighbour[f] >= nCells || neighbour[f] == owner[f])))
+            return build_tables<Label>(points, nPoints, faceOff, faceVerts, nFaces, owner, neighbour, nInternal, nCells, probe);
+    }
+    for (int64_t i = 0; i < (int64_t)faceOff[nFaces]; ++i)
+        if (faceVerts[i] < 0 || faceVerts[i] >= nPoints)
+            return build_tables<Label>(points, nPoints, faceOff, faceVerts, nFaces, owner, neighbour, nInternal, nCells, probe);
+    q = MeshQuality();
+    q.tol = tol;
+    q.nCells = nCells;
+    // mesh.cells(): owned faces ascending, then neighbour faces ascending
+    q.cellOff.assign((size_t)nCells + 1, 0);
+    for (int64_t f = 0; f < nFaces; ++f) q.cellOff[(size_t)owner[f] + 1]++;
+    for (int64_t f = 0; f < nInternal; ++f) q.cellOff[(size_t)neighbour[f] + 1]++;
+    for (int64_t c = 0; c < nCells; ++c) q.cellOff[(size_t)c + 1] += q.cellOff[(size_t)c];
+    q.cellFaces.resize((size_t)q.cellOff[(size_t)nCells]);
+    {
+        std::vector<int64_t> fill(q.cellOff.begin(), q.cellOff.end() - 1);
+        for (int64_t f = 0; f < nFaces; ++f) q.cellFaces[(size_t)fill[(size_t)owner[f]]++] = f;
+        for (int64_t f = 0; f < nInternal; ++f) q.cellFaces[(size_t)fill[(size_t)neighbour[f]]++] = f;
+    }
+    // face planes (the walk's: face_plane) and non-planarity eta_f = max |n . (v - c)| / sqrt(A_f)
+    std::vector<double> fn((size_t)nFaces * 4);
+    std::vector<char> faceBad((size_t)nFaces, 0);
+    for (int64_t f = 0; f < nFaces; ++f) {
+        const Label* v = faceVerts + faceOff[f];
+        const int nv = (int)(faceOff[f + 1] - faceOff[f]);
+        Vec n, c;
+        double area = 0.0;
+        if (!face_plane(points, v, nv, n, c, &area)) return "face " + std::to_string(f) + " has zero area";
+        double worst = 0.0;
+        for (int i = 0; i < nv; ++i) worst = std::max(worst, std::fabs(dot(n, at(points, v[i]) - c)));
+        const double eta = worst / std::sqrt(area);
+        if (q.worstFace < 0 || eta > q.maxEta) { q.maxEta = eta; q.worstFace = f; }
+        faceBad[(size_t)f] = eta > tol ? 1 : 0;
+        fn[4 * f + 0] = n.x; fn[4 * f + 1] = n.y; fn[4 * f + 2] = n.z; fn[4 * f + 3] = dot(n, c);
+    }
+    // OpenFOAM's cell centres and volumes (primitiveMeshCellCentresAndVols, as cases/polymesh.py restates it): the apexes
+    std::vector<Vec> fc((size_t)nFaces), fa((size_t)nFaces);
+    for (int64_t f = 0; f < nFaces; ++f)
+        of_face(points, faceVerts + faceOff[f], (int)(faceOff[f + 1] - faceOff[f]), fc[(size_t)f], fa[(size_t)f]);
+    std::vector<Vec> est((size_t)nCells, Vec{0, 0, 0}), ctr((size_t)nCells, Vec{0, 0, 0});
+    std::vector<double> cnt((size_t)nCells, 0.0), vol((size_t)nCells, 0.0);
+    for (int64_t f = 0; f < nFaces; ++f) { est[(size_t)owner[f]] = est[(size_t)owner[f]] + fc[(size_t)f]; cnt[(size_t)owner[f]] += 1.0; }
+    for (int64_t f = 0; f < nInternal; ++f) { est[(size_t)neighbour[f]] = est[(size_t)neighbour[f]] + fc[(size_t)f]; cnt[(size_t)neighbour[f]] += 1.0; }
+    for (int64_t c = 0; c < nCells; ++c) { const double k = cnt[(size_t)c]; est[(size_t)c] = {est[(size_t)c].x / k, est[(size_t)c].y / k, est[(size_t)c].z / k}; }
+    auto pyramid = [&](int64_t f, int64_t c, bool own) {
+        const Vec e = est[(size_t)c], F = fc[(size_t)f], A = fa[(size_t)f];
+        const Vec d = own ? F - e : e - F;
+        const double pyr = (A.x * d.x + A.y * d.y) + A.z * d.z;
+        const Vec pc{0.75 * F.x + 0.25 * e.x, 0.75 * F.y + 0.25 * e.y, 0.75 * F.z + 0.25 * e.z};
+        ctr[(size_t)c] = ctr[(size_t)c] + Vec{pyr * pc.x, pyr * pc.y, pyr * pc.z};
+        vol[(size_t)c] += pyr;
+    };
+    for (int64_t f = 0; f < nFaces; ++f) pyramid(f, owner[f], true);
+    for (int64_t f = 0; f < nInternal; ++f) pyramid(f, neighbour[f], false);
+    q.centre.resize((size_t)nCells * 3);
+    for (int64_t c = 0; c < nCells; ++c) {
+        const double V = vol[(size_t)c];
+        Vec C = est[(size_t)c];
+        if (std::fabs(V) > 1e-300) { const double w = V == 0.0 ? 1.0 : V; C = {ctr[(size_t)c].x / w, ctr[(size_t)c].y / w, ctr[(size_t)c].z / w}; }
+        q.centre[3 * c] = C.x; q.centre[3 * c + 1] = C.y; q.centre[3 * c + 2] = C.z;
+        vol[(size_t)c] = V / 3.0;
+    }
+    // non-convexity xi_c = (largest distance of a vertex of the cell outside one of its own face planes) / cbrt(volume), the
+    // flag rule, and which flagged cells have a fan of positive tets (star-shaped from the centre)
+    q.flagged.assign((size_t)nCells, 0);
+    for (int64_t c = 0; c < nCells; ++c) {
+        const int64_t s0 = q.cellOff[(size_t)c], s1 = q.cellOff[(size_t)c + 1];
+        double out = 0.0;
+        bool bad = false;
+        for (int64_t s = s0; s < s1; ++s) {
+            const int64_t f = q.cellFaces[(size_t)s];
+            bad = bad || faceBad[(size_t)f];
+            const double sg = owner[f] == c ? -1.0 : 1.0;                // into the cell
+            const Vec n{sg * fn[4 * f], sg * fn[4 * f + 1], sg * fn[4 * f + 2]};
+            const double d = sg * fn[4 * f + 3];
+            for (int64_t t = s0; t < s1; ++t) {
+                const int64_t g = q.cellFaces[(size_t)t];
+                for (int64_t i = faceOff[g]; i < (int64_t)faceOff[g + 1]; ++i) out = std::max(out, d - dot(n, at(points, faceVerts[i])));
+            }
+        }
+        const double V = vol[(size_t)c];
+        const double xi = V > 0.0 ? out / std::cbrt(V) : HUGE_VAL;
+        if (q.worstCell < 0 || xi > q.maxXi) { q.maxXi = xi; q.worstCell = c; }
+        if (bad || xi > tol) q.flagged[(size_t)c] = 1;
+    }
+    const Vec* apexes = reinterpret_cast<const Vec*>(q.centre.data());
+    for (int64_t c = 0; c < nCells; ++c) {
+        if (!q.flagged[(size_t)c]) continue;
+        ++q.nFlagged;
+        const Vec A = apexes[c];
+        bool pos = true;
+        for (int64_t s = q.cellOff[(size_t)c]; s < q.cellOff[(size_t)c + 1] && pos; ++s) {
+            const int64_t f = q.cellFaces[(size_t)s];
+            const Label* v = faceVerts + faceOff[f];
+            const int nv = (int)(faceOff[f + 1] - faceOff[f]);
+            for (int k = 1; k + 1 < nv && pos; ++k) {
+                Vec p0 = at(points, v[0]), pa = at(points, v[k]), pb = at(points, v[k + 1]);
+                if (owner[f] != c) std::swap(pa, pb);
+                pos = dot(cross(pa - p0, pb - p0), p0 - A) > 0.0;
+            }
+        }
+        if (pos) q.flagged[(size_t)c] = 2;
+        else ++q.nBad;
+    }
+    return std::string();
+}
+
+template <typename Label>
+std::string derive_mesh(const double* points, int64_t nPoints, const Label* faceOff, const Label* faceVerts, int64_t nFaces,
+                        const Label* owner, const Label* neighbour, int64_t nInternal, int64_t nCells, const MeshQuality& q,
+                        DerivedMesh& out) {
+    out = DerivedMesh();
+    if (!q.decompose()) {                                        // nothing to decompose (or a bad cell): the derived mesh IS the mesh
+        out.points.assign(points, points + 3 * nPoints);
+        out.faceOff.assign(faceOff, faceOff + nFaces + 1);
+        out.faceVerts.assign(faceVerts, faceVerts + faceOff[nFaces]);
+        out.owner.assign(owner, owner + nFaces);
+        out.neighbour.assign(neighbour, neighbour + nInternal);
+        out.nPoints = nPoints; out.nFaces = nFaces; out.nInternal = nInternal; out.nCells = nCells;
+        out.first.resize((size_t)nCells + 1);
+        out.parent.resize((size_t)nCells);
+        for (int64_t c = 0; c <= nCells; ++c) out.first[(size_t)c] = (int32_t)c;
+        for (int64_t c = 0; c < nCells; ++c) out.parent[(size_t)c] = (int32_t)c;
+        return std::string();
+    }
+    const std::vector<char>& split = q.flagged;                  // 2 = decompose
+    auto isSplit = [&](int64_t c) { return split[(size_t)c] == 2; };
+    auto faceSplit = [&](int64_t f) { return isSplit(owner[f]) || (f < nInternal && isSplit(neighbour[f])); };
+    auto nv = [&](int64_t f) { return (int64_t)(faceOff[f + 1] - faceOff[f]); };
+    // derived cells, contiguous in parent order; per (cell, slot): its first tet (split cells) or its first loop (the others)
+    out.first.assign((size_t)nCells + 1, 0);
+    std::vector<int64_t> slotBase(q.cellFaces.size());
+    std::vector<int64_t> slotOwn((size_t)nFaces, -1), slotNei((size_t)nInternal, -1);
+    for (int64_t c = 0; c < nCells; ++c) {
+        int64_t k = 0;
+        for (int64_t s = q.cellOff[(size_t)c]; s < q.cellOff[(size_t)c + 1]; ++s) {
+            const int64_t f = q.cellFaces[(size_t)s];
+            (owner[f] == c ? slotOwn[(size_t)f] : slotNei[(size_t)f]) = s;
+            slotBase[(size_t)s] = k;
+            k += isSplit(c) || faceSplit(f) ? nv(f) - 2 : 1;
+        }
+        const int64_t nd = isSplit(c) ? k : 1;
+        if ((int64_t)out.first[(size_t)c] + nd > INT32_MAX - 16) return "derived mesh too large for 32-bit cell ids";
+        out.first[(size_t)c + 1] = out.first[(size_t)c] + (int32_t)nd;
+    }
+    const int64_t nDerived = out.first[(size_t)nCells];
+    out.nCells = nDerived;
+    out.parent.resize((size_t)nDerived);
+    for (int64_t c = 0; c < nCells; ++c)
+        for (int32_t d = out.first[(size_t)c]; d < out.first[(size_t)c + 1]; ++d) out.parent[(size_t)d] = (int32_t)c;
+    // points ++ the apexes of the split cells, ascending
+    out.points.assign(points, points + 3 * nPoints);
+    std::vector<int64_t> apexId((size_t)nCells, -1);
+    for (int64_t c = 0; c < nCells; ++c)
+        if (isSplit(c)) {
+            apexId[(size_t)c] = (int64_t)out.points.size() / 3;
+            for (int k = 0; k < 3; ++k) out.points.push_back(q.centre[3 * c + k]);
+        }
+    out.nPoints = (int64_t)out.points.size() / 3;
+    // every derived face once, as its owner (the lower derived cell: the first to list it) lists it: (owner, neighbour or -1,
+    // place in the owner's list of face loops, the loop)
+    struct Rec { int64_t own, nei, pos, off; int nv; };
+    std::vector<Rec> recs;
+    std::vector<int64_t> loops;
+    auto add = [&](int64_t own, int64_t nei, int64_t pos, std::initializer_list<int64_t> v) {
+        recs.push_back({own, nei, pos, (int64_t)loops.size(), (int)v.size()});
+        loops.insert(loops.end(), v.begin(), v.end());
+    };
+    // (cell, slot, triangle k) -> derived cell and the place of the triangle in that cell's list
+    auto side = [&](int64_t c, int64_t s, int64_t k, int64_t& d, int64_t& pos) {
+        if (isSplit(c)) { d = out.first[(size_t)c] + slotBase[(size_t)s] + (k - 1); pos = 0; }
+        else { d = out.first[(size_t)c]; pos = slotBase[(size_t)s] + (k - 1); }
+    };
+    for (int64_t f = 0; f < nFaces; ++f) {
+        const Label* v = faceVerts + faceOff[f];
+        const int64_t n = nv(f), a = owner[f], b = f < nInternal ? (int64_t)neighbour[f] : -1;
+        if (!faceSplit(f)) {
+            const int64_t dA = out.first[(size_t)a], dB = b >= 0 ? out.first[(size_t)b] : -1;
+            const bool flip = b >= 0 && dB < dA;
+            const int64_t s = flip ? slotNei[(size_t)f] : slotOwn[(size_t)f];
+            recs.push_back({flip ? dB : dA, flip ? dA : dB, slotBase[(size_t)s], (int64_t)loops.size(), (int)n});
+            loops.push_back(v[0]);
+            for (int64_t i = 1; i < n; ++i) loops.push_back(flip ? v[n - i] : v[i]);   // turned: (v0, v[n-1], ..., v1)
+            continue;
+        }
+        for (int64_t k = 1; k + 1 < n; ++k) {
+            int64_t dA, pA;
+            side(a, slotOwn[(size_t)f], k, dA, pA);
+            if (b < 0) { add(dA, -1, pA, {(int64_t)v[0], (int64_t)v[k], (int64_t)v[k + 1]}); continue; }
+            int64_t dB, pB;
+            side(b, slotNei[(size_t)f], k, dB, pB);
+            if (dA < dB) add(dA, dB, pA, {(int64_t)v[0], (int64_t)v[k], (int64_t)v[k + 1]});
+            else add(dB, dA, pB, {(int64_t)v[0], (int64_t)v[k + 1], (int64_t)v[k]});
+        }
+    }
+    // the inner facets of the split cells: tet (A, p0, pa, pb) lists (A, pa, p0), (A, pb, pa), (A, p0, pb) after its base; the
+    // facet over the directed base edge u -> v is shared with the tet over v -> u
+    std::vector<std::pair<std::pair<int64_t, int64_t>, std::pair<int64_t, int64_t>>> open;   // ((u, v), (tet, place))
+    for (int64_t c = 0; c < nCells; ++c) {
+        if (!isSplit(c)) continue;
+        const int64_t A = apexId[(size_t)c];
+        open.clear();
+        for (int64_t s = q.cellOff[(size_t)c]; s < q.cellOff[(size_t)c + 1]; ++s) {
+            const int64_t f = q.cellFaces[(size_t)s];
+            const Label* v = faceVerts + faceOff[f];
+            for (int64_t k = 1; k + 1 < nv(f); ++k) {
+                const int64_t t = out.first[(size_t)c] + slotBase[(size_t)s] + (k - 1);
+                int64_t p0 = v[0], pa = v[k], pb = v[k + 1];
+                if (owner[f] != c) std::swap(pa, pb);
+                const int64_t edge[3][2] = {{p0, pa}, {pa, pb}, {pb, p0}};
+                for (int e = 0; e < 3; ++e) {
+                    const int64_t u = edge[e][0], w = edge[e][1];
+                    size_t j = 0;
+                    while (j < open.size() && !(open[j].first.first == w && open[j].first.second == u)) ++j;
+                    if (j == open.size()) { open.push_back({{u, w}, {t, e + 1}}); continue; }
+                    // the earlier tet owns the facet and lists it as (A, v', u') over ITS edge u' -> v' = w -> u
+                    add(open[j].second.first, t, open[j].second.second, {A, u, w});
+                    open.erase(open.begin() + (std::ptrdiff_t)j);
+                }
+            }
+        }
+        if (!open.empty()) return "cell " + std::to_string(c) + ": its faces do not close (cannot decompose it into tets)";
+    }
+    // face order of cases.polymesh.build_polymesh_from_cells: internal faces by (owner, neighbour), boundary faces by owner,
+    // ties in the order the owner lists them
+    std::vector<int64_t> order(recs.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = (int64_t)i;
+    std::sort(order.begin(), order.end(), [&](int64_t i, int64_t j) {
+        const Rec &x = recs[(size_t)i], &y = recs[(size_t)j];
+        const bool bx = x.nei < 0, by = y.nei < 0;
+        if (bx != by) return by;
+        if (x.own != y.own) return x.own < y.own;
+        if (!bx && x.nei != y.nei) return x.nei < y.nei;
+        return x.pos < y.pos;
+    });
+    out.faceOff.assign(1, 0);
+    for (int64_t i : order) {
+        const Rec& r = recs[(size_t)i];
+        out.faceVerts.insert(out.faceVerts.end(), loops.begin() + r.off, loops.begin() + r.off + r.nv);
+        out.faceOff.push_back((int64_t)out.faceVerts.size());
+        out.owner.push_back(r.own);
+        if (r.nei >= 0) out.neighbour.push_back(r.nei);
+    }
+    out.nFaces = (int64_t)out.owner.size();
+    out.nInternal = (int64_t)out.neighbour.size();
+    return std::string();
+}
+
+#define CPF_NONPLANAR_INST(L)                                                                                                 \
+    template std::string measure_mesh<L>(const double*, int64_t, const L*, const L*, int64_t, const L*, const L*, int64_t,   \
+                                         int64_t, double, MeshQuality&);                                                    \
+    template std::string derive_mesh<L>(const double*, int64_t, const L*, const L*, int64_t, const L*, const L*, int64_t,    \
+                                        int64_t, const MeshQuality&, DerivedMesh&);
+CPF_NONPLANAR_INST(int32_t)
+CPF_NONPLANAR_INST(int64_t)
+#undef CPF_NONPLANAR_INST
 
 }  // namespace cpf

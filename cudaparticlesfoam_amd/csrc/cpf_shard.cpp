@@ -123,6 +123,11 @@ typedef HipDev CpfShardDev;
 
 bool cpfMakeDev(cpf_context* ctx, HipDev& d, std::string& why) {
     if (!ctx) { why = "null context"; return false; }
+    if (cpf::context_derived(ctx)) {            // (hand-off ownership by ranges of derived cells: not built yet)
+        why = "the mesh has warped or concave cells decomposed into tets (cpf_get_mesh_quality); the sharded cloud takes the "
+              "mesh's own cells only (option \"split_nonplanar\" 0 before cpf_set_mesh keeps them)";
+        return false;
+    }
     d.ctx = ctx;
     d.device = cpf::context_device(ctx);
     hipError_t e = hipSetDevice(d.device);

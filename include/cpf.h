@@ -138,7 +138,25 @@ int cpf_set_mesh_parts(cpf_context* ctx, const cpf_mesh_part* parts, int nParts)
  * "every particle lies inside the cell it claims"; the reference cannot run such meshes, so no reference fixture pins them.
  * The same holds for two conventions that are exact on the reference's meshes: components of a unit face normal <= 1e-12
  * are stored as zero, and with the Brownian kick on a one-cell-thick mesh the end point is mirrored about the front / back
- * plane before the walk (option "z_fold"). */
+ * plane before the walk (option "z_fold").
+ * VALIDITY DOMAIN: one plane per face is exact for planar faces and convex cells.  Every mesh is measured at ingest
+ * (cpf_get_mesh_quality): face non-planarity eta_f = max |n . (v - c)| / sqrt(A_f) over the face's vertices, cell
+ * non-convexity xi_c = the largest distance of a cell vertex outside one of the cell's own face planes / cbrt(V_c).  A cell
+ * with xi_c > tol or a face with eta_f > tol (option "nonplanar_tol", default 1e-11) is FLAGGED, and (option "split_nonplanar",
+ * default 1) walked as the fan of tets the reference walks: apex = OpenFOAM's cell centre, one tet per face triangle
+ * (f[0], f[k], f[k+1]) -- exact on warped faces.  Inside the library particles then carry DERIVED cell ids (the tets of parent
+ * cell c are numbered contiguously, in parent order); every id this API hands the caller -- cpf_get_particles, the VTU frames,
+ * cpf_cell_histogram_dev's weights, cpf_set_velocity's U, cpf_set_particles' cells -- is a PARENT id.  The _dev entry points that
+ * work on caller-owned arrays (cpf_step_dev, cpf_locate_initial_dev, cpf_sort_by_cell_dev*, cpf_pack_leavers_dev,
+ * cpf_unpack_arrivals_dev) keep DERIVED ids there; cpf_cells_to_parent_dev maps them; cpf_mesh_info and cpf_get_mesh_tables
+ * describe the derived cells.  NOT DECOMPOSED, walked with one plane per face exactly as before: a mesh without flagged cells;
+ * a mesh with a flagged cell whose fan would hold a tet of non-positive volume (not star-shaped from its centre; counted in
+ * nBadCells -- e.g. warped faces with runs of collinear vertices); and a mesh where a whole cell would see a face it shares
+ * with a decomposed cell as more than one plane (its triangles not coplanar to 1e-9: faces of aspect ratio beyond a few
+ * hundred at the default tolerance).  Such meshes keep the one-plane model's error on warped faces.  tol is absolute while
+ * the rounding noise of eta and xi grows with |coordinates| / cell size (about 1e-16 of it): planar meshes far from the origin
+ * for their cell size (1e5 and more) are flagged by noise and decomposed.  On a mesh with decomposed cells cpf_shard_create,
+ * cpf_pack_leavers_dev, cpf_set_tets and the reference-layout stages (cpf_stage_*) refuse with a message. */
 int cpf_set_mesh(cpf_context* ctx, const double* points, int64_t nPoints, const int32_t* faceOffsets,
                  const int32_t* faceVerts, int64_t nFaces, const int32_t* owner, const int32_t* neighbour,
                  int64_t nInternal, int64_t nCells);
@@ -180,6 +198,38 @@ int cpf_mesh_flags_host(const double* points, int64_t nPoints, const int32_t* fa
 int cpf_mesh_box_records_host(const double* points, int64_t nPoints, const int32_t* faceOffsets, const int32_t* faceVerts,
                               int64_t nFaces, const int32_t* owner, const int32_t* neighbour, int64_t nInternal, int64_t nCells,
                               int32_t* isBox, double* boxRec);
+
+/* Mesh quality (see cpf_set_mesh, "VALIDITY DOMAIN") of the mesh as the caller gave it. */
+typedef struct cpf_mesh_quality {
+    double maxNonPlanarity;   /* max eta_f over the faces ... */
+    int64_t worstFace;        /* ... and its face */
+    double maxNonConvexity;   /* max xi_c over the cells ... */
+    int64_t worstCell;        /* ... and its cell */
+    int64_t nCells;           /* cells as given (parent cells) */
+    int64_t nFlaggedCells;    /* cells flagged by the rule */
+    int64_t nBadCells;        /* flagged cells left whole: their fan has a tet of non-positive volume */
+    int64_t nDerivedCells;    /* cells the walk runs on (== nCells when none is decomposed) */
+    double tol;               /* the tolerance applied (option "nonplanar_tol") */
+} cpf_mesh_quality;
+int cpf_get_mesh_quality(const cpf_context* ctx, cpf_mesh_quality* out);
+/* ... on the host alone, for tolerance tol; split = 0 reports nDerivedCells as if "split_nonplanar" were 0. */
+int cpf_mesh_quality_host(const double* points, int64_t nPoints, const int32_t* faceOffsets, const int32_t* faceVerts,
+                          int64_t nFaces, const int32_t* owner, const int32_t* neighbour, int64_t nInternal, int64_t nCells,
+                          double tol, int split, cpf_mesh_quality* out);
+/* The derived polyMesh cpf_set_mesh walks (on the host alone): the flagged cells replaced by their fans of tets; faces in the
+ * order of an OpenFOAM polyMesh (internal faces by (owner, neighbour), boundary faces by owner; ties in the order the owner cell
+ * lists them), points = the mesh's points ++ the apexes of the decomposed cells in ascending cell order, first[nCells+1] = the
+ * derived cells of parent c: first[c] .. first[c+1].  Call with the output pointers NULL for sizes[5] = {nPoints, nFaces,
+ * nFaceVerts, nInternal, nCells} of the derived mesh, then again with pointsOut[nPoints][3], faceOffOut[nFaces+1],
+ * faceVertsOut[nFaceVerts], ownerOut[nFaces], neighbourOut[nInternal], first[nCells+1] (any may be NULL).  Without flagged
+ * cells the derived mesh is the mesh as given. */
+int cpf_build_derived_mesh_host(const double* points, int64_t nPoints, const int32_t* faceOffsets, const int32_t* faceVerts,
+                                int64_t nFaces, const int32_t* owner, const int32_t* neighbour, int64_t nInternal, int64_t nCells,
+                                double tol, int64_t sizes[5], double* pointsOut, int32_t* faceOffOut, int32_t* faceVertsOut,
+                                int32_t* ownerOut, int32_t* neighbourOut, int32_t* first);
+/* Derived cell ids (device int32 [n], e.g. the cell array of cpf_step_dev) -> parent ids; negative codes pass through; in and
+ * out may alias.  Asynchronous on the context stream.  A copy on meshes without decomposed cells. */
+int cpf_cells_to_parent_dev(cpf_context* ctx, const int32_t* in, int32_t* out, int64_t n);
 
 /* Cell-constant velocity U[nCells][3] (host, zero-copy from U.primitiveField()).  Replaces the
  * 12x replication loop + cudaUpdateVelocity of src/advect.H:44-57 (cuda/particles.cu:718-749):
@@ -295,6 +345,10 @@ int cpf_set_seed(cpf_context* ctx, uint32_t seed);
  *                   has no such diagnostics, and they cost the step kernel a resident wave (0.16 -> 0.22 ms
  *                   per 1e7-particle launch)
  *   "timing_stride" cpf_timing_enable brackets every k-th step launch only (default 1)
+ *   "nonplanar_tol" (1e-11; set BEFORE cpf_set_mesh) the tolerance of the flag rule for warped faces and concave cells (see
+ *                   cpf_set_mesh, "VALIDITY DOMAIN"; the default's measurement: docs/experiments.md, "Warped cells")
+ *   "split_nonplanar" (1; set BEFORE cpf_set_mesh) walk flagged cells as their fans of tets; 0 = one plane per face on every
+ *                   mesh (the model before decomposition existed; results then differ from the reference on warped meshes)
  *   "sort_interval" cpf_step re-sorts the context-owned cloud by cell every N cycles (default 50, 0 = never);
  *                   invisible to callers: cpf_get_particles always answers in particle-id order.  The sort writes
  *                   into a second set of particle arrays that then swap roles with the first: 36 B per particle
@@ -350,7 +404,8 @@ int cpf_pack_leavers_dev(cpf_context* ctx, double* x, double* y, double* z, int3
  * (device doubles, overwritten; lost/frozen particles are not counted).  scale = this rank's measured cost per
  * particle-step (or 1 for equal-count cuts); the host layer all-reduces the weights over the ranks. */
 int cpf_cell_histogram_dev(cpf_context* ctx, const int32_t* cell, int64_t n, double scale, double* weights_dev);
-/* step 2: cellLo_dev[0..nRanks] (device int32) = contiguous cell ranges of equal total weight:
+/* step 2 (on a mesh with decomposed cells: PARENT cell ranges, as the weights):
+ * cellLo_dev[0..nRanks] (device int32) = contiguous cell ranges of equal total weight:
  * cellLo[q] = #{ i in 0..nCells : w[0]+...+w[i-1] < total*q/nRanks }, cellLo[0] = 0, cellLo[nRanks] = nCells. */
 int cpf_cell_ranges_dev(cpf_context* ctx, const double* weights_dev, int nRanks, int32_t* cellLo_dev);
 /* append nRecv received records at index nStay.. of the arrays */
