@@ -89,6 +89,12 @@ struct cpf_context {
     // streamed z, cleared by everything else that writes x, y, z or cell -- except a sort, which only permutes
     bool zSettled = false;
     bool lastStepZSettled = false;              // what the most recent cpf_step_dev left behind on ITS arrays (cpf_shard.cpp)
+    // "a live particle's z is not finite", written by a flat launch that streams z (StreamState::zBad, pinned); evZBad is recorded
+    // behind such a launch, and while zBadPending the launch's verdict has not been read: the first launch that would leave z
+    // alone waits for it -- one wait per unsettling event, no pass over the cloud
+    unsigned* h_zBad = nullptr;
+    hipEvent_t evZBad = nullptr;
+    bool zBadPending = false;
     // "VertexVelocity" advect only: the tet decomposition and one velocity per tet-mesh vertex
     double* d_tetPos = nullptr; int32_t* d_tets = nullptr; double* d_vertVel = nullptr;
     int64_t nTetVerts = 0, nTets = 0; int tetsPerCell = 0; bool haveVertVel = false;
@@ -444,6 +450,15 @@ void fieldFlagArrived(cpf_context* ctx) {
     ctx->streamState.flatField = ctx->h_occupied[2] == 0;
     ctx->fieldFlagPending = false;
 }
+// the verdict of the flat launch that streamed z last (cpf_context::h_zBad), waited for if it is still on its way: true = a live
+// particle's z is not finite, and z is not settled
+bool zBadArrived(cpf_context* ctx) {
+    if (ctx->zBadPending) {
+        (void)hipEventSynchronize(ctx->evZBad);
+        ctx->zBadPending = false;
+    }
+    return *static_cast<volatile unsigned*>(ctx->h_zBad) != 0u;
+}
 void pollFieldFlag(cpf_context* ctx) {
     if (ctx->fieldFlagPending && hipEventQuery(ctx->evFieldFlag) == hipSuccess) fieldFlagArrived(ctx);
 }
@@ -475,6 +490,9 @@ int cpf_create(int device, cpf_context** out) {
     if (e == hipSuccess) e = hipHostMalloc((void**)&ctx->h_occupied, 32, hipHostMallocDefault);
     if (e == hipSuccess) { ctx->h_occupied[0] = ctx->h_occupied[1] = 0; ctx->h_occupied[2] = 1; ctx->streamState.occupiedHost = ctx->h_occupied; }
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->evFieldFlag, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&ctx->h_zBad, 64, hipHostMallocDefault);
+    if (e == hipSuccess) { *ctx->h_zBad = 0u; ctx->streamState.zBad = ctx->h_zBad; }
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->evZBad, hipEventDisableTiming);
     if (e == hipSuccess) e = hipMalloc((void**)&ctx->streamState.d_grab, cpf::kStreamGrabBytes);
     if (e == hipSuccess) e = hipMemset(ctx->streamState.d_grab, 0, cpf::kStreamGrabBytes);
     if (e == hipSuccess) {
@@ -509,6 +527,8 @@ int cpf_destroy(cpf_context* ctx) {
     freeDev(ctx->d_occupied);
     if (ctx->evFieldFlag) { (void)hipEventDestroy(ctx->evFieldFlag); ctx->evFieldFlag = nullptr; }
     if (ctx->h_occupied) { (void)hipHostFree(ctx->h_occupied); ctx->h_occupied = nullptr; ctx->streamState.occupiedHost = nullptr; }
+    if (ctx->evZBad) { (void)hipEventDestroy(ctx->evZBad); ctx->evZBad = nullptr; }
+    if (ctx->h_zBad) { (void)hipHostFree(ctx->h_zBad); ctx->h_zBad = nullptr; ctx->streamState.zBad = nullptr; }
     freeDev(ctx->d_tetPos); freeDev(ctx->d_tets); freeDev(ctx->d_vertVel); freeDev(ctx->d_vertCone); freeDev(ctx->d_vertApex);
     freeDev(ctx->snapDev);
     if (ctx->snapHost) { (void)hipHostFree(ctx->snapHost); ctx->snapHost = nullptr; }
@@ -882,6 +902,14 @@ int cpf_step_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cel
     for (int c = 0; c < nLaunch; ++c) {
         const cpf::StepPlan plan = cpf::plan_step(m, ctx->streamState, ctx->stepVariant, vertexU ? &vf : nullptr, n, cycPerLaunch, D,
                                                   flags, ctx->stats);
+        // A flat launch that streams z reports live particles whose z is not finite (StreamState::zBad): z of such a cloud is not
+        // settled, whatever the flat cycle's fixed points are -- at a wall the streaming launch mirrors such a particle to NaN in
+        // x and y, a launch without z would reflect it.  The verdict of the launch that settled z is read here, once, before the
+        // first launch that would rely on it; a launch that streams z starts from a clean flag
+        if (plan.flat_body(ctx->streamState, settled) && zBadArrived(ctx)) settled = false;
+        // ("flat_z" 0: nobody asks.  A verdict still pending belongs to an older launch of the same kind: its 1 may stand)
+        const bool reportsZ = n > 0 && cycPerLaunch > 0 && plan.flat() && !settled && ctx->streamState.flatZ != 0;
+        if (reportsZ && !ctx->zBadPending) *static_cast<volatile unsigned*>(ctx->h_zBad) = 0u;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         const bool timed = ctx->timing && (ctx->timingLaunch++ % (uint64_t)ctx->timingStride) == 0;
         // the streaming kernels stamp the events with the dispatch's own begin / end (StepPlan::stamped); any other kernel,
@@ -907,6 +935,10 @@ int cpf_step_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cel
         }
         CPF_HIP(ctx, le);
         if (n > 0 && cycPerLaunch > 0) settled = plan.flat();
+        if (reportsZ) {
+            CPF_HIP(ctx, hipEventRecord(ctx->evZBad, ctx->stream));
+            ctx->zBadPending = true;
+        }
         if (timed) {
             if (!stamped) CPF_HIP(ctx, hipEventRecord(e1, ctx->stream));
             ctx->events.emplace_back(e0, e1);
@@ -1246,6 +1278,8 @@ int cpf_step_kernel_name(cpf_context* ctx, double D, unsigned flags, char* buf, 
                  p.cone ? "cone locate" : (ctx->d_vertCone || ctx->vertConeWhy.empty() ? "all tets" : ("all tets: " + ctx->vertConeWhy).c_str()));
     else if (p.kernel == cpf::StepPlan::kAhead)
         snprintf(tmp, sizeof tmp, "cpf::step_kernel_ahead<%s, %s>", b[p.reflect], b[p.stats]);
+    else if (p.flat_body(ctx->streamState, ctx->zSettled) && !zBadArrived(ctx))       // (what cpf_step launches next on the context's own cloud)
+        snprintf(tmp, sizeof tmp, "cpf::step_kernel_stream_flat<%s, %s, %s, %d>", b[p.reflect], b[p.storeVel], b[p.stats], p.lookup);
     else if (p.kernel == cpf::StepPlan::kStream)
         snprintf(tmp, sizeof tmp, "cpf::step_kernel_stream<%s, %s, %s, %s, %d>", b[p.brown], b[p.reflect], b[p.storeVel], b[p.stats], p.lookup);
     else if (p.kernel == cpf::StepPlan::kCoop)

@@ -69,6 +69,9 @@ struct StreamState {
     bool flatField = false;
     int flat = 1;             // "flat_walk": 0 = never (diagnostics; bit-identical either way)
     int flatZ = 1;            // "flat_z": 0 = the flat instantiations always stream z (A/B; bit-identical either way)
+    // pinned host word that a flat launch streaming z sets when it loads a live particle with a non-finite z (StreamArgs::zBad);
+    // its owner reads it behind that launch, before it calls the cloud settled.  Null: nobody asks (such a cloud never counts as settled)
+    unsigned* zBad = nullptr;
 };
 
 constexpr int kCoopMaxCells = 1 << 24;     // 32-bit record byte offsets in step_kernel_coop (plan_step falls back above that)
@@ -95,6 +98,8 @@ struct StepPlan {
     bool stamped() const { return kernel == kStream || kernel == kStreamVertex; }
     // the flat walk: every live particle's z is settled behind it (CPF_STEP_Z_SETTLED)
     bool flat() const { return kernel == kStream && (lookup == 8 || lookup == 9); }
+    // ... on a cloud whose z is settled: step_kernel_stream_flat, the body in which z does not exist ("flat_z" 0: never)
+    bool flat_body(const StreamState& ss, bool zSettled) const { return flat() && zSettled && ss.flatZ != 0; }
 };
 // vf: the "VertexVelocity" cycle's tables (null: the cell-constant cycle); stats: statistics counters are on
 StepPlan plan_step(const MeshView& m, const StreamState& ss, int variant, const VertexField* vf, int64_t n, int nCyc, double D,

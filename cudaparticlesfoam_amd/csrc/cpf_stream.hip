@@ -90,6 +90,7 @@ struct StreamKernArgs {
 };
 static_assert(offsetof(StreamKernArgs, x) == 0 && offsetof(StreamKernArgs, cell) == 24, "kernarg_cloud_ptrs reads bytes 0..31");
 constexpr int kKernArgHitSpill = (int)(offsetof(StreamKernArgs, sa) + offsetof(StreamArgs, hitSpill));
+constexpr int kKernArgZBad = (int)(offsetof(StreamKernArgs, sa) + offsetof(StreamArgs, zBad));
 // the Brownian kick's own arguments are read from the kernarg segment where they are needed -- the particle ids once per tile,
 // step0 / seed / sigma once per cycle -- instead of holding seven scalar registers for the whole kernel (CPF_STREAM_BROWN_KERNARG)
 constexpr int kKernArgGid = (int)offsetof(StreamKernArgs, gid), kKernArgSigma = (int)offsetof(StreamKernArgs, sigma);
@@ -156,6 +157,12 @@ constexpr int kKernArgStep0 = (int)offsetof(StreamKernArgs, step0), kKernArgSeed
 #ifndef CPF_STREAM_WAVES_FLAT
 #define CPF_STREAM_WAVES_FLAT CPF_STREAM_WAVES
 #endif
+// the body without z (step_kernel_stream_flat): waves per SIMD the launcher fills, 0 = what the occupancy query says (A/B builds).
+// Its 62 VGPRs / 3840 B of LDS admit an eighth wave, and here it pays: one box, bench.py's value 97 469-97 770 held at seven waves,
+// 98 512-99 584 with eight (the parent 92 607-92 620).  (The three-coordinate body lost 17 % when squeezed into an eighth wave's 64.)
+#ifndef CPF_STREAM_WAVES_FLAT_BODY
+#define CPF_STREAM_WAVES_FLAT_BODY 0
+#endif
 template <bool BROWNIAN, bool STORE_VEL, bool STATS, int LOOKUP>
 // LOOKUP 2 / 3 (mixed records): one wave less; LOOKUP 4 (sparse clouds: pipelined per-lane gathers, 24 more registers): 5
 struct StreamOccupancy {
@@ -169,7 +176,11 @@ struct StreamOccupancy {
 // instead of the record's cell-constant one; everything else -- the record cache, the walk, the prefetch -- is the same code.
 // Two kernels wrap it (below): step_kernel_stream, whose name and parameter list every profile and test of rounds 2-5 knows,
 // and step_kernel_stream_vertex, which appends the VertexField to the same parameter list (the kernarg offsets stay valid).
-template <bool BROWNIAN, bool REFLECT, bool STORE_VEL, bool STATS, int LOOKUP, bool VERTEX>
+// ZSET: the flat walk of a launch whose z is settled (StreamArgs::zSettled) as a body of its own, in which z does not exist --
+// the landing zone is x | y | cell, positions, end points, the hit point and the parked result are pairs, no z term is computed
+// (cpf_walk.h "settled z": the same bits in x, y and the cell as the three-coordinate body run with z = 0, which is what the
+// run-time flag made of such a launch).  A third kernel wraps it: step_kernel_stream_flat, step_kernel_stream's parameter list.
+template <bool BROWNIAN, bool REFLECT, bool STORE_VEL, bool STATS, int LOOKUP, bool VERTEX, bool ZSET = false>
 __device__ __forceinline__ void stream_body(
     const int64_t* __restrict__ gid, double* __restrict__ vel, int64_t n, double dt, double sigma, uint32_t step0,
     int nCyc, uint32_t seed, const MeshView& m, unsigned long long* __restrict__ counters, const StreamArgs& sa, const VertexField& vf) {
@@ -207,11 +218,12 @@ __device__ __forceinline__ void stream_body(
     constexpr bool kInRound = CPF_STREAM_INROUND == 2 || (CPF_STREAM_INROUND == 1 && BROWNIAN);
     static_assert(!(kInRound && (LOOKUP == 2 || LOOKUP == 3 || LOOKUP == 5 || LOOKUP == 11)), "in-round reflection knows neither face groups nor two-record cells");
     constexpr int kPool = HIT_IN_REGS ? 1 : ((LOOKUP == 2 || LOOKUP == 3 || LOOKUP == 5 || LOOKUP == 11) ? 16 : ((BROWNIAN && LOOKUP == 0) ? CPF_STREAM_HIT_POOL_B0 : CPF_STREAM_HIT_POOL));
-    __shared__ double sLane[3][64];
+    static_assert(!ZSET || ((LOOKUP == 8 || LOOKUP == 9) && !BROWNIAN && !VERTEX), "settled z: the flat walk without the kick or the vertex advect");
+    __shared__ double sLane[ZSET ? 2 : 3][64];
     __shared__ double sPool[3][kPool];
     __shared__ unsigned sPoolUsed;
     // landing zone of the next tile: x[64] | y[64] | z[64] | cell[64] (int32) | gid[64] (Brownian only)
-    __shared__ double sPre[BROWNIAN ? 288 : 224];
+    __shared__ double sPre[ZSET ? 160 : (BROWNIAN ? 288 : 224)];                // (ZSET: x[64] | y[64] | cell[64])
     // (VERTEX) the cone rows + 1/det of the 12 tets of up to kVertexBlocks cells: 80 bytes a tet, staged once per cycle and distinct cell of the wave
     __shared__ double sCone[VERTEX ? kVertexBlocks : 1][VERTEX ? kVertexTets * 10 : 1];
     double(*sE)[64] = sLane;
@@ -239,7 +251,17 @@ __device__ __forceinline__ void stream_body(
     constexpr bool FLAT = LOOKUP == 8 || LOOKUP == 9;
     // (FLAT) z of every live particle is a fixed point of the flat cycle: the launch leaves z in memory alone.  Wave-uniform;
     // the landing zone is then x[64] | y[64] | cell[64], and no z is loaded or stored (the z the walk carries in registers is dead)
-    const bool zKeep = FLAT && CPF_STREAM_FLAT_Z != 0 && sa.zSettled != 0;
+    // (ZSET: at compile time, and no test of it is left in the code)
+    const bool zKeep = ZSET || (FLAT && CPF_STREAM_FLAT_Z != 0 && sa.zSettled != 0);
+    // the lane's parked end point / parked result (sE): a pair without z
+    auto park = [&](const D3& e) __attribute__((always_inline)) {
+        sE[0][lane] = e.x; sE[1][lane] = e.y;
+        if (!ZSET) sE[2][lane] = e.z;
+    };
+    auto parked = [&]() __attribute__((always_inline)) -> D3 {
+        if (ZSET) return {sE[0][lane], sE[1][lane], 0.0};
+        return {sE[0][lane], sE[1][lane], sE[2][lane]};
+    };
     constexpr bool mixed = LOOKUP == 2 || LOOKUP == 3 || LOOKUP == 5 || LOOKUP == 11;
     constexpr bool bigCells = LOOKUP == 2;
     constexpr int kGatherAhead = LOOKUP == 4 ? 3 : 0;
@@ -384,6 +406,13 @@ __device__ __forceinline__ void stream_body(
             // particle is read off `cur` wherever it is needed (cur >= 0) instead of being kept in wave masks: scalar
             // registers are what this kernel is shortest of.
             if (ul > plim || pc < 0) pc = CPF_CELL_FROZEN;
+            // (flat walk that streams z) a live particle whose z is not finite: the launch says so, and the cloud's owner does not
+            // call it settled -- a wall would mirror such a particle to NaN in x and y, which a launch without z cannot do
+            // (cpf_walk.h "settled z").  Rare: the pointer is read from the kernarg segment where it is needed
+            if (FLAT && !ZSET && !zKeep && ballot64(pc >= 0 && !(fabs(pz) <= 1.7976931348623157e308)) != 0ull) {
+                unsigned* const bad = static_cast<unsigned*>(kernarg_pointer<kKernArgZBad>());
+                if (bad != nullptr && lane == 0) *bad = 1u;
+            }
 
             int cur = pc;
             // (meshes with two-record cells, LOOKUP 2) a lane between the two halves of a visit -- key2 != 0: the first record has
@@ -547,7 +576,7 @@ __device__ __forceinline__ void stream_body(
                 // the template parameter).  A round that finds every cell on chip (the common case) issues no memory request.
                 const unsigned long long busyMask = ballot64(busy);
                 // the lane's parked end point, requested before the lookup: its LDS round trip hides behind it (1 %)
-                const D3 Epre = {sE[0][lane], sE[1][lane], sE[2][lane]};
+                const D3 Epre = parked();
                 // what the lane looks up: its cell -- or, between the two halves of a visit of a two-record cell, the second record
                 const int lk = (bigCells && key2 != 0) ? key2 : cur;
                 int myslot = -1;
@@ -656,6 +685,12 @@ __device__ __forceinline__ void stream_body(
 #endif
                 if (nJobs != 0) {
                     // the requested records are older than everything the hook issued: wait for exactly them
+                    if (ZSET) {                          // three stores or none, the prefetch's two loads or none
+                        if (younger == 5) wait_vmcnt<5>();
+                        else if (younger == 3) wait_vmcnt<3>();
+                        else if (younger == 2) wait_vmcnt<2>();
+                        else wait_vmcnt<0>();
+                    } else
                     if (younger >= 7) wait_vmcnt<7>();
                     else if (younger == 6) wait_vmcnt<6>();
                     else if (younger == 5) wait_vmcnt<5>();                 // (settled z: three stores + the prefetch)
@@ -687,14 +722,15 @@ __device__ __forceinline__ void stream_body(
                         if (BOX) { const double2 uxy = reinterpret_cast<const double2*>(rec)[5]; u = {uxy.x, uxy.y, reinterpret_cast<const double*>(rec)[12], 0.0}; }
                         else u = rec[6];
                         v = {u.x, u.y, u.z};
-                        Pn = axpy(dt, v, S_);
+                        if (ZSET) Pn = {fma(dt, v.x, S_.x), fma(dt, v.y, S_.y), 0.0};
+                        else Pn = axpy(dt, v, S_);
                     }
-                    D3 disp = {Pn.x - S_.x, Pn.y - S_.y, Pn.z - S_.z};           // not yet walked in this cycle: S_ is the position
+                    D3 disp = {Pn.x - S_.x, Pn.y - S_.y, ZSET ? 0.0 : Pn.z - S_.z};           // not yet walked in this cycle: S_ is the position
                     if (BROWNIAN) {                                               // the deviates drawn in the cycle's first round
                         const D3 xi = {sE[0][lane], sE[1][lane], sE[2][lane]};
                         disp = axpy(CPF_STREAM_BROWN_KERNARG ? kernarg_f64<kKernArgSigma>() : sigma, xi, disp);
                     }
-                    D3 E = {S_.x + disp.x, S_.y + disp.y, S_.z + disp.z};
+                    D3 E = {S_.x + disp.x, S_.y + disp.y, ZSET ? 0.0 : S_.z + disp.z};
                     if (BROWNIAN && REFLECT && zFold) {                           // one cell thick in z: cpf_walk.h, fold_z
                         bool clear;
                         const int nb = fold_z(E.z, rec[BOX ? 0 : 4], rec[BOX ? 0 : 5], clear);      // (never with box records: zFold)
@@ -702,7 +738,7 @@ __device__ __forceinline__ void stream_body(
                         if (STATS) st.refl += nb;
                         if (STORE_VEL && (nb & 1)) v.z = -v.z;
                     }
-                    sE[0][lane] = E.x; sE[1][lane] = E.y; sE[2][lane] = E.z;
+                    park(E);
                     return E;
                 };
                 if (busy) {
@@ -782,7 +818,7 @@ __device__ __forceinline__ void stream_body(
                                 // E comes from its parking slot again -- it is there, from this round's advect or an earlier
                                 // round -- so that it need not stay in registers across the face tests
                                 asm volatile("" ::: "memory");
-                                E = {sE[0][lane], sE[1][lane], sE[2][lane]};
+                                E = parked();
                                 if (kInRound) {
                                     // reflect INSIDE the round (CPF_STREAM_INROUND; measured slower, docs/design_r04.md 5.5): mirror here and
                                     // walk on at once instead of in the next round
@@ -853,9 +889,12 @@ __device__ __forceinline__ void stream_body(
                             park_hit(S_);
                             if (STATS) ++st.refl;
                             const D3 nn = {wallPlane.x, wallPlane.y, wallPlane.z};
-                            const double sd = dot3(wallPlane, E) - wallPlane.w;
-                            E = axpy(-2.0 * sd, nn, E);
-                            sE[0][lane] = E.x; sE[1][lane] = E.y; sE[2][lane] = E.z;
+                            // (ZSET, cpf_walk.h "settled z": the z terms of sd and of the mirrored end point are +-0 * 0)
+                            const double sd = (ZSET ? fma(wallPlane.y, E.y, wallPlane.x * E.x) : dot3(wallPlane, E)) - wallPlane.w;
+                            if (ZSET) E = {fma(-2.0 * sd, nn.x, E.x), fma(-2.0 * sd, nn.y, E.y), 0.0};
+                            else E = axpy(-2.0 * sd, nn, E);
+                            park(E);
+                            // (ZSET: only a launch that stores velocities reads v, all three components, as ever)
                             v = axpy(-2.0 * dot3(wallPlane, v), nn, v);
                             h = 0;
                             ++j;                                                   // j == 5: still on a wall after 5 bounces, lost
@@ -882,14 +921,14 @@ __device__ __forceinline__ void stream_body(
             auto cycle_end = [&]() __attribute__((always_inline)) {
                 // ---- move (particles.cu:693-701); reflected: p = P_hit, disp = P_end - P_hit; else P + disp == E
                 if (cur >= 0) {                              // every lane that began the cycle with a particle
-                    const D3 E = {sE[0][lane], sE[1][lane], sE[2][lane]};
+                    const D3 E = parked();
                     if (REFLECT && j != 0) {                 // reflected at least once
                         D3 hit;
                         if (HIT_IN_REGS) hit = hitReg;
                         else if (hitAt < kPool) hit = {sPool[0][hitAt], sPool[1][hitAt], sPool[2][hitAt]};
                         else load3_sync(static_cast<const double*>(kernarg_pointer<kKernArgHitSpill>()) + (size_t)blockIdx.x * kStreamHitSpillDoubles,
                                         ul * 8u, hit.x, hit.y, hit.z);
-                        S_ = {hit.x + (E.x - hit.x), hit.y + (E.y - hit.y), hit.z + (E.z - hit.z)};
+                        S_ = {hit.x + (E.x - hit.x), hit.y + (E.y - hit.y), ZSET ? 0.0 : hit.z + (E.z - hit.z)};
                     } else S_ = E;
                     if (j >= kMaxReflect) { cur = CPF_CELL_LOST; if (STATS) ++st.lost; }
                 }
@@ -932,7 +971,7 @@ __device__ __forceinline__ void stream_body(
 #endif
                 }
             } else {
-                const D3 prev = {sE[0][lane], sE[1][lane], sE[2][lane]};
+                const D3 prev = parked();
                 (void)hook(prev);                            // zero cycles: loads + stores only (bandwidth calibration)
             }
 
@@ -949,7 +988,7 @@ __device__ __forceinline__ void stream_body(
             // x, y, z and the cell: a frozen or lost particle gets the bytes it was loaded with (and CPF_CELL_FROZEN),
             // which keeps the NUMBER of stores per tile fixed -- the counted wait above needs it
             rtile = tile; havePrev = true;
-            sE[0][lane] = S_.x; sE[1][lane] = S_.y; sE[2][lane] = S_.z;
+            park(S_);
             if (STORE_VEL) { rvx = v.x; rvy = v.y; rvz = v.z; ralive = pc >= 0; }
             rc = cur;
             rlim = plim;
@@ -961,10 +1000,10 @@ __device__ __forceinline__ void stream_body(
             const int64_t b = (int64_t)rtile * 64;
             const CloudPtrs cp = kernarg_cloud_ptrs();
             double* const x = cp.x; double* const y = cp.y; double* const z = cp.z; int32_t* const cell = cp.cell;
-            const double rx = sE[0][lane], ry = sE[1][lane], rz = sE[2][lane];
+            const D3 res = parked();
             if (ul <= rlim) {
-                (x + b)[ul] = rx; (y + b)[ul] = ry;
-                if (!zKeep) (z + b)[ul] = rz;
+                (x + b)[ul] = res.x; (y + b)[ul] = res.y;
+                if (!zKeep) (z + b)[ul] = res.z;
                 (cell + b)[ul] = rc;
             }
             if (STORE_VEL && ralive) {
@@ -1004,10 +1043,20 @@ __global__ __launch_bounds__(64, ((STORE_VEL || STATS) ? 1 : CPF_STREAM_WAVES_VE
     stream_body<BROWNIAN, REFLECT, STORE_VEL, STATS, LOOKUP, true>(gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa, vf);
 }
 
+// the flat walk on a cloud whose z is settled: the body without z (stream_body, ZSET).  step_kernel_stream's parameter list, so
+// that the kernarg offsets stay valid (z is passed and never read); LOOKUP 8 and 9 only
+template <bool REFLECT, bool STORE_VEL, bool STATS, int LOOKUP>
+__global__ __launch_bounds__(64, (StreamOccupancy<false, STORE_VEL, STATS, LOOKUP>::waves)) void step_kernel_stream_flat(
+    double* __restrict__ /* x */, double* __restrict__ /* y */, double* __restrict__ /* z */, int32_t* __restrict__ /* cell */,
+    const int64_t* __restrict__ gid, double* __restrict__ vel, int64_t n, double dt, double sigma, uint32_t step0,
+    int nCyc, uint32_t seed, MeshView m, unsigned long long* __restrict__ counters, StreamArgs sa) {
+    stream_body<false, REFLECT, STORE_VEL, STATS, LOOKUP, false, true>(gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa, VertexField{});
+}
+
 // ------------------------------------------------------------------------------------------------
 // launcher: persistent grid sized by the occupancy of the instantiation
 // ------------------------------------------------------------------------------------------------
-template <bool B, bool R_, bool SV, bool ST, int LF, bool VX = false>
+template <bool B, bool R_, bool SV, bool ST, int LF, bool VX = false, bool ZS = false>
 static hipError_t launch_stream_inst(hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid,
                                      double* vel, int64_t n, double dt, double sigma, uint32_t step0, int nCyc,
                                      uint32_t seed, const MeshView& m, unsigned long long* counters, StreamState& ss,
@@ -1017,9 +1066,11 @@ static hipError_t launch_stream_inst(hipStream_t st, double* x, double* y, doubl
         int nb = 0;
         hipError_t e;
         if constexpr (VX) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, step_kernel_stream_vertex<B, R_, SV, ST, LF>, 64, 0);
+        else if constexpr (ZS) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, step_kernel_stream_flat<R_, SV, ST, LF>, 64, 0);
         else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, step_kernel_stream<B, R_, SV, ST, LF>, 64, 0);
         if (e != hipSuccess) return e;
         wavesPerCU = nb < 1 ? 1 : (nb > 32 ? 32 : nb);
+        if (ZS && CPF_STREAM_WAVES_FLAT_BODY > 0 && wavesPerCU > 4 * CPF_STREAM_WAVES_FLAT_BODY) wavesPerCU = 4 * CPF_STREAM_WAVES_FLAT_BODY;
     }
     const int64_t nTiles = (n + 63) >> 6;
     if (nTiles >= ((int64_t)1 << 31)) return hipErrorInvalidValue;      // the kernel numbers tiles and chunks in 32 bits
@@ -1045,8 +1096,10 @@ static hipError_t launch_stream_inst(hipStream_t st, double* x, double* y, doubl
     if (R * kStreamGroups > ss.hitSpillWaves) R = ss.hitSpillWaves / kStreamGroups;      // (never: the area is sized for the chip)
     if (R < 1 || ss.d_hitSpill == nullptr) return hipErrorInvalidValue;
     // (the flat instantiations only: every other one streams z whatever the caller says; "flat_z" 0: they stream it too)
+    // (ZS: the caller has decided just that, StepPlan::flat_body)
     const bool zSettled = (LF == 8 || LF == 9) && !VX && settled && ss.flatZ != 0;
-    StreamArgs sa = {cur, nxt, (int)R, tpc, (unsigned)bigChunks, ss.debug, ss.d_hitSpill, zSettled ? 1 : 0};
+    if (ZS != zSettled && (LF == 8 || LF == 9) && !VX) return hipErrorInvalidValue;
+    StreamArgs sa = {cur, nxt, (int)R, tpc, (unsigned)bigChunks, ss.debug, ss.d_hitSpill, zSettled ? 1 : 0, ss.zBad};
     if constexpr (VX) {
         if (vf == nullptr) return hipErrorInvalidValue;
         if (evStart != nullptr && evStop != nullptr)
@@ -1055,6 +1108,14 @@ static hipError_t launch_stream_inst(hipStream_t st, double* x, double* y, doubl
         else
         hipLaunchKernelGGL((step_kernel_stream_vertex<B, R_, SV, ST, LF>), dim3((unsigned)(R * kStreamGroups)), dim3(64), 0, st, x, y, z, cell,
                            gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa, *vf);
+        return stream_launch_done(st, ss);
+    } else if constexpr (ZS) {
+        if (evStart != nullptr && evStop != nullptr)
+            hipExtLaunchKernelGGL((step_kernel_stream_flat<R_, SV, ST, LF>), dim3((unsigned)(R * kStreamGroups)), dim3(64), 0, st, evStart,
+                                  evStop, 0, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa);
+        else
+        hipLaunchKernelGGL((step_kernel_stream_flat<R_, SV, ST, LF>), dim3((unsigned)(R * kStreamGroups)), dim3(64), 0, st, x, y, z, cell,
+                           gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa);
         return stream_launch_done(st, ss);
     } else {
     if (evStart != nullptr && evStop != nullptr)
@@ -1151,7 +1212,7 @@ StepPlan plan_step(const MeshView& m, const StreamState& ss, int variant, const 
 }
 
 // the streaming kernels' instantiations: step_kernel_stream with every LOOKUP (the flat walk, 8 and 9, without the kick only),
-// step_kernel_stream_vertex with 0 and 1
+// step_kernel_stream_vertex with 0 and 1, step_kernel_stream_flat with 8 and 9
 template <int... L, class F>
 static hipError_t with_lookup(int lookup, F&& f) {
     hipError_t e = hipErrorInvalidValue;
@@ -1167,6 +1228,13 @@ hipError_t launch_step_stream(const StepPlan& p, hipStream_t st, double* x, doub
             return with_lookup<0, 1>(p.lookup, [&](auto LF) {
                 return launch_stream_inst<B, R, SV, ST, LF, true>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m,
                                                                   counters, ss, vf, zSettled, evStart, evStop);
+            });
+        // a settled cloud under the flat walk: the body without z
+        if (p.flat_body(ss, zSettled))
+            return with_lookup<8, 9>(p.lookup, [&](auto LF) {
+                if constexpr (B) return hipErrorInvalidValue;
+                else return launch_stream_inst<false, R, SV, ST, LF, false, true>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m,
+                                                                                  counters, ss, vf, zSettled, evStart, evStop);
             });
         return with_lookup<0, 1, 2, 3, 4, 5, 6, 8, 9, 11>(p.lookup, [&](auto LF) {
             if constexpr (B && (LF == 8 || LF == 9)) return hipErrorInvalidValue;

@@ -118,6 +118,8 @@ struct StreamArgs {
     double* hitSpill;      // kStreamHitSpillDoubles per workgroup: wall hit points beyond the wave's LDS pool
     int zSettled;          // (flat walk only) z of every live particle is already a fixed point of the flat cycle: z is neither
                            // loaded nor stored (cpf_walk.h "flat walk"; CPF_STEP_Z_SETTLED)
+    unsigned* zBad;        // (flat walk that streams z) set to 1 by a wave that loads a live particle whose z is not finite: such
+                           // a cloud is not called settled (cpf_walk.h "settled z"; StreamState::zBad, host memory the device writes)
 };
 
 // After a streaming launch: the launch zeroed the OTHER counter set for its successor, so the sets swap roles -- but only

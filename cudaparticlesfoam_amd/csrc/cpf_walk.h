@@ -335,7 +335,8 @@ __device__ __forceinline__ void face_test_flat(const double4& p, int bs, const D
 // SETTLED Z (CPF_STEP_Z_SETTLED, StreamArgs::zSettled).  What one flat cycle does to a live particle's z is a function f of z
 // alone: the advect gives Pn.z = z + dt * u.z with u.z == +-0 and dt finite (cpf_step_dev refuses any other), disp.z = Pn.z - z,
 // E.z = z + disp.z; the walk never moves S.z; a mirror about a side wall adds -2 sd * nz with nz == +-0 (a wall is only ever a
-// side face here, and sd is finite: a lane with a non-finite x or y never meets a face, dT = fd / den is then NaN or infinite);
+// side face here, and sd is finite for finite z -- see "not settled" below for the others: a lane with a non-finite x or y never
+// meets a face, dT = fd / den is then NaN or infinite);
 // the move gives E.z, or hit.z + (E.z - hit.z) with hit.z == z.  Case by case, in round-to-nearest:
 //   * z finite and non-zero: every zero added is exact and z + (+0) == z -- f(z) = z, the same bits;
 //   * z == +0: +0 + (+-0) == +0 -- f(+0) = +0;  z == -0: disp.z = (+-0) - (-0) = +0 and -0 + (+0) == +0 -- f(-0) = +0;
@@ -351,6 +352,29 @@ __device__ __forceinline__ void face_test_flat(const double4& p, int bs, const D
 // sort (a sort only permutes) -- a particle set or seeded anew, a frozen particle revived by cpf_locate_initial, hand-off
 // arrivals -- and any launch that is not the flat walk (the kick, a field with a z component, the vertex advect).  Only -0 and
 // +-inf are rewritten by the first cycle; NaN needs the idempotence above, finite non-zero z needs nothing.
+//
+// NOT SETTLED: A LIVE PARTICLE WHOSE Z IS NOT FINITE (round 8).  "sd is finite" above argues from x and y and holds for finite z
+// only.  The flat walk's face tests do not read z, so a live particle with z == NaN (+-inf is NaN after its first flat cycle)
+// does reach a wall, and the mirror's sd = dot3(plane, E) - w = fma(nz, NaN, ...) - w is NaN: the launch that streams z turns
+// its x and y into NaN, a launch that leaves z alone computes with z = 0 and reflects it.  x and y DO depend on z there.  So
+// a cloud that may hold such a particle is not called settled: the flat launch that streams z reports one (StreamArgs::zBad, a
+// pinned word the cloud's owner reads behind that launch, once, before the first launch that would leave z alone -- no pass
+// over the cloud), and flat launches keep streaming z for as long as one is reported.
+//
+// THE BODY WITHOUT Z (stream_body's ZSET, step_kernel_stream_flat: what a flat launch on a settled cloud runs).  The run-time flag
+// above ran the three-coordinate body with z = 0.0 in place of the z it did not load.  Every z term is then a product or a
+// sum of zeros, and dropping it gives the same bits in x, y and the cell, for every input:
+//   * advect, displacement, end point, move: z components only; x and y never read them;
+//   * the mirror: sd = dot3(plane, E) - w = fma(nz, E.z, t) - w with t = fma(ny, E.y, nx * E.x), nz == +-0, E.z == +-0.  The
+//     product is +-0 and t + (+-0) == t unless t is itself a zero, where only the sign of that zero can change; sd = t - w then
+//     differs at most in the sign of a zero result (w == 0), and so does the factor -2 sd.  E.x' = fma(-2 sd, nx, E.x) with
+//     E.x != 0 adds a zero product to a non-zero addend: the same bits.  E.z' = fma(-2 sd, nz, E.z) is a zero: not kept.
+//     (What is left: t == -0, w == 0 and an end point coordinate that is itself a zero -- an end point exactly at the origin, with
+//     x == -0, on a wall through the origin.  Only then could the sign of a stored zero differ.  No comparison reads it either.);
+//   * the velocity mirror, v' = v - 2 dot3(plane, v) n with v.z == +-0, nz == +-0: the same argument term by term; the
+//     body keeps all three components of v as they were (only a launch that stores velocities reads them at all);
+//   * no comparison of the walk reads a z or the sign of a zero (trace_lds4_flat above reads x and y only).
+// What is left in memory: z untouched, the bits a streaming launch would have written (the fixed-point argument above).
 template <bool ZERO_SKIP>
 __device__ __forceinline__ int trace_lds4_flat(D3& S, const D3& E, int cur, const double4* rec, int token, int& outSlot) {
     const D3 P0 = S;

@@ -67,7 +67,9 @@ typedef enum cpf_status {
                                      cell since.  Every live particle's z is then a fixed point of the flat cycle, so a launch
                                      that runs the flat walk neither loads nor stores z (40 instead of 56 bytes per particle);
                                      any other launch ignores the flag.  Results are the same bits with or without it when the
-                                     precondition holds (csrc/cpf_walk.h "flat walk") */
+                                     precondition holds (csrc/cpf_walk.h "flat walk").  The call that follows a flat launch which
+                                     streamed z waits for that launch once: if it met a live particle with a non-finite z, the
+                                     flag is ignored and z is streamed again */
 
 /* ---------------------------------------------------------------------------------------------
  * context
@@ -312,8 +314,10 @@ int cpf_set_seed(cpf_context* ctx, uint32_t seed);
  *                   laid out; after cpf_set_velocity_dev the note arrives asynchronously and the field counts as having one
  *                   until it has), D == 0, at least 8 particles per cell -- runs kernel 4's FLAT instantiations: four side faces with two-term dot products, no z faces, no z in the
  *                   walk.  0 = never.  Bit-identical either way (csrc/cpf_walk.h "flat walk", tests/test_gpu_parity.py)
- *   "flat_z"        (1) the flat walk on a cloud whose z is settled (CPF_STEP_Z_SETTLED) leaves z in memory alone; 0 = it
- *                   always loads and stores z (A/B).  Bit-identical either way
+ *   "flat_z"        (1) the flat walk on a cloud whose z is settled (CPF_STEP_Z_SETTLED) leaves z in memory alone -- it runs
+ *                   step_kernel_stream_flat, a kernel body without z; 0 = it always loads and stores z (A/B).  Bit-identical
+ *                   either way.  A cloud with a live particle whose z is NaN or infinite is never settled: the launch that
+ *                   streams z reports it, and the context / the shard keeps streaming z (a wall mirrors such a particle to NaN)
  *   "box_records"   (1) on a mesh whose cells are ALL axis-aligned boxes (cpf_mesh_box_records_host; 2:1-refined boxes with their
  *                   face groups included) kernel 4 walks 128-byte box
  *                   records -- three candidate faces per visit instead of six -- at every cloud density (measured faster than

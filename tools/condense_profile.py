@@ -32,7 +32,8 @@ for f in glob.glob(os.path.join(ROOT, "gpurun_out", label, "stats", "**", "*kern
     shutil.copy(f, os.path.join(P, label + "_kernel_stats.csv"))
 if "--bench" in sys.argv:
     # headline: no kick, reflecting walls, no stored velocity, statistics off, loop lookup -- with the flat walk (8) since round 4
-    mains = ("<false, true, false, false, 8>", "<false, true, false, false, 0>")
+    # (round 8: on a cloud with settled z -- every timed step -- the body without z, step_kernel_stream_flat)
+    mains = ("step_kernel_stream_flat<true, false, false, 8>", "<false, true, false, false, 8>", "<false, true, false, false, 0>")
     k = max((k for k in steps if any(m in k["kernel"] for m in mains)), key=lambda k: k["calls"])
     n = 10_000_000
     out = dict(label=label, kernel=k["kernel"], particles_per_launch=n,
