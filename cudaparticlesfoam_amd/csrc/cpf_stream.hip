@@ -163,6 +163,30 @@ constexpr int kKernArgStep0 = (int)offsetof(StreamKernArgs, step0), kKernArgSeed
 #ifndef CPF_STREAM_WAVES_FLAT_BODY
 #define CPF_STREAM_WAVES_FLAT_BODY 0
 #endif
+// the round of the body without z (step_kernel_stream_flat), each item an A/B knob (docs/experiments.md, round 9):
+// MASK: which lanes are busy is carried from round to round as a wave mask in scalar registers -- the round's vote on it and the
+// loop's were two trips through a vector register (v_cndmask 0/1 + v_cmp) per round, now one;
+// OUTCOME: "still busy" from plain mask operations instead of three nested exec regions;
+// GATHER: the per-lane gather walk (a round with 32 or more lanes without a record slot: a cloud that is not kept sorted) is the
+// flat walk on the global record -- four side faces, two coordinates -- instead of the six-face walk in three;
+// HINTS: ... and lies behind the round's hot path (branch weights);  ONE_HOOK: the zero-cycle launch runs the round's hook.
+// MASK and OUTCOME are where the time is (+2.5 % each); the other three take a sixth of the code out and nothing off the clock.
+// (Measured and dropped: a one-cell short cut in front of the loop lookup, -1.2 %.)
+#ifndef CPF_FLAT_ROUND_GATHER
+#define CPF_FLAT_ROUND_GATHER 1
+#endif
+#ifndef CPF_FLAT_ROUND_HINTS
+#define CPF_FLAT_ROUND_HINTS 1
+#endif
+#ifndef CPF_FLAT_ROUND_ONE_HOOK
+#define CPF_FLAT_ROUND_ONE_HOOK 1
+#endif
+#ifndef CPF_FLAT_ROUND_MASK
+#define CPF_FLAT_ROUND_MASK 1
+#endif
+#ifndef CPF_FLAT_ROUND_OUTCOME
+#define CPF_FLAT_ROUND_OUTCOME 1
+#endif
 template <bool BROWNIAN, bool STORE_VEL, bool STATS, int LOOKUP>
 // LOOKUP 2 / 3 (mixed records): one wave less; LOOKUP 4 (sparse clouds: pipelined per-lane gathers, 24 more registers): 5
 struct StreamOccupancy {
@@ -249,6 +273,9 @@ __device__ __forceinline__ void stream_body(
     constexpr bool LOOKUP_FIXED = LOOKUP != 0 && LOOKUP != 5 && LOOKUP != 8;
     //   9 = as 1 with the flat walk (a 2-D mesh with fewer than 128 particles per cell: refined 2-D cases)
     constexpr bool FLAT = LOOKUP == 8 || LOOKUP == 9;
+    constexpr bool kMaskBusy = ZSET && CPF_FLAT_ROUND_MASK != 0, kPlainOutcome = ZSET && CPF_FLAT_ROUND_OUTCOME != 0;
+    constexpr bool kFlatGather = ZSET && CPF_FLAT_ROUND_GATHER != 0, kHints = ZSET && CPF_FLAT_ROUND_HINTS != 0;
+    constexpr bool kOneHook = ZSET && CPF_FLAT_ROUND_ONE_HOOK != 0;
     // (FLAT) z of every live particle is a fixed point of the flat cycle: the launch leaves z in memory alone.  Wave-uniform;
     // the landing zone is then x[64] | y[64] | cell[64], and no z is loaded or stored (the z the walk carries in registers is dead)
     // (ZSET: at compile time, and no test of it is left in the code)
@@ -475,6 +502,7 @@ __device__ __forceinline__ void stream_body(
             // crossed or hit in this cycle), it has been reflected iff j != 0, and it is lost in this cycle iff
             // j >= kMaxReflect (still on a wall after 5 bounces; a wall without reflection sets j = kMaxReflect too).
             bool busy = false;
+            unsigned long long busyM = 0ull;         // (kMaskBusy) the busy lanes as a wave mask, from one round to the next
             bool zUnclear = false;                   // (kick on a one-cell-thick mesh) some lane's mirrored end point is not clear of the z planes
             int token = INT32_MIN, h = 0, j = 0;
             int hitAt = -1;                          // pool: where this lane's hit point is parked (< kPool: pool entry)
@@ -493,6 +521,7 @@ __device__ __forceinline__ void stream_body(
             auto cycle_begin = [&](int c) __attribute__((always_inline)) {
                 if (cur < 0) cur = CPF_CELL_FROZEN;                                  // lost in the previous cycle: w = 0
                 busy = cur >= 0;
+                if (kMaskBusy) busyM = ballot64(cur >= 0);
                 token = INT32_MIN; h = 0; j = 0;
                 if (bigCells) key2 = 0;
                 if (!HIT_IN_REGS && REFLECT) { hitAt = -1; if (lane == 0) sPoolUsed = 0u; }
@@ -574,7 +603,8 @@ __device__ __forceinline__ void stream_body(
                 // are what that case is short of (measured: the fixed sequence costs pitzDaily 1.5-3 %, and saves the
                 // large meshes 4-7 %; both in ONE kernel behind a run-time flag: the worse of the two everywhere, hence
                 // the template parameter).  A round that finds every cell on chip (the common case) issues no memory request.
-                const unsigned long long busyMask = ballot64(busy);
+                const unsigned long long busyMask = kMaskBusy ? busyM : ballot64(busy);
+                if (kMaskBusy) busy = __builtin_amdgcn_inverse_ballot_w64(busyM);
                 // the lane's parked end point, requested before the lookup: its LDS round trip hides behind it (1 %)
                 const D3 Epre = parked();
                 // what the lane looks up: its cell -- or, between the two halves of a visit of a two-record cell, the second record
@@ -751,7 +781,8 @@ __device__ __forceinline__ void stream_body(
                     // lane walks the cell's CSR slots per lane from global memory, in the gather branch below
                     bool hdrCell = false;
                     if (bigCells && myslot >= 0) hdrCell = *reinterpret_cast<const int*>(&slots[0][0] + myslot * kSlotStride + 7) == kBigCellMark;
-                    if (myslot >= 0 && !(bigCells && hdrCell)) {
+                    // (the body without z: the lane has its record on chip -- the per-lane gather walk lies behind the round's hot path)
+                    if ((kHints && __builtin_expect(myslot >= 0, 1)) || (!kHints && myslot >= 0 && !(bigCells && hdrCell))) {
                         const double4* rec = &slots[0][0] + myslot * kStride;
                         if (needAdvect) E = advect(rec);
                         // ---- the visit, and -- in the same round -- the visits after a wall.  A wall hit never changes the
@@ -840,7 +871,7 @@ __device__ __forceinline__ void stream_body(
                         // no slot: more distinct new cells in the wave than the round can place (a cloud that is not
                         // kept sorted).  Per-lane gathers keep such a wave moving.
                         next = kSitOut;
-                        if (gatherRound || (bigCells && hdrCell)) {
+                        if ((kHints && __builtin_expect(gatherRound, 0)) || (!kHints && (gatherRound || (bigCells && hdrCell)))) {
                             const double4* rec = BOX ? m.boxRec + 4 * (int64_t)cur : m.cellRec + 8 * (int64_t)cur;
                             if (needAdvect) E = advect(rec);
                             int gS0 = 0;
@@ -859,6 +890,9 @@ __device__ __forceinline__ void stream_body(
                                 }
                             }
                             if (BOX) next = trace_box<false, mixed>(S_, E, cur, rec, token, outSlot);
+                            // (the body without z) the flat walk on the global record: four side faces, two coordinates, the face
+                            // test of the LDS visit.  Same bits as the six-face walk with z = 0 (cpf_walk.h "the body without z")
+                            else if (kFlatGather) next = trace_lds4_flat<false>(S_, E, cur, rec, token, outSlot);
                             else if (!gBig)
                             next = trace_fixed<6, false, mixed, kGatherAhead>(S_, E, cur, rec, reinterpret_cast<const int32_t*>(rec + 7), token, outSlot, 0);
                             if (STATS) ++st.hops;
@@ -903,8 +937,11 @@ __device__ __forceinline__ void stream_body(
                     token = cross ? cur : (wall ? next : token);                   // (a wall's code as token: the advect is done)
                     cur = cross ? next : cur;
                     h += cross ? 1 : 0;
+                    if (kPlainOutcome) busy = !(ends | (cross & (h == kMaxHops)) | (wall & (j >= kMaxReflect)));
+                    else
                     busy = !(ends || (cross && h == kMaxHops) || (wall && j >= kMaxReflect));   // hop cap: keep the last cell
                 }
+                if (kMaskBusy) busyM = ballot64(busy);
 #ifdef CPF_STREAM_TIMELINE
                 {
                     const unsigned nb = (unsigned)__popcll(busyMask), ns = (unsigned)__popcll(ballot64(tlSat));
@@ -934,13 +971,20 @@ __device__ __forceinline__ void stream_body(
                 }
             };
 
-            if (nCyc > 0) {
+            // (the body without z: a zero-cycle launch runs ONE round with no busy lane and neither a cycle's begin nor its move --
+            // the round's own hook stores what was loaded -- so that the kernel holds one instance of the hook)
+            const int nRun = (kOneHook && nCyc <= 0) ? 1 : nCyc;
+            if (kOneHook || nCyc > 0) {
                 // ONE instance of the round in the kernel's code: the tile's first round carries the hook behind a
                 // wave-uniform flag (three inlined copies -- hook round, other rounds of the first cycle, rounds of the later
                 // cycles of a fused launch -- were 3 x 1400 instructions and a dozen register shuffles at every loop edge).
                 // A cycle's first round always runs, even with no busy lane (cycle 0's carries the hook).
-                for (int c = 0; c < nCyc; ++c) {
-                    cycle_begin(c);
+                for (int c = 0; c < nRun; ++c) {
+                    // (read per cycle through an opaque copy: a test of nCyc itself is invariant in this loop, and hipcc then
+                    // makes two copies of the loop, round and all, one per outcome)
+                    int live = nCyc;
+                    if (kOneHook) asm volatile("" : "+s"(live));
+                    if (live > 0) cycle_begin(c);
 #ifdef CPF_STREAM_TIMELINE
                     tlVis = 0; tlRoundIdx = 0;
 #endif
@@ -955,6 +999,12 @@ __device__ __forceinline__ void stream_body(
                     const D3 capKeep = S_;
                     const int capCur = cur;
 #else
+                    // (the body without z: its round is small enough for hipcc to peel the loop's first trip -- the hook round -- into
+                    // a second copy of the round, which the comment above is about)
+                    if constexpr (ZSET) {
+                        _Pragma("clang loop unroll(disable)")
+                        do { round(hookDue, cycleStart, c); hookDue = false; cycleStart = false; } while (kMaskBusy ? busyM != 0ull : ballot64(busy) != 0ull);
+                    } else
                     do { round(hookDue, cycleStart, c); hookDue = false; cycleStart = false; } while (ballot64(busy) != 0ull);
 #endif
 #ifdef CPF_STREAM_TIMELINE
@@ -965,7 +1015,7 @@ __device__ __forceinline__ void stream_body(
                         if (tlH != nullptr && lane == 0) atomicAdd(&tlH[16 * 65 + 16 + r * 16u + iv], 1ull);
                     }
 #endif
-                    cycle_end();
+                    if (live > 0) cycle_end();
 #ifdef CPF_STREAM_CAP_TEST
                     if (capDropped) { S_ = capKeep; cur = capCur; }       // stops where its last crossing left it (a consistent state)
 #endif

@@ -9,6 +9,8 @@
 # kernel calls, average duration, HBM bytes per launch with the gfx950 corrections of profiles/r03_pmc_hbm.json: FETCH_SIZE KB x
 # 1024 x 1.9975, WRITE_SIZE KB x 1024 x 0.9934, calibrated on the zero-cycle launch: tools/calib.py), SQ counters per launch
 # and per 64-particle tile: gpurun_out/LABEL_sq.txt.  Copy what is to be judged into profiles/.
+# (round 9: --sq runs FIVE passes; the fifth set holds SQ_INST_CYCLES_SALU -- issue slots of the scalar pipe -- SQ_WAIT_INST_ANY / _LDS and
+# SQ_IFETCH beside SQ_WAVE_CYCLES)
 set -u
 cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
@@ -29,6 +31,7 @@ if [ $SQ = 1 ]; then
    "SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_SCA SQ_INSTS_BRANCH SQ_INSTS_LDS SQ_ACTIVE_INST_LDS"
    "SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INST_LEVEL_LDS SQ_INST_LEVEL_VMEM SQ_IFETCH SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_FLAT SQ_INSTS_FLAT"
    "GRBM_GUI_ACTIVE GRBM_COUNT"
+   "SQ_INST_CYCLES_SALU SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_IFETCH SQ_WAVE_CYCLES SQ_BUSY_CYCLES"
   )
   k=0
   for S in "${SETS[@]}"; do run "sq$k" --kernel-trace --pmc $S; k=$((k+1)); done

@@ -10,24 +10,35 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CS = os.path.join(ROOT, "cudaparticlesfoam_amd", "csrc")
 
 
+def hipcc_cmd(src):
+    """The product's compile of one csrc file (csrc/Makefile's flags), without its output option."""
+    extra = ["-mllvm", "--amdgpu-sched-strategy=max-ilp"] if src == "cpf_stream.hip" else []      # as in csrc/Makefile
+    return (["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-O3", "-fPIC", "-ffp-contract=off"] + extra +
+            ["-I" + os.path.join(ROOT, "include"), "-I" + CS, os.path.join(CS, src), "-Rpass-analysis=kernel-resource-usage"])
+
+
+def parse(remarks):
+    """Rows (name, VGPRs, AGPRs, SGPRs, scratch, waves, SGPR spills, VGPR spills, LDS) from the compiler's remarks (stderr)."""
+    rows = []
+    txt = re.sub(r" \[-Rpass-analysis=kernel-resource-usage\]", "", remarks)
+    for b in re.split(r"(?=remark: [^\n]*Function Name:)", txt):
+        m = re.search(r"Function Name:\s*(\S+)", b)
+        if not m:
+            continue
+        name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip().split("(")[0]
+        if "step_kernel" not in name:
+            continue
+        g = lambda k: (re.search(k + r":\s*(\S+)", b) or [None, "?"])[1]   # noqa: E731
+        rows.append((name, g("VGPRs"), g("AGPRs"), g("TotalSGPRs"), g(r"ScratchSize \[bytes/lane\]"),
+                     g(r"Occupancy \[waves/SIMD\]"), g("SGPRs Spill"), g("VGPRs Spill"), g(r"LDS Size \[bytes/block\]")))
+    return rows
+
+
 def collect():
     rows = []
     for src in ("cpf_stream.hip", "cpf_kernels.hip"):
-        extra = ["-mllvm", "--amdgpu-sched-strategy=max-ilp"] if src == "cpf_stream.hip" else []      # as in csrc/Makefile
-        r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-O3", "-fPIC", "-ffp-contract=off"] + extra +
-                           ["-I" + os.path.join(ROOT, "include"), "-I" + CS, "-c", os.path.join(CS, src), "-o", "/dev/null",
-                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-        txt = re.sub(r" \[-Rpass-analysis=kernel-resource-usage\]", "", r.stderr)
-        for b in re.split(r"(?=remark: [^\n]*Function Name:)", txt):
-            m = re.search(r"Function Name:\s*(\S+)", b)
-            if not m:
-                continue
-            name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip().split("(")[0]
-            if "step_kernel" not in name:
-                continue
-            g = lambda k: (re.search(k + r":\s*(\S+)", b) or [None, "?"])[1]   # noqa: E731
-            rows.append((name, g("VGPRs"), g("AGPRs"), g("TotalSGPRs"), g(r"ScratchSize \[bytes/lane\]"),
-                         g(r"Occupancy \[waves/SIMD\]"), g("SGPRs Spill"), g("VGPRs Spill"), g(r"LDS Size \[bytes/block\]")))
+        r = subprocess.run(hipcc_cmd(src) + ["-c", "-o", "/dev/null"], capture_output=True, text=True)
+        rows += parse(r.stderr)
     return rows
 
 

@@ -24,6 +24,8 @@ def main():
     ap.add_argument("--mesh3d", action="store_true", help="the 245 760-cell 3-D mesh (tools/_cases.py: box3d), swirl field")
     ap.add_argument("--tjunction", action="store_true", help="the reference's TJunction tutorial mesh (248 000 cells), split flow u0 = 3")
     ap.add_argument("--case", default=None, help="tools/_cases.py: pitz | box3d | tjunction | octagons | pentagons | dodecagons | hexgrid")
+    ap.add_argument("--settled", action="store_true", help="the launches after the first carry CPF_STEP_Z_SETTLED: on a 2-D case the "
+                    "measured launch is then the flat walk's body without z (step_kernel_stream_flat)")
     ap.add_argument("--census", action="store_true", help="busy lanes per round index, sit-outs, rounds against the largest visit count of a tile")
     args = ap.parse_args()
     import torch
@@ -45,14 +47,17 @@ def main():
     NCEN = 16 * 65 + 16 + 256 + 16
     tl = torch.zeros(8 * 16384 + NCEN, dtype=torch.int64, device=dev)
     p = lambda t: t.data_ptr()   # noqa: E731
-    for _ in range(args.pre_steps):
-        ctx.step_dev(p(x), p(y), p(z), p(c), p(g) if args.D > 0 else None, None, n, dt, args.D, 0, 1, 0)
+    from cudaparticlesfoam_amd import _lib as L
+    for k in range(args.pre_steps):
+        ctx.step_dev(p(x), p(y), p(z), p(c), p(g) if args.D > 0 else None, None, n, dt, args.D, 0, 1,
+                     L.STEP_Z_SETTLED if (args.settled and k > 0) else 0)
+    settled = L.STEP_Z_SETTLED if (args.settled and args.pre_steps > 0) else 0
     torch.cuda.synchronize()
     tl.zero_()
     if args.census:
         ctx.set_option("stream_debug", 4)        # the census' global atomics distort the timeline: only on request
     ctx.timing_enable(True)
-    ctx.step_dev(p(x), p(y), p(z), p(c), p(g) if args.D > 0 else None, p(tl), n, dt, args.D, 5, 1, 0)
+    ctx.step_dev(p(x), p(y), p(z), p(c), p(g) if args.D > 0 else None, p(tl), n, dt, args.D, 5, 1, settled)
     launches, ms = ctx.timing_read()
     raw_all = tl.cpu().numpy()
     raw, cen = raw_all[:8 * 16384], raw_all[8 * 16384:].astype(np.float64)
@@ -66,7 +71,7 @@ def main():
     start = (t0 - base) * 10.0 / 1e3          # us (100 MHz ticks)
     end = (t1 - base) * 10.0 / 1e3
     q = lambda a: [round(float(v), 2) for v in np.percentile(a, [0, 5, 25, 50, 75, 95, 100])]   # noqa: E731
-    out = dict(label=args.label, opts=args.opt, kernel_ms=round(ms / launches, 4), waves=int(t.shape[0]),
+    out = dict(label=args.label, opts=args.opt, settled=bool(settled), kernel_ms=round(ms / launches, 4), waves=int(t.shape[0]),
                start_us_pct=q(start), end_us_pct=q(end), life_us_pct=q(end - start),
                tiles_pct=q(t[:, 2]), rounds_per_tile=round(float(t[:, 3].sum() / max(1, t[:, 2].sum())), 3),
                us_per_tile_pct=q((end - start) / np.maximum(t[:, 2], 1)),
