@@ -1187,7 +1187,7 @@ int cpf_set_option(cpf_context* ctx, const char* key, double value) {
     }
     if (k == "stream_lookup") {
         // (2, 3, 5 on an all-hex mesh: diagnostics -- what the mixed-mesh instantiations cost by themselves; same results)
-        CPF_REQUIRE(ctx, value == -1 || (value >= 0 && value <= 6 && value == (int)value), CPF_ERR_ARG, "stream_lookup must be -1 (auto) or 0 ... 6");  // (8: chosen by the library, "flat_walk")
+        CPF_REQUIRE(ctx, value == -1 || (value >= cpf::kLookupLoop && value <= cpf::kLookupBox && value == (int)value), CPF_ERR_ARG, "stream_lookup must be -1 (auto) or 0 ... 6");  // (8: chosen by the library, "flat_walk")
         ctx->streamState.lookup = (int)value;
         return CPF_OK;
     }

@@ -4,6 +4,7 @@
 
 #include <cstdint>
 #include <type_traits>
+#include <utility>
 
 #include "cpf.h"
 #include "cpf_internal.h"   // kGroupBase
@@ -51,7 +52,7 @@ struct StreamState {
     int tilesPerChunk = 0;    // "stream_tiles_per_chunk"; 0 = by lookup method: 4 (loop lookup), 3 (fixed lookup: slower tiles, finer dealing)
     int wavesPerCU = 0;       // "stream_waves_per_cu": 0 = what the occupancy query says
     int coopMaxCells = 0;     // "coop_max_cells": test hook, lowers the wave-cooperative kernel's 2^24-cell limit (0 = the limit)
-    int lookup = -1;          // "stream_lookup": 0 loop over distinct cells, 1 fixed tag compare, -1 = by particles per cell
+    int lookup = -1;          // "stream_lookup": a mode of kLookupModes (below), 0 ... 6; -1 = by particles per cell
     double tailFraction = -1.0; // "stream_tail_fraction": share of the cloud dealt tile by tile at the end of a launch; < 0 = by lookup method: 0.1 / 0.2
     int debug = 0;            // "stream_debug": diagnostics only (1 = no stores, 2 = no loads; results are wrong)
     // What the last sort found: [0] cells that hold particles, [1] live particles (pinned host memory, written by an async copy
@@ -80,6 +81,87 @@ constexpr int kFusedCoopCycles = 1 << 30;  // fused launches of this many cycles
                                           // the flat walk and box records it is 5-30 % faster at 8 and 16 -- cpf_stream.hip, plan_step)
 struct VertexField;                  // cpf_walk.h
 
+// ------------------------------------------------------------------------------------------------
+// The streaming kernels' LOOKUP (cpf_stream.hip: the last template argument of step_kernel_stream, _vertex and _flat; StepPlan::lookup):
+// how a wave finds its cells in its record cache, and which records can turn up.  THE legend of the modes and the one place that
+// says what a number means -- the planner, the launcher, the option check and the kernel all read kLookupModes; what a mode costs in
+// record slots, waves per SIMD and hit pool is StreamShape (cpf_stream.hip), what it measured docs/design_r04.md 5.1.  The values
+// are part of every kernel's name (profiles, tests, tools/condense_profile.py know them): a new mode takes a new number.
+//   0  kLookupLoop       all-hex mesh, many particles per cell (>= 128: 1-3 distinct cells per round): one scalar iteration per
+//                        DISTINCT cell of the wave, a compare against the scalar cell id
+//   1  kLookupFixed      all-hex mesh, few particles per cell (3-D meshes: 5-13 distinct cells per tile): six compares of every
+//                        lane's cell against the broadcast tags
+//   2  kLookupMixedBig   as 3, and header records of cells with more than six slots may turn up as well (two-record cells: a visit
+//                        in two rounds; beyond twelve slots the CSR walk) -- MeshView::mixed == 2
+//   3  kLookupMixed      fixed compare on a mesh that is not all-hex (MeshView::mixed) whose cells all have at most six slots: face
+//                        groups and padded records only, the usual 2:1-refined hex mesh
+//   4  kLookupSparse     fixed compare for SPARSE clouds on all-hex meshes (fewer than kStreamSparsePerCell particles per cell: nearly
+//                        every lane of a tile sits in a cell of its own and walks by per-lane gathers from L2 / HBM): the gather walk
+//                        keeps three planes in flight instead of one -- two dependent round trips per visit instead of six -- for 24
+//                        more registers, i.e. five waves per SIMD.  2.1e6-cell box: 1.25e6 particles (one rank's share of BASELINE
+//                        configs[4]) 0.187 -> 0.141 ms, 1e7 particles 0.673 / 0.631 -> 0.641 / 0.607; in the dense regime the same
+//                        change costs 6 % (0.259 -> 0.277)
+//   5  kLookupMixedLoop  as 3 with the LOOP lookup and six slots: a refined mesh that still holds hundreds of particles per cell
+//                        (pitzDaily with a 2:1 patch: 0.157 -> see docs/design_r04.md 5.6)
+//   6  kLookupBox        as 1 on the mesh's 128-byte BOX records instead of the 256-byte ones (every cell an axis-aligned box:
+//                        cpf_walk.h "box records") -- dense and sparse clouds alike: three candidate faces per visit, one LDS round
+//                        trip per record, one cache line per gathered record
+//   8  kLookupFlatLoop   as 0 with the FLAT walk (cpf_walk.h): a 2-D mesh extruded straight in z, a field without a z component, no
+//                        kick -- the headline; behind it every live particle's z is settled (StepPlan::flat)
+//   9  kLookupFlatFixed  as 1 with the flat walk (a 2-D mesh with fewer than 128 particles per cell: refined 2-D cases)
+//   11 kLookupBoxGroups  as 6 on a mesh with face groups: 2:1-refined boxes (box records with group slots)
+// "stream_lookup" (StreamState::lookup) may ask for 0 ... 6; 8, 9 and 11 are the planner's own (stream_lookup_mode).
+enum : int { kLookupLoop = 0, kLookupFixed = 1, kLookupMixedBig = 2, kLookupMixed = 3, kLookupSparse = 4, kLookupMixedLoop = 5,
+             kLookupBox = 6, kLookupFlatLoop = 8, kLookupFlatFixed = 9, kLookupBoxGroups = 11 };
+struct LookupMode {
+    int id;
+    bool fixed;        // compare every lane's cell against the tags (else: loop over the wave's distinct cells)
+    bool mixed;        // mixed records: face groups and padded records can turn up
+    bool bigCells;     // ... and two-record cells and header records
+    bool box;          // 128-byte box records
+    bool flat;         // the flat walk
+    int gatherAhead;   // planes the per-lane gather walk keeps in flight beyond the one it tests (0: the plain gather walk)
+};
+constexpr LookupMode kLookupModes[] = {
+    // id               fixed  mixed  big    box    flat   ahead
+    {kLookupLoop,       false, false, false, false, false, 0},
+    {kLookupFixed,      true,  false, false, false, false, 0},
+    {kLookupMixedBig,   true,  true,  true,  false, false, 0},
+    {kLookupMixed,      true,  true,  false, false, false, 0},
+    {kLookupSparse,     true,  false, false, false, false, 3},
+    {kLookupMixedLoop,  false, true,  false, false, false, 0},
+    {kLookupBox,        true,  false, false, true,  false, 0},
+    {kLookupFlatLoop,   false, false, false, false, true,  0},
+    {kLookupFlatFixed,  true,  false, false, false, true,  0},
+    {kLookupBoxGroups,  true,  true,  false, true,  false, 0},
+};
+constexpr int kLookupModeCount = (int)(sizeof(kLookupModes) / sizeof(kLookupModes[0]));
+// the table's row of a mode; id -1: no such mode
+constexpr LookupMode lookup_traits(int lookup) {
+    for (const LookupMode& r : kLookupModes)
+        if (r.id == lookup) return r;
+    return {-1, false, false, false, false, false, 0};
+}
+// the table pinned to the numbers every profile and test knows: the modes that have a property, as a bit set of their values
+constexpr unsigned lookup_set(bool LookupMode::*property) {
+    unsigned s = 0;
+    for (const LookupMode& r : kLookupModes)
+        if (r.*property) s |= 1u << r.id;
+    return s;
+}
+constexpr unsigned lookup_bits() { return 0u; }
+template <class... T>
+constexpr unsigned lookup_bits(int id, T... more) { return (1u << id) | lookup_bits(more...); }
+static_assert(kLookupModeCount == 10 && lookup_traits(7).id == -1 && lookup_traits(10).id == -1, "ten modes: 0 ... 6, 8, 9, 11");
+static_assert(lookup_set(&LookupMode::fixed) == lookup_bits(1, 2, 3, 4, 6, 9, 11), "loop lookup: 0, 5, 8");
+static_assert(lookup_set(&LookupMode::mixed) == lookup_bits(2, 3, 5, 11), "mixed records");
+static_assert(lookup_set(&LookupMode::bigCells) == lookup_bits(2), "two-record cells");
+static_assert(lookup_set(&LookupMode::box) == lookup_bits(6, 11), "box records");
+static_assert(lookup_set(&LookupMode::flat) == lookup_bits(8, 9), "flat walk");
+static_assert(lookup_traits(4).gatherAhead == 3 && lookup_traits(0).gatherAhead + lookup_traits(1).gatherAhead +
+              lookup_traits(2).gatherAhead + lookup_traits(3).gatherAhead + lookup_traits(5).gatherAhead + lookup_traits(6).gatherAhead +
+              lookup_traits(8).gatherAhead + lookup_traits(9).gatherAhead + lookup_traits(11).gatherAhead == 0, "gather ahead: 4 only");
+
 // What one step launch runs: plan_step (cpf_stream.hip) decides, launch_step runs it, cpf_step_dev times it and learns from
 // it whether the launch settles z, cpf_step_kernel_name prints it.
 struct StepPlan {
@@ -88,16 +170,14 @@ struct StepPlan {
     enum Kernel { kGeneric = 0, kFixed = 1, kFixedScalar = 2, kCoop = 3, kStream = 4, kAhead = 5, kVertex, kStreamVertex };
     Kernel kernel = kGeneric;
     bool brown = false, reflect = false, storeVel = false, stats = false;   // the template flags
-    // the streaming kernels' LOOKUP: 0 loop, 1 fixed compare, 4 fixed compare for sparse clouds, 2 / 3 fixed compare + mixed records
-    // with / without header records, 5 loop + mixed records, 6 fixed compare + box records, 11 box records + face groups, 8 / 9 flat walk
-    int lookup = -1;
+    int lookup = -1;      // the streaming kernels' LOOKUP: a mode of kLookupModes (above)
     bool cone = false;    // the vertex kernels: cone locate (else all tets)
     // timed, the streaming kernels take the events to hipExtLaunchKernelGGL -- start and stop are then the dispatch's own begin
     // / end time stamps, what rocprofv3's kernel trace reports, instead of events recorded around the launch (which also time
     // the gap an event record puts between two otherwise back-to-back kernels: 5 % on a 0.12 ms kernel)
     bool stamped() const { return kernel == kStream || kernel == kStreamVertex; }
     // the flat walk: every live particle's z is settled behind it (CPF_STEP_Z_SETTLED)
-    bool flat() const { return kernel == kStream && (lookup == 8 || lookup == 9); }
+    bool flat() const { return kernel == kStream && lookup_traits(lookup).flat; }
     // ... on a cloud whose z is settled: step_kernel_stream_flat, the body in which z does not exist ("flat_z" 0: never)
     bool flat_body(const StreamState& ss, bool zSettled) const { return flat() && zSettled && ss.flatZ != 0; }
 };
@@ -125,6 +205,17 @@ decltype(auto) with_bools(F&& f, bool b, Bs... bs) {
     if (b) return with_bools([&](auto... c) -> decltype(auto) { return f(std::true_type{}, c...); }, bs...);
     return with_bools([&](auto... c) -> decltype(auto) { return f(std::false_type{}, c...); }, bs...);
 }
+
+// f(std::integral_constant<int, id>{}) for the mode `lookup` of kLookupModes (none: hipErrorInvalidValue): a launcher's LOOKUP as a
+// template argument, one instantiation per mode of the table -- f itself refuses, with `if constexpr`, the modes it has no kernel for
+template <class F, size_t... I>
+hipError_t with_lookup(int lookup, F&& f, std::index_sequence<I...>) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((lookup == kLookupModes[I].id && ((e = f(std::integral_constant<int, kLookupModes[I].id>{})), true)) || ...);
+    return e;
+}
+template <class F>
+hipError_t with_lookup(int lookup, F&& f) { return with_lookup(lookup, f, std::make_index_sequence<kLookupModeCount>{}); }
 
 hipError_t launch_locate_initial(hipStream_t st, const double* x, const double* y, const double* z, int32_t* cell,
                                  int64_t n, const MeshView& m, const GridView& g);

@@ -1,6 +1,6 @@
 // Streaming step kernel (gfx950 / CDNA4, wave64): all-hex meshes, and meshes with a minority of other cells (mixed cell
-// records: padded, face groups, header records -- the LOOKUP 2 / 3 / 5 instantiations; docs/design_r04.md 5.1 has the table; LOOKUP 6:
-// box records, 8 / 9: the flat walk of 2-D cases).
+// records: padded, face groups, header records; box records; the flat walk of 2-D cases -- the LOOKUP instantiations, whose legend
+// and properties are kLookupModes in cpf_device.h).
 //
 // Same fused cycle and the same per-particle arithmetic as step_kernel_coop (cpf_kernels.hip) -- advect -> Brownian
 // kick -> plane-exit walk -> wall reflect -> move, src/advect.H:96-161 -- organised around what the measurements of
@@ -51,10 +51,7 @@ namespace cpf {
 // fewer lanes sit a round out for want of a slot.  Measured on one box, 6 / 4 -> 9 / 8: 3-D bench box 0.2759 -> 0.2663 ms,
 // TJunction 0.1595 / 0.1757 -> 0.1557 / 0.1683, 2.1e6-cell box with 5 particles per cell 0.738 -> 0.682 (12 slots: a wave
 // per SIMD less, 0.267 / 0.692); pitzDaily with 9 / 8 LOSES 5 % (0.1190 -> 0.1250), hence per lookup method.
-constexpr int kStreamSlots = CPF_STREAM_SLOTS;
-constexpr int kStreamSlotsFixed = CPF_STREAM_SLOTS_FIXED;
 constexpr int kSlotStride = 8;                          // double4 per slot = one 256-byte record, see `slots`
-static_assert(kStreamSlots >= 4 && kStreamSlots <= 32 && kStreamSlotsFixed >= 4 && kStreamSlotsFixed <= 32, "slots");
 #ifndef CPF_STREAM_GATHER_LANES
 #define CPF_STREAM_GATHER_LANES 32
 #endif
@@ -187,13 +184,65 @@ constexpr int kKernArgStep0 = (int)offsetof(StreamKernArgs, step0), kKernArgSeed
 #ifndef CPF_FLAT_ROUND_OUTCOME
 #define CPF_FLAT_ROUND_OUTCOME 1
 #endif
+// (with the kick the landing zone and the hit pool are larger: 7 slots keep the sixth wave, 6600 of 6826 bytes)
+#ifndef CPF_STREAM_SLOTS_BROWN
+#define CPF_STREAM_SLOTS_BROWN 10
+#endif
+#ifndef CPF_STREAM_HIT_REGS_L2
+#define CPF_STREAM_HIT_REGS_L2 0
+#endif
+// step_kernel_stream_vertex: the tet tables add ~40 vector registers to the advect: four waves per SIMD
+#ifndef CPF_STREAM_WAVES_VERTEX
+#define CPF_STREAM_WAVES_VERTEX 4
+#endif
+// What an instantiation has room for, by lookup mode (kLookupModes, cpf_device.h) and flags: record slots, hit pool, waves per SIMD
 template <bool BROWNIAN, bool STORE_VEL, bool STATS, int LOOKUP>
-// LOOKUP 2 / 3 (mixed records): one wave less; LOOKUP 4 (sparse clouds: pipelined per-lane gathers, 24 more registers): 5
-struct StreamOccupancy {
-    static constexpr bool kMixed = LOOKUP == 2 || LOOKUP == 3 || LOOKUP == 5 || LOOKUP == 11;
-    // (LOOKUP 2 carries the state of a half-done visit of a two-record cell: 80 registers, exactly what 6 waves allow)
-    static constexpr int waves = (STORE_VEL || STATS) ? 1 : (LOOKUP == 4 ? (BROWNIAN ? 4 : 5) : (BROWNIAN ? (kMixed ? 5 : ((LOOKUP == 6 || LOOKUP == 11) ? CPF_STREAM_WAVES_BOX_B : (LOOKUP == 1 ? CPF_STREAM_WAVES_B1 : CPF_STREAM_WAVES_B0))) : (LOOKUP == 2 ? CPF_STREAM_WAVES_L2 : ((kMixed && LOOKUP != 11) ? 6 : ((LOOKUP == 6 || LOOKUP == 11) ? CPF_STREAM_WAVES_BOX : (LOOKUP == 8 ? CPF_STREAM_WAVES_FLAT : CPF_STREAM_WAVES))))));
+struct StreamShape {
+    static constexpr LookupMode mode = lookup_traits(LOOKUP);
+    static_assert(mode.id == LOOKUP, "LOOKUP: a mode of kLookupModes");
+    static constexpr int slots = [] {                                       // record slots per wave (the measurements: CPF_STREAM_SLOTS)
+        if (!mode.fixed) return CPF_STREAM_SLOTS;
+        if (mode.box) return BROWNIAN ? CPF_STREAM_SLOTS_BOX_B : CPF_STREAM_SLOTS_BOX;
+        if (BROWNIAN && LOOKUP == kLookupFixed) return CPF_STREAM_SLOTS_BROWN;
+        return CPF_STREAM_SLOTS_FIXED;
+    }();
+    static_assert(slots >= 4 && slots <= 32, "slots");
+    static constexpr int stride = mode.box ? 4 : kSlotStride;               // double4 per slot
+    // a reflected lane's last wall hit point: in six VGPRs, else in a per-wave LDS pool of `pool` entries (stream_body, "HIT_IN_REGS")
+    static constexpr bool hitInRegs = !BROWNIAN && (!mode.bigCells || CPF_STREAM_HIT_REGS_L2);
+    static constexpr int pool = [] {
+        if (hitInRegs) return 1;
+        if (mode.mixed) return 16;
+        if (BROWNIAN && LOOKUP == kLookupLoop) return CPF_STREAM_HIT_POOL_B0;
+        return CPF_STREAM_HIT_POOL;
+    }();
+    static constexpr int waves = [] {              // per SIMD, step_kernel_stream and _flat (step_kernel_stream_vertex: CPF_STREAM_WAVES_VERTEX)
+        if (STORE_VEL || STATS) return 1;
+        if (mode.gatherAhead != 0) return BROWNIAN ? 4 : 5;      // sparse clouds: pipelined per-lane gathers, 24 more registers
+        if (BROWNIAN && mode.mixed) return 5;                    // mixed records: one wave less
+        if (BROWNIAN && mode.box) return CPF_STREAM_WAVES_BOX_B;
+        if (BROWNIAN) return LOOKUP == kLookupFixed ? CPF_STREAM_WAVES_B1 : CPF_STREAM_WAVES_B0;
+        // (two-record cells: the state of a half-done visit is carried along -- 80 registers, exactly what 6 waves allow)
+        if (mode.bigCells) return CPF_STREAM_WAVES_L2;
+        if (mode.box) return CPF_STREAM_WAVES_BOX;               // (with face groups or without)
+        if (mode.mixed) return 6;                                // mixed records: one wave less
+        if (LOOKUP == kLookupFlatLoop) return CPF_STREAM_WAVES_FLAT;
+        return CPF_STREAM_WAVES;
+    }();
 };
+// the shapes pinned -- slots, waves, pool without the kick | with it -- while every knob has its default (an A/B build moves them)
+#if CPF_STREAM_SLOTS == 6 && CPF_STREAM_SLOTS_FIXED == 9 && CPF_STREAM_SLOTS_BROWN == 10 && CPF_STREAM_SLOTS_BOX == 9 && CPF_STREAM_SLOTS_BOX_B == 12 && \
+    CPF_STREAM_WAVES == 7 && CPF_STREAM_WAVES_B0 == 7 && CPF_STREAM_WAVES_B1 == 5 && CPF_STREAM_WAVES_L2 == 6 && CPF_STREAM_WAVES_BOX == 6 && \
+    CPF_STREAM_WAVES_BOX_B == 6 && CPF_STREAM_WAVES_FLAT == 7 && CPF_STREAM_HIT_POOL == 40 && CPF_STREAM_HIT_POOL_B0 == 18 && CPF_STREAM_HIT_REGS_L2 == 0
+template <int LOOKUP>
+constexpr bool shape_is(int slots, int waves, int pool, int slotsB, int wavesB, int poolB) {
+    using P = StreamShape<false, false, false, LOOKUP>; using B = StreamShape<true, false, false, LOOKUP>;
+    return P::slots == slots && P::waves == waves && P::pool == pool && B::slots == slotsB && B::waves == wavesB && B::pool == poolB;
+}
+static_assert(shape_is<0>(6, 7, 1, 6, 7, 18) && shape_is<1>(9, 7, 1, 10, 5, 40) && shape_is<2>(9, 6, 16, 9, 5, 16) && shape_is<3>(9, 6, 1, 9, 5, 16) &&
+              shape_is<4>(9, 5, 1, 9, 4, 40) && shape_is<5>(6, 6, 1, 6, 5, 16) && shape_is<6>(9, 6, 1, 12, 6, 40) && shape_is<8>(6, 7, 1, 6, 7, 40) &&
+              shape_is<9>(9, 7, 1, 9, 7, 40) && shape_is<11>(9, 6, 1, 12, 5, 16), "StreamShape: slots, waves, pool per mode");
+#endif
 
 // The kernel's body.  VERTEX: the advect takes the velocity INTERPOLATED at the particle from tet-vertex values (the reference's
 // "VertexVelocity" mode, cuda/particles.cu:244-313; vertex_velocity() in cpf_walk.h, per-lane reads of the tet tables from L2)
@@ -208,14 +257,10 @@ template <bool BROWNIAN, bool REFLECT, bool STORE_VEL, bool STATS, int LOOKUP, b
 __device__ __forceinline__ void stream_body(
     const int64_t* __restrict__ gid, double* __restrict__ vel, int64_t n, double dt, double sigma, uint32_t step0,
     int nCyc, uint32_t seed, const MeshView& m, unsigned long long* __restrict__ counters, const StreamArgs& sa, const VertexField& vf) {
-    // (with the kick the landing zone and the hit pool are larger: 7 slots keep the sixth wave, 6600 of 6826 bytes)
-#ifndef CPF_STREAM_SLOTS_BROWN
-#define CPF_STREAM_SLOTS_BROWN 10
-#endif
-    constexpr int NS = (LOOKUP == 0 || LOOKUP == 5 || LOOKUP == 8) ? kStreamSlots : ((LOOKUP == 6 || LOOKUP == 11) ? (BROWNIAN ? CPF_STREAM_SLOTS_BOX_B : CPF_STREAM_SLOTS_BOX) : (BROWNIAN && LOOKUP == 1 ? CPF_STREAM_SLOTS_BROWN : kStreamSlotsFixed));
-    // LOOKUP 6: the mesh's 128-byte BOX records instead of the 256-byte ones (cpf_walk.h "box records")
-    constexpr bool BOX = LOOKUP == 6 || LOOKUP == 11;             // (11: ... on a mesh with face groups: 2:1-refined boxes)
-    constexpr int kStride = BOX ? 4 : kSlotStride;               // double4 per slot
+    using Shape = StreamShape<BROWNIAN, STORE_VEL, STATS, LOOKUP>;     // (what a LOOKUP mode means: the legend is kLookupModes, cpf_device.h)
+    constexpr bool LOOKUP_FIXED = Shape::mode.fixed, mixed = Shape::mode.mixed, bigCells = Shape::mode.bigCells, BOX = Shape::mode.box;
+    constexpr bool FLAT = Shape::mode.flat, HIT_IN_REGS = Shape::hitInRegs;
+    constexpr int kGatherAhead = Shape::mode.gatherAhead, NS = Shape::slots, kStride = Shape::stride, kPool = Shape::pool;
     constexpr unsigned kRecBytes = 32u * kStride;
     constexpr unsigned ALL = NS == 32 ? 0xFFFFFFFFu : ((1u << NS) - 1u);
     // the wave's record cache.  (256 bytes per slot is one full turn of the 64 LDS banks, so lanes reading the same plane
@@ -235,14 +280,9 @@ __device__ __forceinline__ void stream_body(
     //     and entries beyond the pool go to the wave's own 1.5 KB of global memory (sa.hitSpill).  (A pool of 10 for
     //     every instantiation, tried first, cost bench.py's window 3 %: there the cloud drifts into the outlet wall
     //     and whole tiles reflect, 54 of 64 lanes through the spill path.)
-#ifndef CPF_STREAM_HIT_REGS_L2
-#define CPF_STREAM_HIT_REGS_L2 0
-#endif
-    constexpr bool HIT_IN_REGS = !BROWNIAN && (LOOKUP != 2 || CPF_STREAM_HIT_REGS_L2);
     constexpr bool kInRound = CPF_STREAM_INROUND == 2 || (CPF_STREAM_INROUND == 1 && BROWNIAN);
-    static_assert(!(kInRound && (LOOKUP == 2 || LOOKUP == 3 || LOOKUP == 5 || LOOKUP == 11)), "in-round reflection knows neither face groups nor two-record cells");
-    constexpr int kPool = HIT_IN_REGS ? 1 : ((LOOKUP == 2 || LOOKUP == 3 || LOOKUP == 5 || LOOKUP == 11) ? 16 : ((BROWNIAN && LOOKUP == 0) ? CPF_STREAM_HIT_POOL_B0 : CPF_STREAM_HIT_POOL));
-    static_assert(!ZSET || ((LOOKUP == 8 || LOOKUP == 9) && !BROWNIAN && !VERTEX), "settled z: the flat walk without the kick or the vertex advect");
+    static_assert(!(kInRound && mixed), "in-round reflection knows neither face groups nor two-record cells");
+    static_assert(!ZSET || (FLAT && !BROWNIAN && !VERTEX), "settled z: the flat walk without the kick or the vertex advect");
     __shared__ double sLane[ZSET ? 2 : 3][64];
     __shared__ double sPool[3][kPool];
     __shared__ unsigned sPoolUsed;
@@ -256,23 +296,6 @@ __device__ __forceinline__ void stream_body(
     const unsigned preBase = uniform32(lds_addr(sPre));
     const unsigned slotBase = uniform32(lds_addr(slots));
     const int tpc = sa.tilesPerChunk;
-    // LOOKUP: how a wave finds its cells in its record cache, and which records can turn up --
-    //   0 loop over the distinct cells of the wave, 1 fixed tag compare, 2 / 3 fixed tag compare on a mesh that is not
-    //   all-hex (MeshView::mixed): 3 = every cell has at most six slots -- face groups and padded records only, the usual
-    //   2:1-refined hex mesh --, 2 = header records of cells with more than six slots may turn up as well
-    //   4 = fixed tag compare for SPARSE clouds on all-hex meshes (fewer than kStreamSparsePerCell particles per cell: nearly
-    //   every lane of a tile sits in a cell of its own and walks by per-lane gathers from L2 / HBM): the gather walk keeps three
-    //   planes in flight instead of one -- two dependent round trips per visit instead of six -- for 24 more registers, i.e.
-    //   five waves per SIMD.  2.1e6-cell box: 1.25e6 particles (one rank's share of BASELINE configs[4]) 0.187 -> 0.141 ms,
-    //   1e7 particles 0.673 / 0.631 -> 0.641 / 0.607; in the dense regime the same change costs 6 % (0.259 -> 0.277)
-    //   5 = as 3 (mixed records without header records) with the LOOP lookup and six slots: a refined mesh that still holds
-    //   hundreds of particles per cell (pitzDaily with a 2:1 patch: 0.157 -> see docs/design_r04.md 5.6)
-    //   6 = as 1 on the mesh's 128-byte BOX records (every cell an axis-aligned box: cpf_walk.h "box records") -- dense and sparse
-    //   clouds alike: three candidate faces per visit, one LDS round trip per record, one cache line per gathered record
-    //   8 = as 0 with the FLAT walk (cpf_walk.h): a 2-D mesh extruded straight in z, a field without a z component, no kick
-    constexpr bool LOOKUP_FIXED = LOOKUP != 0 && LOOKUP != 5 && LOOKUP != 8;
-    //   9 = as 1 with the flat walk (a 2-D mesh with fewer than 128 particles per cell: refined 2-D cases)
-    constexpr bool FLAT = LOOKUP == 8 || LOOKUP == 9;
     constexpr bool kMaskBusy = ZSET && CPF_FLAT_ROUND_MASK != 0, kPlainOutcome = ZSET && CPF_FLAT_ROUND_OUTCOME != 0;
     constexpr bool kFlatGather = ZSET && CPF_FLAT_ROUND_GATHER != 0, kHints = ZSET && CPF_FLAT_ROUND_HINTS != 0;
     constexpr bool kOneHook = ZSET && CPF_FLAT_ROUND_ONE_HOOK != 0;
@@ -289,9 +312,6 @@ __device__ __forceinline__ void stream_body(
         if (ZSET) return {sE[0][lane], sE[1][lane], 0.0};
         return {sE[0][lane], sE[1][lane], sE[2][lane]};
     };
-    constexpr bool mixed = LOOKUP == 2 || LOOKUP == 3 || LOOKUP == 5 || LOOKUP == 11;
-    constexpr bool bigCells = LOOKUP == 2;
-    constexpr int kGatherAhead = LOOKUP == 4 ? 3 : 0;
     const bool zFold = !BOX && BROWNIAN && REFLECT && m.zThin != 0;      // (stream_lookup_mode: no box records on a mesh one cell thick)
     const bool zLast = !FLAT && !BROWNIAN && m.zPairLast != 0;   // (with the kick every particle moves in z: the test would be wasted)
     // the kick on a one-cell-thick mesh whose side faces have nz == 0 exactly: the four side faces with two-term dot products
@@ -831,7 +851,7 @@ __device__ __forceinline__ void stream_body(
                             next = trace_lds4_flat_z<false>(S_, E, cur, rec, token, outSlot);     // (cpf_walk.h: flat walk under the kick)
                             else
                             next = (CPF_STREAM_PAIRED && LOOKUP_FIXED && !BROWNIAN && !mixed) ? trace_lds6_paired(S_, E, cur, rec, token, outSlot, zLast)
-                                                                : trace_lds6<(!BROWNIAN && (CPF_STREAM_L1_ZERO_SKIP || LOOKUP != 1)), mixed>(S_, E, cur, rec, token, outSlot, zLast, zFold && !zUnclear);
+                                                                : trace_lds6<(!BROWNIAN && (CPF_STREAM_L1_ZERO_SKIP || LOOKUP != kLookupFixed)), mixed>(S_, E, cur, rec, token, outSlot, zLast, zFold && !zUnclear);
                             if (STATS) ++st.hops;
                             }
                             if (REFLECT && next < 0 && !(mixed && is_group(next))) {       // (is_group: face-group codes and kSitOut)
@@ -1073,18 +1093,14 @@ __device__ __forceinline__ void stream_body(
 }
 
 template <bool BROWNIAN, bool REFLECT, bool STORE_VEL, bool STATS, int LOOKUP>
-__global__ __launch_bounds__(64, (StreamOccupancy<BROWNIAN, STORE_VEL, STATS, LOOKUP>::waves)) void step_kernel_stream(
+__global__ __launch_bounds__(64, (StreamShape<BROWNIAN, STORE_VEL, STATS, LOOKUP>::waves)) void step_kernel_stream(
     double* __restrict__ /* x */, double* __restrict__ /* y */, double* __restrict__ /* z */, int32_t* __restrict__ /* cell */,   // read through kernarg_cloud_ptrs()
     const int64_t* __restrict__ gid, double* __restrict__ vel, int64_t n, double dt, double sigma, uint32_t step0,
     int nCyc, uint32_t seed, MeshView m, unsigned long long* __restrict__ counters, StreamArgs sa) {
     stream_body<BROWNIAN, REFLECT, STORE_VEL, STATS, LOOKUP, false>(gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa, VertexField{});
 }
 
-// the "VertexVelocity" cycle (CPF_STEP_VERTEX_VELOCITY) on the streaming kernel: all-hex meshes, loop / fixed lookup; the tet
-// tables add ~40 vector registers to the advect: four waves per SIMD
-#ifndef CPF_STREAM_WAVES_VERTEX
-#define CPF_STREAM_WAVES_VERTEX 4
-#endif
+// the "VertexVelocity" cycle (CPF_STEP_VERTEX_VELOCITY) on the streaming kernel: all-hex meshes, loop / fixed lookup
 template <bool BROWNIAN, bool REFLECT, bool STORE_VEL, bool STATS, int LOOKUP>
 __global__ __launch_bounds__(64, ((STORE_VEL || STATS) ? 1 : CPF_STREAM_WAVES_VERTEX)) void step_kernel_stream_vertex(
     double* __restrict__ /* x */, double* __restrict__ /* y */, double* __restrict__ /* z */, int32_t* __restrict__ /* cell */,
@@ -1096,7 +1112,7 @@ __global__ __launch_bounds__(64, ((STORE_VEL || STATS) ? 1 : CPF_STREAM_WAVES_VE
 // the flat walk on a cloud whose z is settled: the body without z (stream_body, ZSET).  step_kernel_stream's parameter list, so
 // that the kernarg offsets stay valid (z is passed and never read); LOOKUP 8 and 9 only
 template <bool REFLECT, bool STORE_VEL, bool STATS, int LOOKUP>
-__global__ __launch_bounds__(64, (StreamOccupancy<false, STORE_VEL, STATS, LOOKUP>::waves)) void step_kernel_stream_flat(
+__global__ __launch_bounds__(64, (StreamShape<false, STORE_VEL, STATS, LOOKUP>::waves)) void step_kernel_stream_flat(
     double* __restrict__ /* x */, double* __restrict__ /* y */, double* __restrict__ /* z */, int32_t* __restrict__ /* cell */,
     const int64_t* __restrict__ gid, double* __restrict__ vel, int64_t n, double dt, double sigma, uint32_t step0,
     int nCyc, uint32_t seed, MeshView m, unsigned long long* __restrict__ counters, StreamArgs sa) {
@@ -1111,13 +1127,16 @@ static hipError_t launch_stream_inst(hipStream_t st, double* x, double* y, doubl
                                      double* vel, int64_t n, double dt, double sigma, uint32_t step0, int nCyc,
                                      uint32_t seed, const MeshView& m, unsigned long long* counters, StreamState& ss,
                                      const VertexField* vf, bool settled, hipEvent_t evStart, hipEvent_t evStop) {
+    constexpr LookupMode mode = lookup_traits(LF);
+    constexpr auto kernel = [] {
+        if constexpr (VX) return &step_kernel_stream_vertex<B, R_, SV, ST, LF>;
+        else if constexpr (ZS) return &step_kernel_stream_flat<R_, SV, ST, LF>;
+        else return &step_kernel_stream<B, R_, SV, ST, LF>;
+    }();
     static int wavesPerCU = 0;                       // per instantiation; benign race (same value)
     if (wavesPerCU == 0) {
         int nb = 0;
-        hipError_t e;
-        if constexpr (VX) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, step_kernel_stream_vertex<B, R_, SV, ST, LF>, 64, 0);
-        else if constexpr (ZS) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, step_kernel_stream_flat<R_, SV, ST, LF>, 64, 0);
-        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, step_kernel_stream<B, R_, SV, ST, LF>, 64, 0);
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 64, 0);
         if (e != hipSuccess) return e;
         wavesPerCU = nb < 1 ? 1 : (nb > 32 ? 32 : nb);
         if (ZS && CPF_STREAM_WAVES_FLAT_BODY > 0 && wavesPerCU > 4 * CPF_STREAM_WAVES_FLAT_BODY) wavesPerCU = 4 * CPF_STREAM_WAVES_FLAT_BODY;
@@ -1130,8 +1149,8 @@ static hipError_t launch_stream_inst(hipStream_t st, double* x, double* y, doubl
     // finer chunks and a longer tile-by-tile tail (tools/sweep3d_opts.sh: 3 / 0.2 against 4 / 0.1 on the 3-D box 0.2632 /
     // 0.2701 -> 0.2585 / 0.2661 ms, TJunction 0.1581 / 0.1708 -> 0.1569 / 0.1687, 5 particles per cell 0.682 / 0.670 -> 0.677 /
     // 0.636; pitzDaily is at its optimum with 4 / 0.1, tools/tail_sweep.sh)
-    int tpc = ss.tilesPerChunk > 0 ? ss.tilesPerChunk : ((LF == 0 || LF == 5 || LF == 8) ? 4 : 3);
-    const double tailFraction = ss.tailFraction >= 0.0 ? ss.tailFraction : ((LF == 0 || LF == 5 || LF == 8) ? 0.1 : 0.2);
+    int tpc = ss.tilesPerChunk > 0 ? ss.tilesPerChunk : (!mode.fixed ? 4 : 3);
+    const double tailFraction = ss.tailFraction >= 0.0 ? ss.tailFraction : (!mode.fixed ? 0.1 : 0.2);
     while (tpc > 1 && nTiles / tpc < 4 * slotsOnChip) tpc = tpc > 2 ? tpc - 1 : 1;
     // the first (1 - tailFraction) of the cloud in chunks of tpc tiles, the rest tile by tile
     int64_t bigChunks = (int64_t)((double)(nTiles / tpc) * (1.0 - tailFraction));
@@ -1147,35 +1166,21 @@ static hipError_t launch_stream_inst(hipStream_t st, double* x, double* y, doubl
     if (R < 1 || ss.d_hitSpill == nullptr) return hipErrorInvalidValue;
     // (the flat instantiations only: every other one streams z whatever the caller says; "flat_z" 0: they stream it too)
     // (ZS: the caller has decided just that, StepPlan::flat_body)
-    const bool zSettled = (LF == 8 || LF == 9) && !VX && settled && ss.flatZ != 0;
-    if (ZS != zSettled && (LF == 8 || LF == 9) && !VX) return hipErrorInvalidValue;
+    const bool zSettled = mode.flat && !VX && settled && ss.flatZ != 0;
+    if (ZS != zSettled && mode.flat && !VX) return hipErrorInvalidValue;
     StreamArgs sa = {cur, nxt, (int)R, tpc, (unsigned)bigChunks, ss.debug, ss.d_hitSpill, zSettled ? 1 : 0, ss.zBad};
-    if constexpr (VX) {
-        if (vf == nullptr) return hipErrorInvalidValue;
+    auto launch = [&](const auto&... tail) {       // StreamKernArgs' order; tail: what the kernel appends to it (the vertex kernel's VertexField)
+        const dim3 grid((unsigned)(R * kStreamGroups));
         if (evStart != nullptr && evStop != nullptr)
-            hipExtLaunchKernelGGL((step_kernel_stream_vertex<B, R_, SV, ST, LF>), dim3((unsigned)(R * kStreamGroups)), dim3(64), 0, st, evStart,
-                                  evStop, 0, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa, *vf);
+            hipExtLaunchKernelGGL(kernel, grid, dim3(64), 0, st, evStart, evStop, 0, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc,
+                                  seed, m, counters, sa, tail...);
         else
-        hipLaunchKernelGGL((step_kernel_stream_vertex<B, R_, SV, ST, LF>), dim3((unsigned)(R * kStreamGroups)), dim3(64), 0, st, x, y, z, cell,
-                           gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa, *vf);
+            hipLaunchKernelGGL(kernel, grid, dim3(64), 0, st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa,
+                               tail...);
         return stream_launch_done(st, ss);
-    } else if constexpr (ZS) {
-        if (evStart != nullptr && evStop != nullptr)
-            hipExtLaunchKernelGGL((step_kernel_stream_flat<R_, SV, ST, LF>), dim3((unsigned)(R * kStreamGroups)), dim3(64), 0, st, evStart,
-                                  evStop, 0, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa);
-        else
-        hipLaunchKernelGGL((step_kernel_stream_flat<R_, SV, ST, LF>), dim3((unsigned)(R * kStreamGroups)), dim3(64), 0, st, x, y, z, cell,
-                           gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa);
-        return stream_launch_done(st, ss);
-    } else {
-    if (evStart != nullptr && evStop != nullptr)
-        hipExtLaunchKernelGGL((step_kernel_stream<B, R_, SV, ST, LF>), dim3((unsigned)(R * kStreamGroups)), dim3(64), 0, st, evStart,
-                              evStop, 0, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa);
-    else
-    hipLaunchKernelGGL((step_kernel_stream<B, R_, SV, ST, LF>), dim3((unsigned)(R * kStreamGroups)), dim3(64), 0, st, x, y, z, cell,
-                       gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa);
-    return stream_launch_done(st, ss);
-    }
+    };
+    if constexpr (VX) return vf == nullptr ? hipErrorInvalidValue : launch(*vf);
+    else return launch();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1191,22 +1196,23 @@ static int stream_lookup_mode(int64_t n, const MeshView& m, const StreamState& s
     }
     // the "VertexVelocity" cycle: the loop or the fixed lookup on the 256-byte records (no flat walk: the interpolated velocity
     // may have a z component whatever the cell field says)
-    if (vertex) return n < 128 * cells ? 1 : 0;
+    if (vertex) return n < 128 * cells ? kLookupFixed : kLookupLoop;
     // not all-hex: with / without big cells (more than six slots); without them and with many particles per cell, the loop lookup
-    // (every cell a box although the mesh has face groups -- 2:1-refined boxes: box records with group slots, 11)
-    if (m.mixed == 1 && m.boxRec != nullptr && m.zThin == 0 && ss.lookup < 0) return 11;
-    if (m.mixed) return m.mixed == 2 ? 2 : ((ss.lookup >= 0 ? ss.lookup == 0 : n >= 128 * cells) ? 5 : 3);
+    // (every cell a box although the mesh has face groups -- 2:1-refined boxes: box records with group slots)
+    if (m.mixed == 1 && m.boxRec != nullptr && m.zThin == 0 && ss.lookup < 0) return kLookupBoxGroups;
+    if (m.mixed == 2) return kLookupMixedBig;
+    if (m.mixed) return (ss.lookup >= 0 ? ss.lookup == kLookupLoop : n >= 128 * cells) ? kLookupMixedLoop : kLookupMixed;
     const bool box = m.boxRec != nullptr && m.zThin == 0;
-    if (ss.lookup >= 0) return (ss.lookup == 6 && !box) ? 1 : ss.lookup;      // "stream_lookup": 0, 1, 4 or 6 (2, 3, 5: diagnostics)
+    if (ss.lookup >= 0) return (ss.lookup == kLookupBox && !box) ? kLookupFixed : ss.lookup;      // "stream_lookup": 0, 1, 4 or 6 (2, 3, 5: diagnostics)
     // box records whatever the density: also above 128 particles per cell they beat the loop lookup on 256-byte records (round 4,
     // 3-D boxes of 2 048 / 20 480 / 61 440 cells with 1e7 particles: 0.1216 / 0.1648 / 0.2036 -> 0.1203 / 0.1617 / 0.1892 ms, with the
     // kick 0.1584 / 0.2178 / 0.2729 -> 0.1568 / 0.2052 / 0.2375)
-    if (box && CPF_STREAM_BOX_SPARSE) return 6;
-    if (n < kStreamSparsePerCell * cells) return 4;
-    // a 2-D mesh, a field without a z component, no kick: the flat walk (8 = 0, 9 = 1 with it)
+    if (box && CPF_STREAM_BOX_SPARSE) return kLookupBox;
+    if (n < kStreamSparsePerCell * cells) return kLookupSparse;
+    // a 2-D mesh, a field without a z component, no kick: the flat walk
     const bool flat = !brown && ss.flat && ss.flatField && m.zSide0 != 0;
-    if (n < 128 * cells) return flat ? 9 : 1;
-    return flat ? 8 : 0;
+    if (n < 128 * cells) return flat ? kLookupFlatFixed : kLookupFixed;
+    return flat ? kLookupFlatLoop : kLookupLoop;
 }
 
 StepPlan plan_step(const MeshView& m, const StreamState& ss, int variant, const VertexField* vf, int64_t n, int nCyc, double D,
@@ -1261,35 +1267,29 @@ StepPlan plan_step(const MeshView& m, const StreamState& ss, int variant, const 
     return p;
 }
 
-// the streaming kernels' instantiations: step_kernel_stream with every LOOKUP (the flat walk, 8 and 9, without the kick only),
-// step_kernel_stream_vertex with 0 and 1, step_kernel_stream_flat with 8 and 9
-template <int... L, class F>
-static hipError_t with_lookup(int lookup, F&& f) {
-    hipError_t e = hipErrorInvalidValue;
-    (void)((lookup == L && ((e = f(std::integral_constant<int, L>{})), true)) || ...);
-    return e;
-}
+// the streaming kernels' instantiations, from kLookupModes (with_lookup): step_kernel_stream with every mode, the flat walk without the kick
+// only and on a settled cloud as step_kernel_stream_flat; step_kernel_stream_vertex with the plain modes (loop / fixed, 256-byte records)
+constexpr bool vertex_mode(LookupMode r) { return !(r.mixed || r.box || r.flat || r.gatherAhead != 0); }
 hipError_t launch_step_stream(const StepPlan& p, hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid,
                               double* vel, int64_t n, double dt, double sigma, uint32_t step0, int nCyc, uint32_t seed,
                               const MeshView& m, unsigned long long* counters, const VertexField* vf, StreamState& ss, bool zSettled,
                               hipEvent_t evStart, hipEvent_t evStop) {
     return with_bools([&](auto B, auto R, auto SV, auto ST) {
+        auto inst = [&](auto kick, auto LF, auto VX, auto ZS) {      // the launcher of: kick, mode, "VertexVelocity" cycle, body without z
+            return launch_stream_inst<kick, R, SV, ST, LF, VX, ZS>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters,
+                                                                   ss, vf, zSettled, evStart, evStop);
+        };
+        constexpr std::true_type yes{}; constexpr std::false_type no{};
         if (p.kernel == StepPlan::kStreamVertex)
-            return with_lookup<0, 1>(p.lookup, [&](auto LF) {
-                return launch_stream_inst<B, R, SV, ST, LF, true>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m,
-                                                                  counters, ss, vf, zSettled, evStart, evStop);
+            return with_lookup(p.lookup, [&](auto LF) {
+                if constexpr (vertex_mode(lookup_traits(LF))) return inst(B, LF, yes, no);
+                else return hipErrorInvalidValue;
             });
-        // a settled cloud under the flat walk: the body without z
-        if (p.flat_body(ss, zSettled))
-            return with_lookup<8, 9>(p.lookup, [&](auto LF) {
-                if constexpr (B) return hipErrorInvalidValue;
-                else return launch_stream_inst<false, R, SV, ST, LF, false, true>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m,
-                                                                                  counters, ss, vf, zSettled, evStart, evStop);
-            });
-        return with_lookup<0, 1, 2, 3, 4, 5, 6, 8, 9, 11>(p.lookup, [&](auto LF) {
-            if constexpr (B && (LF == 8 || LF == 9)) return hipErrorInvalidValue;
-            else return launch_stream_inst<B, R, SV, ST, LF>(st, x, y, z, cell, gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters,
-                                                             ss, vf, zSettled, evStart, evStop);
+        const bool body = p.flat_body(ss, zSettled);             // a settled cloud under the flat walk: the body without z
+        return with_lookup(p.lookup, [&](auto LF) {
+            if constexpr (!lookup_traits(LF).flat) return inst(B, LF, no, no);
+            else if constexpr (B) return hipErrorInvalidValue;   // the flat walk: without the kick only
+            else return body ? inst(no, LF, no, yes) : inst(no, LF, no, no);
         });
     }, p.brown, p.reflect, p.storeVel, p.stats);
 }

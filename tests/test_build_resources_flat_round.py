@@ -10,7 +10,6 @@ the LDS walk and four in the flat gather walk.  Both parent figures are the pare
 walk and the six of ``trace_fixed<6>`` on the global record -- is a ``hipcc -S`` compile of the parent commit with the same flags.
 The fixed lookup's entry (9) is no worse off than its parent: 94 scalar registers and two of them spilled to vector lanes."""
 import os
-import re
 import subprocess
 import sys
 
@@ -20,27 +19,10 @@ PARENT_INSTRUCTIONS = 1442        # docs/experiments.md, round 8
 MAX_DIVISIONS = 8                 # the parent: 10 (hipcc -S of the parent commit)
 
 
-def _kernel_bodies(asm):
-    """mangled kernel name -> its instructions (labels, directives and comments dropped)."""
-    out, name = {}, None
-    for line in asm.splitlines():
-        m = re.match(r"^(_Z\w+):", line)
-        if m:
-            name = m.group(1); out[name] = []
-            continue
-        if line.startswith(".Lfunc_end"):
-            name = None
-            continue
-        t = line.split(";")[0].strip()
-        if name is None or not t or t.startswith(".") or t.endswith(":"):
-            continue
-        out[name].append(t)
-    return out
-
-
 def test_flat_round_resources_and_code(tmp_path):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import resource_usage
+    _kernel_bodies = resource_usage.kernel_bodies          # (lives with the digest mode that shares it)
     asm_path = str(tmp_path / "cpf_stream.s")
     r = subprocess.run(resource_usage.hipcc_cmd("cpf_stream.hip") + ["-S", "--cuda-device-only", "-o", asm_path],
                        capture_output=True, text=True)

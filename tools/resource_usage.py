@@ -1,20 +1,28 @@
 #!/usr/bin/env python3
 """Compiler resource usage of every step-kernel instantiation -> profiles/<label>_resource_usage.txt
-(hipcc -Rpass-analysis=kernel-resource-usage; runs without a GPU).  python tools/resource_usage.py r02"""
+(hipcc -Rpass-analysis=kernel-resource-usage; runs without a GPU).  python tools/resource_usage.py r02
+
+python tools/resource_usage.py --digest <label> [--root <checkout>] [file.hip ...] -> profiles/<label>_code_digest.txt: one line
+per kernel of cpf_stream.hip and cpf_kernels.hip -- demangled name | instruction count | SHA-256 of its normalised instruction
+stream -- to compare the generated code of two commits (the other one through ``git worktree add`` and --root).  A refactor
+that claims "no instruction changes" shows two listings that ``diff`` finds equal."""
+import hashlib
 import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CS = os.path.join(ROOT, "cudaparticlesfoam_amd", "csrc")
 
 
-def hipcc_cmd(src):
-    """The product's compile of one csrc file (csrc/Makefile's flags), without its output option."""
+def hipcc_cmd(src, root=ROOT):
+    """The product's compile of one csrc file (csrc/Makefile's flags), without its output option; root: the checkout to compile."""
+    cs = os.path.join(root, "cudaparticlesfoam_amd", "csrc")
     extra = ["-mllvm", "--amdgpu-sched-strategy=max-ilp"] if src == "cpf_stream.hip" else []      # as in csrc/Makefile
     return (["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-O3", "-fPIC", "-ffp-contract=off"] + extra +
-            ["-I" + os.path.join(ROOT, "include"), "-I" + CS, os.path.join(CS, src), "-Rpass-analysis=kernel-resource-usage"])
+            ["-I" + os.path.join(root, "include"), "-I" + cs, os.path.join(cs, src), "-Rpass-analysis=kernel-resource-usage"])
 
 
 def parse(remarks):
@@ -42,7 +50,60 @@ def collect():
     return rows
 
 
+def kernel_bodies(asm):
+    """mangled kernel name -> its instructions (labels, directives and comments dropped)."""
+    out, name = {}, None
+    for line in asm.splitlines():
+        m = re.match(r"^(_Z\w+):", line)
+        if m:
+            name = m.group(1); out[name] = []
+            continue
+        if line.startswith(".Lfunc_end"):
+            name = None
+            continue
+        t = line.split(";")[0].strip()
+        if name is None or not t or t.startswith(".") or t.endswith(":"):
+            continue
+        out[name].append(t)
+    return out
+
+
+def digests(asm):
+    """Rows (demangled name, instruction count, SHA-256) of every kernel in a ``hipcc -S --cuda-device-only`` listing.  The
+    hash is over kernel_bodies' instructions, one per line, single-spaced, with the function index taken out of the block labels
+    that branches name (.LBB<function>_<block>): a kernel that only moved within its file keeps its digest."""
+    bodies = kernel_bodies(asm)
+    names = subprocess.run(["c++filt"], input="\n".join(bodies), capture_output=True, text=True).stdout.split("\n")
+    rows = []
+    for mangled, name in zip(bodies, names):
+        text = "\n".join(re.sub(r"\.LBB\d+_(\d+)", r".LBB_\1", " ".join(t.split())) for t in bodies[mangled])
+        rows.append((name.split("(")[0], str(len(bodies[mangled])), hashlib.sha256(text.encode()).hexdigest()))
+    return sorted(rows)
+
+
+def main_digest(argv):
+    root = ROOT
+    if "--root" in argv:
+        i = argv.index("--root"); root = os.path.abspath(argv[i + 1]); del argv[i:i + 2]
+    label, srcs = argv[0], argv[1:] or ["cpf_stream.hip", "cpf_kernels.hip"]
+    out = ["# Generated code of the kernels: hipcc -S --cuda-device-only with csrc/Makefile's flags (gfx950), per kernel the",
+           "# SHA-256 of its instructions without comments, directives, labels and the function index of .LBB<function>_<block>.",
+           "# tools/resource_usage.py --digest " + label,
+           "# file | kernel | instructions | sha256"]
+    for src in srcs:
+        asm_path = os.path.join(tempfile.mkdtemp(), src + ".s")
+        r = subprocess.run(hipcc_cmd(src, root)[:-1] + ["-S", "--cuda-device-only", "-o", asm_path], capture_output=True, text=True)
+        if r.returncode != 0:
+            sys.exit(r.stderr[-4000:])
+        out += [" | ".join((src,) + row) for row in digests(open(asm_path).read())]
+    path = os.path.join(ROOT, "profiles", label + "_code_digest.txt")
+    open(path, "w").write("\n".join(out) + "\n")
+    print("%s: %d kernels" % (path, len(out) - 4))
+
+
 def main():
+    if len(sys.argv) > 2 and sys.argv[1] == "--digest":
+        return main_digest(sys.argv[2:])
     label = sys.argv[1] if len(sys.argv) > 1 else "r03"
     rows = collect()
     out = ["# Compiler resource usage of the step kernels: hipcc -O3 --offload-arch=gfx950 -ffp-contract=off",
