@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <condition_variable>
 #include <mutex>
 #include <string>
@@ -16,110 +17,175 @@
 #include "cpf.h"
 #include "cpf_device.h"
 #include "cpf_internal.h"
+#include "cpf_own.h"
 #include "cpf_walk.h"      // VertexField
 
+// (device-scope release is all a time stamp needs; measured against the default flags: no difference)
+#ifndef CPF_TIMING_EVENT_FLAGS
+#define CPF_TIMING_EVENT_FLAGS hipEventReleaseToDevice
+#endif
+
+namespace {
+using cpf::DevBuf; using cpf::Event; using cpf::PinnedBuf;
+
+// What the context owns, grouped by lifetime: each group goes away as a whole -- assigned over with an empty one, or with the
+// context.  The members are owners (cpf_own.h): nothing here is freed by hand.
+
+// The mesh: the host tables and every device table made from them.  Replaced by cpf_set_mesh.
+struct Mesh {
+    bool have = false, haveU = false;
+    cpf::HostTables host;
+    DevBuf<int32_t> cellOff, nbr, groupOff, groupNbr;
+    DevBuf<double4> planes;
+    DevBuf<double4> U;
+    DevBuf<double> U3;          // staging for host uploads
+    DevBuf<double> boxRec;      // 128-byte box records (meshes of axis-aligned boxes with records; cpf_walk.h "box records")
+    DevBuf<double4> cellRec;    // packed per-cell records (all-hex meshes; mixed meshes: cpf_walk.h "cell records")
+    int64_t nSecondRecords = 0; // second records (cells with 7..12 slots), behind the nCells first ones
+    DevBuf<float> cellBox;      // per-cell boxes for the sort key
+    DevBuf<int32_t> curveRank;  // per-cell rank along the Morton curve: the sort's major key for sparse clouds ("sort_curve")
+    DevBuf<int32_t> binOff, binCells;
+    size_t bytes = 0;           // of the device tables (cpf_mesh_info)
+    // warped / concave cells (cpf_mesh.cpp: measure_mesh, derive_mesh; DESIGN.md "Warped cells")
+    cpf_mesh_quality quality{};         // of the mesh as the caller gave it
+    int64_t nParent = 0;                // cells of the mesh as given: == host.nCells unless cells were decomposed
+    std::vector<int32_t> first;         // [nParent+1] derived cells of parent c: first[c] .. first[c+1] (decomposed meshes only)
+    DevBuf<int32_t> parentOf;           // [host.nCells] parent of every derived cell; null: no cell decomposed
+    DevBuf<double> Uparent;             // [nParent][3] staging of cpf_set_velocity on a decomposed mesh
+};
+
+// "VertexVelocity" advect only: the tet decomposition and one velocity per tet-mesh vertex.  It belongs to the mesh it was made
+// for (cpf_set_tets checks it against that mesh's cell count): a new mesh starts without one.  Built by cpf_set_tets into a
+// local and moved in whole, so nTets, tetsPerCell and the cone pair never describe tables that do not exist.
+struct TetField {
+    DevBuf<double> pos; DevBuf<int32_t> tets; DevBuf<double> vel;
+    int64_t nVerts = 0, nTets = 0; int tetsPerCell = 0; bool haveVel = false;
+    DevBuf<double> cone;        // cone-locate tet records (cpf_walk.h, VertexField), if the decomposition admits them
+    DevBuf<double> apex;        // ... and the cells' apexes: both or neither
+    std::string coneWhy;        // why the tables were not built (cpf_step_kernel_name says so)
+};
+
+struct CloudArrays {
+    DevBuf<double> x, y, z;
+    DevBuf<int32_t> cell;
+    DevBuf<int64_t> gid;
+    hipError_t alloc(size_t c) {                // (stops at the first failure)
+        hipError_t e;
+        (void)((e = x.alloc(c)) || (e = y.alloc(c)) || (e = z.alloc(c)) || (e = cell.alloc(c)) || (e = gid.alloc(c)));
+        return e;
+    }
+};
+// The context's own cloud.  Replaced by cpf_alloc_particles.
+struct Cloud {
+    int64_t cap = 0, n = 0;
+    CloudArrays cur;
+    // second set of x, y, z, cell, gid: the sort writes the reordered cloud there and the sets swap roles (no copy back);
+    // allocated by the first sort, all five or none
+    CloudArrays spare;
+    DevBuf<double> vel;
+    bool located = false;
+    // z of the cloud is a fixed point of the flat cycle (CPF_STEP_Z_SETTLED): set behind a flat launch that streamed z, cleared
+    // by everything else that writes x, y, z or cell -- except a sort, which only permutes
+    bool zSettled = false;
+};
+
+// asynchronous output (cpf_write_vtu_async): one frame in flight.  Lives as long as the context.
+struct FrameWriter {
+    std::thread thread;
+    bool live = false;
+    int status = CPF_OK;
+    // the frame's snapshot: packed in particle-id order on the compute stream into `snapDev`, copied to pinned host memory on
+    // `io` behind an event, read by the worker thread only -- the step loop's stream never waits for PCIe (round 6)
+    DevBuf<char> snapDev;
+    PinnedBuf<char> snapHost;
+    size_t snapBytes = 0;
+    cpf::Stream io;
+    Event evSnap, evCopied;
+    double ke = 0.0;                            // of the frame the worker wrote last (valid after its join)
+    std::mutex keMutex; std::condition_variable keCv; bool keReady = false;
+};
+
+// cpf_timing_*: event pairs round step launches.  Lives as long as the context.
+struct Timing {
+    int stride = 1;                             // "timing_stride": bracket every k-th step launch only
+    uint64_t launch = 0;
+    bool on = false;
+    std::vector<std::pair<Event, Event>> recorded;
+    std::vector<Event> pool;
+    hipError_t take(Event& ev) {
+        if (pool.empty()) return ev.create(CPF_TIMING_EVENT_FLAGS);
+        ev = std::move(pool.back()); pool.pop_back();
+        return hipSuccess;
+    }
+    void give_back(Event& ev) { if (ev) pool.push_back(std::move(ev)); }
+    // sums the recorded pairs and hands their events back, from the oldest on: all of them (the caller has synchronised), or,
+    // polling, those whose end has been reached -- launches complete in stream order
+    hipError_t drain(bool poll, int64_t* launches, double* total_ms) {
+        double tot = 0.0; size_t done = 0; hipError_t e = hipSuccess;
+        for (; done < recorded.size(); ++done) {
+            auto& p = recorded[done];
+            if (poll && (e = hipEventQuery(p.second)) != hipSuccess) break;
+            float ms = 0.f;
+            if ((e = hipEventElapsedTime(&ms, p.first, p.second)) != hipSuccess) break;
+            tot += (double)ms;
+            give_back(p.first); give_back(p.second);
+        }
+        recorded.erase(recorded.begin(), recorded.begin() + (std::ptrdiff_t)done);
+        if (e != hipSuccess && e != hipErrorNotReady) return e;
+        *launches = (int64_t)done;
+        *total_ms = tot;
+        return hipSuccess;
+    }
+};
+}  // namespace
+
+// Members are destroyed in reverse order: everything below is released before `ownStream` is.
 struct cpf_context {
     int device = 0;
-    hipStream_t ownStream = nullptr, stream = nullptr;
+    cpf::Stream ownStream;
+    hipStream_t stream = nullptr;               // ownStream, or the caller's (cpf_set_stream)
     mutable std::string err;
-    // mesh
-    bool haveMesh = false, haveU = false;
-    cpf::HostTables host;
-    int32_t* d_cellOff = nullptr;
-    double4* d_planes = nullptr;
-    int32_t* d_nbr = nullptr;
-    int32_t *d_groupOff = nullptr, *d_groupNbr = nullptr;
+    // ---- options: they survive a new mesh and a new cloud
     bool zFold = true;               // "z_fold": mirror the kicked end point about the planes of a one-cell-thick mesh before the walk
-    double4* d_U = nullptr;
-    double* d_U3 = nullptr;     // staging for host uploads
-    double* d_boxRec = nullptr;     // 128-byte box records (meshes of axis-aligned boxes with records; cpf_walk.h "box records")
     bool boxRecords = true;         // "box_records": 0 = never use them (diagnostics; bit-identical either way)
-    double4* d_cellRec = nullptr;   // packed per-cell records (all-hex meshes; mixed meshes: cpf_walk.h "cell records")
-    unsigned long long* d_occupied = nullptr;   // [0] occupied cells, [1] live particles of the last sort (device) ...
-    hipEvent_t evFieldFlag = nullptr;           // recorded behind the read-back of "the field has a z component" (cpf_set_velocity_dev)
-    bool fieldFlagPending = false;              // ... and not yet seen complete: until then the field counts as having one
-    unsigned long long* h_occupied = nullptr;   // ... and their pinned host copy (StreamState::occupiedHost)
-    int64_t nSecondRecords = 0;     // second records (cells with 7..12 slots), behind the nCells first ones
-    float* d_cellBox = nullptr;     // per-cell boxes for the sort key
-    int32_t* d_curveRank = nullptr; // per-cell rank along the Morton curve: the sort's major key for sparse clouds ("sort_curve")
     int sortMethod = 2;             // "sort_method": the (key, index) sort: 2 = this library's radix sort (cpf_kernels.hip, rt_sort_pairs), 0 = hipcub's;
                                     // the same order either way
     int sortCurve = -1;             // "sort_curve": -1 = Morton rank when the cloud has fewer than 8 particles per cell, 0 = cell id, 1 = Morton rank
-    int32_t* d_binOff = nullptr;
-    int32_t* d_binCells = nullptr;
-    size_t meshBytes = 0;
-    // owned cloud
-    int64_t cap = 0, n = 0;
-    double *x = nullptr, *y = nullptr, *z = nullptr, *vel = nullptr;
-    int32_t* cell = nullptr;
-    int64_t* gid = nullptr;
-    // second set of x, y, z, cell, gid: the sort writes the reordered cloud there and the sets swap roles (no copy back);
-    // allocated by the first sort
-    double *x2 = nullptr, *y2 = nullptr, *z2 = nullptr;
-    int32_t* cell2 = nullptr;
-    int64_t* gid2 = nullptr;
-    bool located = false;
-    // scratch
-    void* scratch = nullptr;
-    size_t scratchBytes = 0;
-    // counters / rng
-    // [kCounterSlots][4] = steps, hops, reflections, lost, sharded by block id (one hot word would
-    // serialise every block of every launch on a single L2 atomic unit), then 4 scratch words
-    unsigned long long* d_counters = nullptr;
-    uint32_t seed = 1591593751u;                // cuda/particles.cu:544
-    uint32_t stepCounter = 0;
     int sortInterval = 50;                      // "sort_interval": cpf_step re-sorts the owned cloud by cell every N cycles
-    uint32_t lastSortStep = 0;
     bool stats = false;                         // "stats": per-launch counters (steps, cells visited, reflections, lost)
     int stepVariant = -1;                       // cpf_set_option("step_variant"), see include/cpf.h: -1 = choose per launch
     bool vtuBinary = false;                     // cpf_set_option("vtu_binary"): frames with raw appended arrays instead of the reference's ASCII
     bool mixedRecords = true;                   // cpf_set_option("mixed_records"): build cell records for hex-dominant meshes too (before cpf_set_mesh)
-    // warped / concave cells (cpf_mesh.cpp: measure_mesh, derive_mesh; DESIGN.md "Warped cells")
     double nonplanarTol = cpf::kNonPlanarTolDefault;    // "nonplanar_tol" (before cpf_set_mesh)
     bool splitNonplanar = true;                         // "split_nonplanar" (before cpf_set_mesh): 0 = one plane per face everywhere
-    cpf_mesh_quality quality{};                         // of the mesh as the caller gave it
-    int64_t nParent = 0;                                // cells of the mesh as given: == host.nCells unless cells were decomposed
-    std::vector<int32_t> first;                         // [nParent+1] derived cells of parent c: first[c] .. first[c+1] (decomposed meshes only)
-    int32_t* d_parentOf = nullptr;                      // [host.nCells] parent of every derived cell; null: no cell decomposed
-    double* d_Uparent = nullptr;                        // [nParent][3] staging of cpf_set_velocity on a decomposed mesh
-    cpf::StreamState streamState;               // chunk counter + tuning of the streaming step kernel
-    int64_t lastStepN = -1;                     // particle count of the most recent step launch (cpf_step_kernel_name)
-    int lastStepCycles = 1;                     // ... and its cycles per launch
-    // z of the context's own cloud is a fixed point of the flat cycle (CPF_STEP_Z_SETTLED): set behind a flat launch that
-    // streamed z, cleared by everything else that writes x, y, z or cell -- except a sort, which only permutes
-    bool zSettled = false;
-    bool lastStepZSettled = false;              // what the most recent cpf_step_dev left behind on ITS arrays (cpf_shard.cpp)
+    bool vertexFast = true;                     // cpf_set_option("vertex_fast")
+    uint32_t seed = 1591593751u;                // cuda/particles.cu:544
+    // ---- the groups
+    Mesh mesh; TetField tet; Cloud cloud; FrameWriter frame; Timing timing;
+    // ---- what lives as long as the context
+    DevBuf<char> scratch;
+    size_t scratchBytes = 0;
+    // [kCounterSlots][4] = steps, hops, reflections, lost, sharded by block id (one hot word would
+    // serialise every block of every launch on a single L2 atomic unit), then 4 scratch words
+    DevBuf<unsigned long long> counters;
+    DevBuf<unsigned long long> occupied;        // [0] occupied cells, [1] live particles of the last sort (device) ...
+    PinnedBuf<unsigned long long> h_occupied;   // ... and their pinned host copy (StreamState::occupiedHost)
+    Event evFieldFlag;                          // recorded behind the read-back of "the field has a z component" (cpf_set_velocity_dev)
+    bool fieldFlagPending = false;              // ... and not yet seen complete: until then the field counts as having one
     // "a live particle's z is not finite", written by a flat launch that streams z (StreamState::zBad, pinned); evZBad is recorded
     // behind such a launch, and while zBadPending the launch's verdict has not been read: the first launch that would leave z
     // alone waits for it -- one wait per unsettling event, no pass over the cloud
-    unsigned* h_zBad = nullptr;
-    hipEvent_t evZBad = nullptr;
+    PinnedBuf<unsigned> h_zBad;
+    Event evZBad;
     bool zBadPending = false;
-    // "VertexVelocity" advect only: the tet decomposition and one velocity per tet-mesh vertex
-    double* d_tetPos = nullptr; int32_t* d_tets = nullptr; double* d_vertVel = nullptr;
-    int64_t nTetVerts = 0, nTets = 0; int tetsPerCell = 0; bool haveVertVel = false;
-    double* d_vertCone = nullptr;               // cone-locate tet records (cpf_walk.h, VertexField), if the decomposition admits them
-    double* d_vertApex = nullptr;               // ... and the cells' apexes
-    bool vertexFast = true;                     // cpf_set_option("vertex_fast")
-    std::string vertConeWhy;                    // why the tables were not built (cpf_step_kernel_name says so)
-    // asynchronous output (cpf_write_vtu_async): one frame in flight
-    std::thread writer;
-    bool writerLive = false;
-    int writerStatus = CPF_OK;
-    // the frame's snapshot: packed in particle-id order on the compute stream into `snapDev`, copied to pinned host memory on
-    // `ioStream` behind an event, read by the worker thread only -- the step loop's stream never waits for PCIe (round 6)
-    void* snapDev = nullptr; void* snapHost = nullptr;
-    size_t snapBytes = 0;
-    hipStream_t ioStream = nullptr;
-    hipEvent_t evSnap = nullptr, evCopied = nullptr;
-    double frameKE = 0.0;                       // of the frame the worker wrote last (valid after its join)
-    std::mutex keMutex; std::condition_variable keCv; bool keReady = false;
-    // timing
-    int timingStride = 1;                       // "timing_stride": bracket every k-th step launch only
-    uint64_t timingLaunch = 0;
-    bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-    std::vector<hipEvent_t> eventPool;
+    DevBuf<unsigned> grab;                      // the streaming kernel's chunk counters ...
+    DevBuf<double> hitSpill;                    // ... and the overflow area of its hit pool: StreamState views them
+    cpf::StreamState streamState;               // chunk counter + tuning of the streaming step kernel
+    uint32_t stepCounter = 0;
+    uint32_t lastSortStep = 0;
+    int64_t lastStepN = -1;                     // particle count of the most recent step launch (cpf_step_kernel_name)
+    int lastStepCycles = 1;                     // ... and its cycles per launch
+    bool lastStepZSettled = false;              // what the most recent cpf_step_dev left behind on ITS arrays (cpf_shard.cpp)
 };
 
 namespace {
@@ -151,65 +217,50 @@ int fail(const cpf_context* ctx, int code, const std::string& msg) {
 #define CPF_REQUIRE(ctx, cond, code, msg) \
     do { if (!(cond)) return fail(ctx, code, msg); } while (0)
 
-template <typename T>
-void freeDev(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
+// What kind of mesh the tables describe: all-hex, and for any other mesh whose cells have records (`records`) which kinds of
+// record can turn up -- 0: none, 1: padded ones only, 2: two-record and / or header cells too (cpf_walk.h "cell records")
+bool isAllHex(const cpf::HostTables& t) { return t.minCellFaces == 6 && t.maxCellFaces == 6 && t.nGroups() == 0; }
+int mixedKind(const cpf::HostTables& t, bool records) { return (records && !isAllHex(t)) ? (t.nBigCells > 0 ? 2 : 1) : 0; }
+// a mesh that is not all-hex gets records where at most a quarter of its cells have more than TWELVE slots ("mixed_records")
+bool mixedRecordsFit(const cpf::HostTables& t) { return t.nHugeCells * 4 <= t.nCells; }
 
 cpf::MeshView meshView(const cpf_context* c) {
     cpf::MeshView m;
-    m.cellOff = c->d_cellOff; m.planes = c->d_planes; m.nbr = c->d_nbr; m.U = c->d_U;
-    m.groupOff = c->d_groupOff; m.groupNbr = c->d_groupNbr;
-    m.cellRec = c->d_cellRec;
-    m.boxRec = c->boxRecords ? reinterpret_cast<const double4*>(c->d_boxRec) : nullptr;
-    m.nCells = (int32_t)c->host.nCells;
-    m.allHex = (c->host.minCellFaces == 6 && c->host.maxCellFaces == 6 && c->host.nGroups() == 0) ? 1 : 0;
-    m.zPairLast = c->host.zPairLast ? 1 : 0;
-    m.zThin = (c->host.zThin && c->zFold) ? 1 : 0;
-    m.zSide0 = c->host.zSide0 ? 1 : 0;
-    m.mixed = (c->d_cellRec && !m.allHex) ? (c->host.nBigCells > 0 ? 2 : 1) : 0;      // 2: two-record and / or header cells
+    m.cellOff = c->mesh.cellOff; m.planes = c->mesh.planes; m.nbr = c->mesh.nbr; m.U = c->mesh.U;
+    m.groupOff = c->mesh.groupOff; m.groupNbr = c->mesh.groupNbr;
+    m.cellRec = c->mesh.cellRec;
+    m.boxRec = c->boxRecords ? reinterpret_cast<const double4*>(c->mesh.boxRec.get()) : nullptr;
+    m.nCells = (int32_t)c->mesh.host.nCells;
+    m.allHex = isAllHex(c->mesh.host) ? 1 : 0;
+    m.zPairLast = c->mesh.host.zPairLast ? 1 : 0;
+    m.zThin = (c->mesh.host.zThin && c->zFold) ? 1 : 0;
+    m.zSide0 = c->mesh.host.zSide0 ? 1 : 0;
+    m.mixed = mixedKind(c->mesh.host, c->mesh.cellRec != nullptr);
     return m;
 }
 cpf::GridView gridView(const cpf_context* c) {
     cpf::GridView g;
     for (int k = 0; k < 3; ++k) {
-        g.origin[k] = c->host.origin[k]; g.invBin[k] = c->host.invBin[k];
-        g.lo[k] = c->host.lo[k]; g.hi[k] = c->host.hi[k]; g.dims[k] = c->host.dims[k];
+        g.origin[k] = c->mesh.host.origin[k]; g.invBin[k] = c->mesh.host.invBin[k];
+        g.lo[k] = c->mesh.host.lo[k]; g.hi[k] = c->mesh.host.hi[k]; g.dims[k] = c->mesh.host.dims[k];
     }
-    g.binOff = c->d_binOff; g.binCells = c->d_binCells;
+    g.binOff = c->mesh.binOff; g.binCells = c->mesh.binCells;
     return g;
 }
 
 int ensureScratch(cpf_context* ctx, size_t bytes) {
     if (bytes <= ctx->scratchBytes) return CPF_OK;
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    freeDev(ctx->scratch);
     ctx->scratchBytes = 0;
-    CPF_HIP(ctx, hipMalloc(&ctx->scratch, bytes));
+    CPF_HIP(ctx, ctx->scratch.alloc(bytes));
     ctx->scratchBytes = bytes;
     return CPF_OK;
 }
 
 int sortEndBit(const cpf_context* ctx) {
     int bits = 1;
-    while (((int64_t)1 << bits) < ctx->host.nCells + 2) ++bits;   // the all-ones key of lost/frozen sorts last
-    return std::min(bits + ctx->host.subBits[0] + ctx->host.subBits[1] + ctx->host.subBits[2], 32);  // + sub-cell bits
-}
-
-void freeMesh(cpf_context* c) {
-    freeDev(c->d_cellOff); freeDev(c->d_planes); freeDev(c->d_nbr); freeDev(c->d_groupOff); freeDev(c->d_groupNbr); freeDev(c->d_U); freeDev(c->d_U3); freeDev(c->d_cellRec); freeDev(c->d_boxRec); freeDev(c->d_cellBox); freeDev(c->d_curveRank);
-    freeDev(c->d_binOff); freeDev(c->d_binCells);
-    c->haveMesh = c->haveU = false; c->meshBytes = 0;
-    c->nSecondRecords = 0;
-    freeDev(c->d_parentOf); freeDev(c->d_Uparent);
-    c->first.clear(); c->nParent = 0; c->quality = cpf_mesh_quality{};
-    // the tet decomposition of the "VertexVelocity" mode belongs to the mesh it was made for (cpf_set_tets checks it against
-    // that mesh's cell count): a new mesh starts without one
-    freeDev(c->d_tetPos); freeDev(c->d_tets); freeDev(c->d_vertVel);
-    c->haveVertVel = false; c->nTets = c->nTetVerts = 0; c->tetsPerCell = 0;
-}
-void freeCloud(cpf_context* c) {
-    freeDev(c->x); freeDev(c->y); freeDev(c->z); freeDev(c->vel); freeDev(c->cell); freeDev(c->gid);
-    freeDev(c->x2); freeDev(c->y2); freeDev(c->z2); freeDev(c->cell2); freeDev(c->gid2);
-    c->cap = c->n = 0; c->located = false; c->zSettled = false;
+    while (((int64_t)1 << bits) < ctx->mesh.host.nCells + 2) ++bits;   // the all-ones key of lost/frozen sorts last
+    return std::min(bits + ctx->mesh.host.subBits[0] + ctx->mesh.host.subBits[1] + ctx->mesh.host.subBits[2], 32);  // + sub-cell bits
 }
 
 cpf_mesh_quality toQuality(const cpf::MeshQuality& q, int64_t nDerived) {
@@ -256,44 +307,46 @@ int setMeshImpl(cpf_context* ctx, const double* points, int64_t nPoints, const L
     if (!why.empty()) return fail(ctx, CPF_ERR_MESH, "cpf_set_mesh: " + why);
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    freeMesh(ctx);
+    ctx->mesh = Mesh{};
+    ctx->tet = TetField{};
     ctx->streamState.flatField = false;
-    ctx->host = std::move(t);
-    ctx->nParent = nCells;
-    ctx->quality = toQuality(q, ctx->host.nCells);
-    nCells = ctx->host.nCells;                         // from here on: the cells the walk runs on
-    const cpf::HostTables& h = ctx->host;
-    auto up = [&](auto*& dptr, const void* src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc((void**)&dptr, std::max<size_t>(bytes, 16));
+    ctx->mesh.host = std::move(t);
+    ctx->mesh.nParent = nCells;
+    ctx->mesh.quality = toQuality(q, ctx->mesh.host.nCells);
+    nCells = ctx->mesh.host.nCells;                         // from here on: the cells the walk runs on
+    const cpf::HostTables& h = ctx->mesh.host;
+    auto up = [&](auto& buf, const auto& src) -> hipError_t {      // (planes: four doubles of `src` per element of `buf`)
+        const size_t bytes = src.size() * sizeof(src[0]);
+        hipError_t e = buf.alloc(bytes / sizeof(*buf.get()));
         if (e != hipSuccess) return e;
-        ctx->meshBytes += bytes;
-        return hipMemcpy(dptr, src, bytes, hipMemcpyHostToDevice);
+        ctx->mesh.bytes += bytes;
+        return hipMemcpy(buf, src.data(), bytes, hipMemcpyHostToDevice);
     };
-    CPF_HIP(ctx, up(ctx->d_cellOff, h.cellOff.data(), h.cellOff.size() * 4));
-    CPF_HIP(ctx, up(ctx->d_planes, h.planes.data(), h.planes.size() * 8));
-    CPF_HIP(ctx, up(ctx->d_nbr, h.nbr.data(), h.nbr.size() * 4));
-    CPF_HIP(ctx, up(ctx->d_groupOff, h.groupOff.data(), h.groupOff.size() * 4));
-    CPF_HIP(ctx, up(ctx->d_groupNbr, h.groupNbr.data(), h.groupNbr.size() * 4));
-    CPF_HIP(ctx, up(ctx->d_binOff, h.binOff.data(), h.binOff.size() * 4));
-    CPF_HIP(ctx, up(ctx->d_binCells, h.binCells.data(), h.binCells.size() * 4));
-    CPF_HIP(ctx, up(ctx->d_cellBox, h.cellBox.data(), h.cellBox.size() * 4));
-    CPF_HIP(ctx, up(ctx->d_curveRank, h.curveRank.data(), h.curveRank.size() * 4));
+    CPF_HIP(ctx, up(ctx->mesh.cellOff, h.cellOff));
+    CPF_HIP(ctx, up(ctx->mesh.planes, h.planes));
+    CPF_HIP(ctx, up(ctx->mesh.nbr, h.nbr));
+    CPF_HIP(ctx, up(ctx->mesh.groupOff, h.groupOff));
+    CPF_HIP(ctx, up(ctx->mesh.groupNbr, h.groupNbr));
+    CPF_HIP(ctx, up(ctx->mesh.binOff, h.binOff));
+    CPF_HIP(ctx, up(ctx->mesh.binCells, h.binCells));
+    CPF_HIP(ctx, up(ctx->mesh.cellBox, h.cellBox));
+    CPF_HIP(ctx, up(ctx->mesh.curveRank, h.curveRank));
     if (derive) {
-        ctx->first = std::move(dm.first);
-        CPF_HIP(ctx, up(ctx->d_parentOf, dm.parent.data(), dm.parent.size() * 4));
-        CPF_HIP(ctx, hipMalloc((void**)&ctx->d_Uparent, (size_t)ctx->nParent * 3 * sizeof(double)));
-        ctx->meshBytes += (size_t)ctx->nParent * 24;
+        ctx->mesh.first = std::move(dm.first);
+        CPF_HIP(ctx, up(ctx->mesh.parentOf, dm.parent));
+        CPF_HIP(ctx, ctx->mesh.Uparent.alloc((size_t)ctx->mesh.nParent * 3));
+        ctx->mesh.bytes += (size_t)ctx->mesh.nParent * 24;
     }
-    CPF_HIP(ctx, hipMalloc((void**)&ctx->d_U, (size_t)nCells * sizeof(double4)));
-    CPF_HIP(ctx, hipMalloc((void**)&ctx->d_U3, (size_t)nCells * 3 * sizeof(double)));
-    CPF_HIP(ctx, hipMemset(ctx->d_U, 0, (size_t)nCells * sizeof(double4)));
-    if (ctx->host.minCellFaces == 6 && ctx->host.maxCellFaces == 6 && ctx->host.nGroups() == 0) {
-        CPF_HIP(ctx, hipMalloc((void**)&ctx->d_cellRec, (size_t)nCells * 8 * sizeof(double4)));
-        CPF_HIP(ctx, cpf::launch_build_cell_records(ctx->stream, ctx->d_planes, ctx->d_nbr, ctx->d_U, ctx->d_cellRec, nCells));
+    CPF_HIP(ctx, ctx->mesh.U.alloc((size_t)nCells));
+    CPF_HIP(ctx, ctx->mesh.U3.alloc((size_t)nCells * 3));
+    CPF_HIP(ctx, hipMemset(ctx->mesh.U, 0, (size_t)nCells * sizeof(double4)));
+    if (isAllHex(h)) {
+        CPF_HIP(ctx, ctx->mesh.cellRec.alloc((size_t)nCells * 8));
+        CPF_HIP(ctx, cpf::launch_build_cell_records(ctx->stream, ctx->mesh.planes, ctx->mesh.nbr, ctx->mesh.U, ctx->mesh.cellRec, nCells));
         CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->meshBytes += (size_t)nCells * 256;
-        if (!h.boxRec.empty()) CPF_HIP(ctx, up(ctx->d_boxRec, h.boxRec.data(), h.boxRec.size() * 8));
-    } else if (ctx->host.nHugeCells * 4 <= nCells && ctx->mixedRecords) {
+        ctx->mesh.bytes += (size_t)nCells * 256;
+        if (!h.boxRec.empty()) CPF_HIP(ctx, up(ctx->mesh.boxRec, h.boxRec));
+    } else if (mixedRecordsFit(h) && ctx->mixedRecords) {
         // not all-hex, but at most a quarter of the cells have more than TWELVE slots: records for the streaming kernel --
         // padded where a cell has fewer than six slots, a second record for slots 6..11 of a cell with 7..12 (true polyhedra
         // keep the LDS face test: two rounds per visit), a header record + CSR walk only beyond that (cpf_walk.h "cell
@@ -301,28 +354,27 @@ int setMeshImpl(cpf_context* ctx, const double* points, int64_t nPoints, const L
         std::vector<int32_t> recB((size_t)nCells, -1);
         int64_t nSecond = 0;
         for (int64_t c = 0; c < nCells; ++c) {
-            const int nf = ctx->host.cellOff[(size_t)c + 1] - ctx->host.cellOff[(size_t)c];
+            const int nf = ctx->mesh.host.cellOff[(size_t)c + 1] - ctx->mesh.host.cellOff[(size_t)c];
             if (nf > 6 && nf <= 12) recB[(size_t)c] = (int32_t)(nCells + nSecond++);
         }
         CPF_REQUIRE(ctx, nCells + nSecond < ((int64_t)1 << 31), CPF_ERR_MESH, "cpf_set_mesh: too many cell records");
-        int32_t* d_recB = nullptr;
+        DevBuf<int32_t> d_recB;                                                 // (gone with this block on every path)
         hipError_t e = hipSuccess;
-        if (nSecond > 0) e = up(d_recB, recB.data(), recB.size() * 4);          // (freed below on every path)
-        if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_cellRec, (size_t)(nCells + nSecond) * 8 * sizeof(double4));
-        if (e == hipSuccess) e = cpf::launch_build_cell_records_mixed(ctx->stream, ctx->d_cellOff, ctx->d_planes, ctx->d_nbr, ctx->d_U, d_recB,
-                                                                      ctx->d_cellRec, nCells);
+        if (nSecond > 0) e = up(d_recB, recB);
+        if (e == hipSuccess) e = ctx->mesh.cellRec.alloc((size_t)(nCells + nSecond) * 8);
+        if (e == hipSuccess) e = cpf::launch_build_cell_records_mixed(ctx->stream, ctx->mesh.cellOff, ctx->mesh.planes, ctx->mesh.nbr, ctx->mesh.U, d_recB,
+                                                                      ctx->mesh.cellRec, nCells);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        freeDev(d_recB);
         CPF_HIP(ctx, e);
-        ctx->nSecondRecords = nSecond;
-        ctx->meshBytes += (size_t)(nCells + nSecond) * 256;
+        ctx->mesh.nSecondRecords = nSecond;
+        ctx->mesh.bytes += (size_t)(nCells + nSecond) * 256;
         // every cell an axis-aligned box although the mesh has face groups (2:1-refined boxes): box records too
-        if (!h.boxRec.empty() && nSecond == 0) CPF_HIP(ctx, up(ctx->d_boxRec, h.boxRec.data(), h.boxRec.size() * 8));
+        if (!h.boxRec.empty() && nSecond == 0) CPF_HIP(ctx, up(ctx->mesh.boxRec, h.boxRec));
     }
-    ctx->meshBytes += (size_t)nCells * (sizeof(double4) + 24);
-    ctx->haveMesh = true;
-    ctx->located = false;
-    ctx->zSettled = false;
+    ctx->mesh.bytes += (size_t)nCells * (sizeof(double4) + 24);
+    ctx->mesh.have = true;
+    ctx->cloud.located = false;
+    ctx->cloud.zSettled = false;
     if (ctx->h_occupied) ctx->h_occupied[0] = ctx->h_occupied[1] = 0;      // (what the last sort counted belonged to the old mesh)
     return CPF_OK;
 }
@@ -332,17 +384,17 @@ int setMeshImpl(cpf_context* ctx, const double* points, int64_t nPoints, const L
 namespace {
 WriterRegistry::~WriterRegistry() {
     for (cpf_context* c : live)
-        if (c->writerLive && c->writer.joinable()) { c->writer.join(); c->writerLive = false; }
+        if (c->frame.live && c->frame.thread.joinable()) { c->frame.thread.join(); c->frame.live = false; }
 }
 }  // namespace
 
 namespace cpf {
 bool vtu_binary(const cpf_context* ctx) { return ctx && ctx->vtuBinary; }
-bool context_derived(const cpf_context* ctx) { return ctx && ctx->d_parentOf != nullptr; }
+bool context_derived(const cpf_context* ctx) { return ctx && ctx->mesh.parentOf != nullptr; }
 void* context_stream(const cpf_context* ctx) { return (void*)ctx->stream; }
 int context_device(const cpf_context* ctx) { return ctx->device; }
-bool context_timing(const cpf_context* ctx) { return ctx->timing; }
-int64_t context_cells(const cpf_context* ctx) { return ctx->haveMesh ? ctx->host.nCells : 0; }
+bool context_timing(const cpf_context* ctx) { return ctx->timing.on; }
+int64_t context_cells(const cpf_context* ctx) { return ctx->mesh.have ? ctx->mesh.host.nCells : 0; }
 bool context_step_settled_z(const cpf_context* ctx) { return ctx->lastStepZSettled; }
 }  // namespace cpf
 
@@ -404,15 +456,15 @@ std::string tetFanDefect(const double* pos, const int32_t* tets, int64_t nCells,
 // U[nCells][3] (device) -> the padded field and the cell records; on a mesh that qualifies for the flat walk (cpf_walk.h) the
 // kernel also notes whether any cell has a z component, and the note is read back behind it (8 bytes, asynchronous)
 hipError_t layOutField(cpf_context* ctx, const double* dU3, int64_t nCells) {
-    const bool ask = ctx->host.zSide0 && ctx->d_occupied && ctx->h_occupied;
+    const bool ask = ctx->mesh.host.zSide0 && ctx->occupied && ctx->h_occupied;
     ctx->streamState.flatField = false;
     ctx->fieldFlagPending = false;
     hipError_t e = hipSuccess;
-    if (ask) e = hipMemsetAsync(ctx->d_occupied + 2, 0, 8, ctx->stream);
-    if (e == hipSuccess) e = cpf::launch_u3_to_u4(ctx->stream, dU3, ctx->d_U, nCells, ask ? ctx->d_occupied + 2 : nullptr);
-    if (e == hipSuccess && ctx->d_cellRec) e = cpf::launch_update_record_velocity(ctx->stream, ctx->d_U, ctx->d_cellRec, ctx->d_boxRec, nCells);
+    if (ask) e = hipMemsetAsync(ctx->occupied + 2, 0, 8, ctx->stream);
+    if (e == hipSuccess) e = cpf::launch_u3_to_u4(ctx->stream, dU3, ctx->mesh.U, nCells, ask ? ctx->occupied + 2 : nullptr);
+    if (e == hipSuccess && ctx->mesh.cellRec) e = cpf::launch_update_record_velocity(ctx->stream, ctx->mesh.U, ctx->mesh.cellRec, ctx->mesh.boxRec, nCells);
     if (e == hipSuccess && ask) {
-        e = hipMemcpyAsync(ctx->h_occupied + 2, ctx->d_occupied + 2, 8, hipMemcpyDeviceToHost, ctx->stream);
+        e = hipMemcpyAsync(ctx->h_occupied + 2, ctx->occupied + 2, 8, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipEventRecord(ctx->evFieldFlag, ctx->stream);
         ctx->fieldFlagPending = e == hipSuccess;
     }
@@ -422,16 +474,16 @@ hipError_t layOutField(cpf_context* ctx, const double* dU3, int64_t nCells) {
 // whose every plane has the point within kTol on its inner side (the walk's face test, cpf_walk.h plane_dist), or else the one
 // whose worst plane distance is smallest.  Negative codes pass through.
 std::string resolveSubCells(const cpf_context* ctx, int64_t n, const double* xyz, const int32_t* cell, std::vector<int32_t>& out) {
-    const cpf::HostTables& h = ctx->host;
+    const cpf::HostTables& h = ctx->mesh.host;
     out.resize((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         const int32_t c = cell[i];
         if (c < 0) { out[(size_t)i] = c; continue; }
-        if (c >= ctx->nParent) return "cell[" + std::to_string(i) + "] = " + std::to_string(c) + " is not a cell of the mesh";
+        if (c >= ctx->mesh.nParent) return "cell[" + std::to_string(i) + "] = " + std::to_string(c) + " is not a cell of the mesh";
         const double px = xyz[3 * i], py = xyz[3 * i + 1], pz = xyz[3 * i + 2];
-        int32_t pick = ctx->first[(size_t)c];
+        int32_t pick = ctx->mesh.first[(size_t)c];
         double pickWorst = HUGE_VAL;
-        for (int32_t d = ctx->first[(size_t)c]; d < ctx->first[(size_t)c + 1]; ++d) {
+        for (int32_t d = ctx->mesh.first[(size_t)c]; d < ctx->mesh.first[(size_t)c + 1]; ++d) {
             double worst = -HUGE_VAL;
             for (int32_t s = h.cellOff[(size_t)d]; s < h.cellOff[(size_t)d + 1]; ++s) {
                 const double* pl = &h.planes[4 * (size_t)s];
@@ -462,6 +514,23 @@ bool zBadArrived(cpf_context* ctx) {
 void pollFieldFlag(cpf_context* ctx) {
     if (ctx->fieldFlagPending && hipEventQuery(ctx->evFieldFlag) == hipSuccess) fieldFlagArrived(ctx);
 }
+// how many of ids[0 .. n) are negative, read back (synchronises the stream); counted in the counters' scratch words
+int countNegative(cpf_context* ctx, const int32_t* ids, int64_t n, int64_t* out) {
+    unsigned long long* cnt = ctx->counters + cpf::kCounterSlots * 4;
+    CPF_HIP(ctx, hipMemsetAsync(cnt, 0, 8, ctx->stream));
+    CPF_HIP(ctx, cpf::launch_count_negative(ctx->stream, ids, n, cnt));
+    unsigned long long h = 0;
+    CPF_HIP(ctx, hipMemcpyAsync(&h, cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *out = (int64_t)h;
+    return CPF_OK;
+}
+// cpf::launch_pack_by_gid's three outputs for n particles in one buffer: xyzw[n][4] at 0, cell[n] at offC, vel[n][4] at offV
+struct PackLayout {
+    size_t offC, offV, bytes;
+    static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
+    explicit PackLayout(size_t n) : offC(al(n * 32)), offV(offC + al(n * 4)), bytes(offV + al(n * 32)) {}
+};
 }  // namespace
 
 extern "C" {
@@ -482,19 +551,20 @@ int cpf_create(int device, cpf_context** out) {
     cpf_context* ctx = new (std::nothrow) cpf_context();
     if (!ctx) return fail(nullptr, CPF_ERR_NOMEM, "cpf_create: out of host memory");
     ctx->device = device;
-    e = hipStreamCreateWithFlags(&ctx->ownStream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_counters, (cpf::kCounterSlots * 4 + 4) * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(ctx->d_counters, 0, (cpf::kCounterSlots * 4 + 4) * sizeof(unsigned long long));
+    e = ctx->ownStream.create(hipStreamNonBlocking);
+    if (e == hipSuccess) e = ctx->counters.alloc(cpf::kCounterSlots * 4 + 4);
+    if (e == hipSuccess) e = hipMemset(ctx->counters, 0, (cpf::kCounterSlots * 4 + 4) * sizeof(unsigned long long));
     // ([2]: "the velocity field has a z component", written by the kernel that lays the field out -- the flat walk)
-    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_occupied, 32);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&ctx->h_occupied, 32, hipHostMallocDefault);
+    if (e == hipSuccess) e = ctx->occupied.alloc(4);
+    if (e == hipSuccess) e = ctx->h_occupied.alloc(4);
     if (e == hipSuccess) { ctx->h_occupied[0] = ctx->h_occupied[1] = 0; ctx->h_occupied[2] = 1; ctx->streamState.occupiedHost = ctx->h_occupied; }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->evFieldFlag, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&ctx->h_zBad, 64, hipHostMallocDefault);
+    if (e == hipSuccess) e = ctx->evFieldFlag.create(hipEventDisableTiming);
+    if (e == hipSuccess) e = ctx->h_zBad.alloc(16);
     if (e == hipSuccess) { *ctx->h_zBad = 0u; ctx->streamState.zBad = ctx->h_zBad; }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->evZBad, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void**)&ctx->streamState.d_grab, cpf::kStreamGrabBytes);
-    if (e == hipSuccess) e = hipMemset(ctx->streamState.d_grab, 0, cpf::kStreamGrabBytes);
+    if (e == hipSuccess) e = ctx->evZBad.create(hipEventDisableTiming);
+    if (e == hipSuccess) e = ctx->grab.alloc(cpf::kStreamGrabBytes / sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemset(ctx->grab, 0, cpf::kStreamGrabBytes);
+    if (e == hipSuccess) ctx->streamState.d_grab = ctx->grab;
     if (e == hipSuccess) {
         int cus = 0;
         e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
@@ -503,12 +573,11 @@ int cpf_create(int device, cpf_context** out) {
     if (e == hipSuccess) {
         // overflow area of the streaming kernel's per-wave pool of wall hit points: 1.5 KB per wave slot the chip can hold
         ctx->streamState.hitSpillWaves = 32 * ctx->streamState.numCU;
-        e = hipMalloc((void**)&ctx->streamState.d_hitSpill,
-                      (size_t)ctx->streamState.hitSpillWaves * cpf::kStreamHitSpillDoubles * sizeof(double));
+        e = ctx->hitSpill.alloc((size_t)ctx->streamState.hitSpillWaves * cpf::kStreamHitSpillDoubles);
+        if (e == hipSuccess) ctx->streamState.d_hitSpill = ctx->hitSpill;
     }
     if (e != hipSuccess) {
         std::string m = std::string("cpf_create: ") + hipGetErrorString(e);
-        if (ctx->ownStream) (void)hipStreamDestroy(ctx->ownStream);
         delete ctx;
         return fail(nullptr, CPF_ERR_HIP, m);
     }
@@ -522,22 +591,6 @@ int cpf_destroy(cpf_context* ctx) {
     (void)cpf_write_vtu_wait(ctx);                                             // never lose a frame
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    freeMesh(ctx); freeCloud(ctx);
-    freeDev(ctx->scratch); freeDev(ctx->d_counters); freeDev(ctx->streamState.d_grab); freeDev(ctx->streamState.d_hitSpill);
-    freeDev(ctx->d_occupied);
-    if (ctx->evFieldFlag) { (void)hipEventDestroy(ctx->evFieldFlag); ctx->evFieldFlag = nullptr; }
-    if (ctx->h_occupied) { (void)hipHostFree(ctx->h_occupied); ctx->h_occupied = nullptr; ctx->streamState.occupiedHost = nullptr; }
-    if (ctx->evZBad) { (void)hipEventDestroy(ctx->evZBad); ctx->evZBad = nullptr; }
-    if (ctx->h_zBad) { (void)hipHostFree(ctx->h_zBad); ctx->h_zBad = nullptr; ctx->streamState.zBad = nullptr; }
-    freeDev(ctx->d_tetPos); freeDev(ctx->d_tets); freeDev(ctx->d_vertVel); freeDev(ctx->d_vertCone); freeDev(ctx->d_vertApex);
-    freeDev(ctx->snapDev);
-    if (ctx->snapHost) { (void)hipHostFree(ctx->snapHost); ctx->snapHost = nullptr; }
-    if (ctx->evSnap) (void)hipEventDestroy(ctx->evSnap);
-    if (ctx->evCopied) (void)hipEventDestroy(ctx->evCopied);
-    if (ctx->ioStream) (void)hipStreamDestroy(ctx->ioStream);
-    for (auto& p : ctx->events) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-    for (auto& ev : ctx->eventPool) (void)hipEventDestroy(ev);
-    if (ctx->ownStream) (void)hipStreamDestroy(ctx->ownStream);
     delete ctx;
     return CPF_OK;
 }
@@ -583,71 +636,72 @@ int cpf_set_mesh_l64(cpf_context* ctx, const double* points, int64_t nPoints, co
                                 nCells);
 }
 
+}  // extern "C"
+namespace {
+// The *_host entry points (no context, no GPU): the mesh arrays and whatever else must not be null (`more`) checked, then
+// `body` under the guard against a host that runs out of memory.  hostTables: ... with the mesh's tables built for `use`.
+template <typename Body>
+int hostMesh(const double* points, const int32_t* faceOffsets, const int32_t* faceVerts, const int32_t* owner,
+             const int32_t* neighbour, int64_t nInternal, bool more, Body body) {
+    if (!points || !faceOffsets || !faceVerts || !owner || (!neighbour && nInternal != 0) || !more) return CPF_ERR_ARG;
+    try { return body(); } catch (const std::bad_alloc&) { return CPF_ERR_NOMEM; }
+}
+template <typename Use>
+int hostTables(const double* points, int64_t nPoints, const int32_t* faceOffsets, const int32_t* faceVerts, int64_t nFaces,
+               const int32_t* owner, const int32_t* neighbour, int64_t nInternal, int64_t nCells, Use use) {
+    return hostMesh(points, faceOffsets, faceVerts, owner, neighbour, nInternal, true, [&] {
+        cpf::HostTables t;
+        if (!cpf::build_tables<int32_t>(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal, nCells, t).empty())
+            return CPF_ERR_MESH;
+        use(t);
+        return CPF_OK;
+    });
+}
+}  // namespace
+extern "C" {
+
 int cpf_build_mesh_tables_host(const double* points, int64_t nPoints, const int32_t* faceOffsets, const int32_t* faceVerts,
                                int64_t nFaces, const int32_t* owner, const int32_t* neighbour, int64_t nInternal, int64_t nCells,
                                int64_t* nSlots, int64_t* nGroups, int64_t* nMembers, int32_t* cellOff, double* planes,
                                int32_t* nbr, int32_t* groupOff, int32_t* groupNbr) {
-    if (!points || !faceOffsets || !faceVerts || !owner || (!neighbour && nInternal != 0)) return CPF_ERR_ARG;
-    cpf::HostTables t;
-    try {
-        const std::string why = cpf::build_tables<int32_t>(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal, nCells, t);
-        if (!why.empty()) return CPF_ERR_MESH;
-    } catch (const std::bad_alloc&) {
-        return CPF_ERR_NOMEM;
-    }
-    const int64_t g = t.nGroups(), mem = t.groupOff[(size_t)g];
-    if (nSlots) *nSlots = t.nSlots;
-    if (nGroups) *nGroups = g;
-    if (nMembers) *nMembers = mem;
-    if (cellOff) std::memcpy(cellOff, t.cellOff.data(), t.cellOff.size() * 4);
-    if (planes) std::memcpy(planes, t.planes.data(), t.planes.size() * 8);
-    if (nbr) std::memcpy(nbr, t.nbr.data(), t.nbr.size() * 4);
-    if (groupOff) std::memcpy(groupOff, t.groupOff.data(), (size_t)(g + 1) * 4);
-    if (groupNbr) std::memcpy(groupNbr, t.groupNbr.data(), (size_t)mem * 4);
-    return CPF_OK;
+    return hostTables(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal, nCells, [&](const cpf::HostTables& t) {
+        const int64_t g = t.nGroups(), mem = t.groupOff[(size_t)g];
+        if (nSlots) *nSlots = t.nSlots;
+        if (nGroups) *nGroups = g;
+        if (nMembers) *nMembers = mem;
+        if (cellOff) std::memcpy(cellOff, t.cellOff.data(), t.cellOff.size() * 4);
+        if (planes) std::memcpy(planes, t.planes.data(), t.planes.size() * 8);
+        if (nbr) std::memcpy(nbr, t.nbr.data(), t.nbr.size() * 4);
+        if (groupOff) std::memcpy(groupOff, t.groupOff.data(), (size_t)(g + 1) * 4);
+        if (groupNbr) std::memcpy(groupNbr, t.groupNbr.data(), (size_t)mem * 4);
+    });
 }
 
 int cpf_mesh_flags_host(const double* points, int64_t nPoints, const int32_t* faceOffsets, const int32_t* faceVerts,
                         int64_t nFaces, const int32_t* owner, const int32_t* neighbour, int64_t nInternal, int64_t nCells,
                         int32_t* allHex, int32_t* zLayered, int32_t* zThin, int32_t* mixed) {
-    if (!points || !faceOffsets || !faceVerts || !owner || (!neighbour && nInternal != 0)) return CPF_ERR_ARG;
-    cpf::HostTables t;
-    try {
-        const std::string why = cpf::build_tables<int32_t>(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal, nCells, t);
-        if (!why.empty()) return CPF_ERR_MESH;
-    } catch (const std::bad_alloc&) {
-        return CPF_ERR_NOMEM;
-    }
-    // (as meshView() derives them from a context's tables, with the default options)
-    const bool hex = t.minCellFaces == 6 && t.maxCellFaces == 6 && t.nGroups() == 0;
-    if (allHex) *allHex = hex ? 1 : 0;
-    if (zLayered) *zLayered = t.zPairLast ? 1 : 0;
-    if (zThin) *zThin = t.zThin ? 1 : 0;
-    if (mixed) *mixed = hex ? 0 : (t.nHugeCells * 4 <= nCells ? (t.nBigCells > 0 ? 2 : 1) : 0);
-    return CPF_OK;
+    return hostTables(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal, nCells, [&](const cpf::HostTables& t) {
+        // (what a context with the default options reports for this mesh: cpf_get_mesh_flags)
+        if (allHex) *allHex = isAllHex(t) ? 1 : 0;
+        if (zLayered) *zLayered = t.zPairLast ? 1 : 0;
+        if (zThin) *zThin = t.zThin ? 1 : 0;
+        if (mixed) *mixed = mixedKind(t, mixedRecordsFit(t));
+    });
 }
 
 int cpf_mesh_box_records_host(const double* points, int64_t nPoints, const int32_t* faceOffsets, const int32_t* faceVerts,
                               int64_t nFaces, const int32_t* owner, const int32_t* neighbour, int64_t nInternal, int64_t nCells,
                               int32_t* isBox, double* boxRec) {
-    if (!points || !faceOffsets || !faceVerts || !owner || (!neighbour && nInternal != 0)) return CPF_ERR_ARG;
-    cpf::HostTables t;
-    try {
-        const std::string why = cpf::build_tables<int32_t>(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal, nCells, t);
-        if (!why.empty()) return CPF_ERR_MESH;
-    } catch (const std::bad_alloc&) {
-        return CPF_ERR_NOMEM;
-    }
-    if (isBox) *isBox = t.boxRec.empty() ? 0 : 1;
-    if (boxRec && !t.boxRec.empty()) std::memcpy(boxRec, t.boxRec.data(), t.boxRec.size() * 8);
-    return CPF_OK;
+    return hostTables(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal, nCells, [&](const cpf::HostTables& t) {
+        if (isBox) *isBox = t.boxRec.empty() ? 0 : 1;
+        if (boxRec && !t.boxRec.empty()) std::memcpy(boxRec, t.boxRec.data(), t.boxRec.size() * 8);
+    });
 }
 
 int cpf_mesh_quality_host(const double* points, int64_t nPoints, const int32_t* faceOffsets, const int32_t* faceVerts,
                           int64_t nFaces, const int32_t* owner, const int32_t* neighbour, int64_t nInternal, int64_t nCells,
                           double tol, int split, cpf_mesh_quality* out) {
-    if (!points || !faceOffsets || !faceVerts || !owner || (!neighbour && nInternal != 0) || !out || !(tol > 0.0)) return CPF_ERR_ARG;
-    try {
+    return hostMesh(points, faceOffsets, faceVerts, owner, neighbour, nInternal, out && tol > 0.0, [&] {
         cpf::MeshQuality q;
         if (!cpf::measure_mesh<int32_t>(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal, nCells, tol, q).empty())
             return CPF_ERR_MESH;
@@ -659,18 +713,15 @@ int cpf_mesh_quality_host(const double* points, int64_t nPoints, const int32_t* 
             nDerived = dm.nCells;
         }
         *out = toQuality(q, nDerived);
-    } catch (const std::bad_alloc&) {
-        return CPF_ERR_NOMEM;
-    }
-    return CPF_OK;
+        return CPF_OK;
+    });
 }
 
 int cpf_build_derived_mesh_host(const double* points, int64_t nPoints, const int32_t* faceOffsets, const int32_t* faceVerts,
                                 int64_t nFaces, const int32_t* owner, const int32_t* neighbour, int64_t nInternal, int64_t nCells,
                                 double tol, int64_t sizes[5], double* pointsOut, int32_t* faceOffOut, int32_t* faceVertsOut,
                                 int32_t* ownerOut, int32_t* neighbourOut, int32_t* first) {
-    if (!points || !faceOffsets || !faceVerts || !owner || (!neighbour && nInternal != 0) || !sizes || !(tol > 0.0)) return CPF_ERR_ARG;
-    try {
+    return hostMesh(points, faceOffsets, faceVerts, owner, neighbour, nInternal, sizes && tol > 0.0, [&] {
         cpf::MeshQuality q;
         if (!cpf::measure_mesh<int32_t>(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal, nCells, tol, q).empty())
             return CPF_ERR_MESH;
@@ -683,42 +734,40 @@ int cpf_build_derived_mesh_host(const double* points, int64_t nPoints, const int
         if (pointsOut) std::memcpy(pointsOut, dm.points.data(), dm.points.size() * 8);
         narrow(dm.faceOff, faceOffOut); narrow(dm.faceVerts, faceVertsOut); narrow(dm.owner, ownerOut); narrow(dm.neighbour, neighbourOut);
         if (first) std::memcpy(first, dm.first.data(), dm.first.size() * 4);
-    } catch (const std::bad_alloc&) {
-        return CPF_ERR_NOMEM;
-    }
-    return CPF_OK;
+        return CPF_OK;
+    });
 }
 
 int cpf_get_mesh_quality(const cpf_context* ctx, cpf_mesh_quality* out) {
     CPF_REQUIRE(ctx, ctx && out, CPF_ERR_ARG, "null argument");
-    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_get_mesh_quality: call cpf_set_mesh first");
-    *out = ctx->quality;
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_get_mesh_quality: call cpf_set_mesh first");
+    *out = ctx->mesh.quality;
     return CPF_OK;
 }
 
 int cpf_cells_to_parent_dev(cpf_context* ctx, const int32_t* in, int32_t* out, int64_t n) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_cells_to_parent_dev: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_cells_to_parent_dev: call cpf_set_mesh first");
     CPF_REQUIRE(ctx, n >= 0 && (n == 0 || (in && out)), CPF_ERR_ARG, "cpf_cells_to_parent_dev: bad arguments");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->d_parentOf) CPF_HIP(ctx, cpf::launch_cells_to_parent(ctx->stream, in, out, ctx->d_parentOf, n, ctx->host.nCells));
+    if (ctx->mesh.parentOf) CPF_HIP(ctx, cpf::launch_cells_to_parent(ctx->stream, in, out, ctx->mesh.parentOf, n, ctx->mesh.host.nCells));
     else if (n > 0 && in != out) CPF_HIP(ctx, hipMemcpyAsync(out, in, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
     return CPF_OK;
 }
 
 int cpf_mesh_info(const cpf_context* ctx, int64_t* nCells, int64_t* nSlots, int64_t* deviceBytes) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_mesh_info: no mesh set");
-    if (nCells) *nCells = ctx->host.nCells;
-    if (nSlots) *nSlots = ctx->host.nSlots;
-    if (deviceBytes) *deviceBytes = (int64_t)ctx->meshBytes;
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_mesh_info: no mesh set");
+    if (nCells) *nCells = ctx->mesh.host.nCells;
+    if (nSlots) *nSlots = ctx->mesh.host.nSlots;
+    if (deviceBytes) *deviceBytes = (int64_t)ctx->mesh.bytes;
     return CPF_OK;
 }
 
 int cpf_get_mesh_tables(const cpf_context* ctx, int32_t* cellOff, double* planes, int32_t* nbr) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_get_mesh_tables: no mesh set");
-    const cpf::HostTables& h = ctx->host;
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_get_mesh_tables: no mesh set");
+    const cpf::HostTables& h = ctx->mesh.host;
     if (cellOff) std::memcpy(cellOff, h.cellOff.data(), h.cellOff.size() * 4);
     if (planes) std::memcpy(planes, h.planes.data(), h.planes.size() * 8);
     if (nbr) std::memcpy(nbr, h.nbr.data(), h.nbr.size() * 4);
@@ -727,8 +776,8 @@ int cpf_get_mesh_tables(const cpf_context* ctx, int32_t* cellOff, double* planes
 
 int cpf_get_mesh_groups(const cpf_context* ctx, int64_t* nGroups, int64_t* nMembers, int32_t* groupOff, int32_t* groupNbr) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_get_mesh_groups: no mesh set");
-    const cpf::HostTables& h = ctx->host;
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_get_mesh_groups: no mesh set");
+    const cpf::HostTables& h = ctx->mesh.host;
     const int64_t g = h.nGroups();
     if (nGroups) *nGroups = g;
     if (nMembers) *nMembers = h.groupOff[(size_t)g];
@@ -739,7 +788,7 @@ int cpf_get_mesh_groups(const cpf_context* ctx, int64_t* nGroups, int64_t* nMemb
 
 int cpf_get_mesh_flags(const cpf_context* ctx, int32_t* allHex, int32_t* zLayered, int32_t* zThin, int32_t* mixed) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_get_mesh_flags: no mesh set");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_get_mesh_flags: no mesh set");
     const cpf::MeshView m = meshView(ctx);
     if (allHex) *allHex = m.allHex;
     if (zLayered) *zLayered = m.zPairLast;
@@ -750,33 +799,33 @@ int cpf_get_mesh_flags(const cpf_context* ctx, int32_t* allHex, int32_t* zLayere
 
 int cpf_set_velocity(cpf_context* ctx, const double* U, int64_t nCells) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_set_velocity: call cpf_set_mesh first");
-    CPF_REQUIRE(ctx, U && nCells == ctx->nParent, CPF_ERR_ARG, "cpf_set_velocity: U is null or nCells differs from the mesh");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_set_velocity: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, U && nCells == ctx->mesh.nParent, CPF_ERR_ARG, "cpf_set_velocity: U is null or nCells differs from the mesh");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->d_parentOf) {                             // per parent cell -> every derived cell of it
-        CPF_HIP(ctx, hipMemcpyAsync(ctx->d_Uparent, U, (size_t)nCells * 24, hipMemcpyHostToDevice, ctx->stream));
-        CPF_HIP(ctx, cpf::launch_gather_parent_u3(ctx->stream, ctx->d_Uparent, ctx->d_parentOf, ctx->d_U3, ctx->host.nCells));
+    if (ctx->mesh.parentOf) {                             // per parent cell -> every derived cell of it
+        CPF_HIP(ctx, hipMemcpyAsync(ctx->mesh.Uparent, U, (size_t)nCells * 24, hipMemcpyHostToDevice, ctx->stream));
+        CPF_HIP(ctx, cpf::launch_gather_parent_u3(ctx->stream, ctx->mesh.Uparent, ctx->mesh.parentOf, ctx->mesh.U3, ctx->mesh.host.nCells));
     } else {
-        CPF_HIP(ctx, hipMemcpyAsync(ctx->d_U3, U, (size_t)nCells * 24, hipMemcpyHostToDevice, ctx->stream));
+        CPF_HIP(ctx, hipMemcpyAsync(ctx->mesh.U3, U, (size_t)nCells * 24, hipMemcpyHostToDevice, ctx->stream));
     }
-    CPF_HIP(ctx, layOutField(ctx, ctx->d_U3, ctx->host.nCells));
+    CPF_HIP(ctx, layOutField(ctx, ctx->mesh.U3, ctx->mesh.host.nCells));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));   // U may be pageable host memory owned by the caller
     fieldFlagArrived(ctx);
-    ctx->haveU = true;
+    ctx->mesh.haveU = true;
     return CPF_OK;
 }
 
 int cpf_set_velocity_dev(cpf_context* ctx, const double* dU, int64_t nCells) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_set_velocity_dev: call cpf_set_mesh first");
-    CPF_REQUIRE(ctx, dU && nCells == ctx->nParent, CPF_ERR_ARG, "cpf_set_velocity_dev: bad arguments");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_set_velocity_dev: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, dU && nCells == ctx->mesh.nParent, CPF_ERR_ARG, "cpf_set_velocity_dev: bad arguments");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->d_parentOf) {                             // per parent cell -> every derived cell of it
-        CPF_HIP(ctx, cpf::launch_gather_parent_u3(ctx->stream, dU, ctx->d_parentOf, ctx->d_U3, ctx->host.nCells));
-        dU = ctx->d_U3;
+    if (ctx->mesh.parentOf) {                             // per parent cell -> every derived cell of it
+        CPF_HIP(ctx, cpf::launch_gather_parent_u3(ctx->stream, dU, ctx->mesh.parentOf, ctx->mesh.U3, ctx->mesh.host.nCells));
+        dU = ctx->mesh.U3;
     }
-    CPF_HIP(ctx, layOutField(ctx, dU, ctx->host.nCells));   // (asynchronous: the flat walk waits until the flag has been seen to arrive)
-    ctx->haveU = true;
+    CPF_HIP(ctx, layOutField(ctx, dU, ctx->mesh.host.nCells));   // (asynchronous: the flat walk waits until the flag has been seen to arrive)
+    ctx->mesh.haveU = true;
     return CPF_OK;
 }
 
@@ -785,60 +834,56 @@ int cpf_alloc_particles(cpf_context* ctx, int64_t capacity) {
     CPF_REQUIRE(ctx, capacity > 0 && capacity < ((int64_t)1 << 31), CPF_ERR_ARG, "cpf_alloc_particles: capacity must be in (0, 2^31)");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    freeCloud(ctx);
+    ctx->cloud = Cloud{};
     const size_t c = (size_t)capacity;
-    CPF_HIP(ctx, hipMalloc((void**)&ctx->x, c * 8));
-    CPF_HIP(ctx, hipMalloc((void**)&ctx->y, c * 8));
-    CPF_HIP(ctx, hipMalloc((void**)&ctx->z, c * 8));
-    CPF_HIP(ctx, hipMalloc((void**)&ctx->vel, c * 24));
-    CPF_HIP(ctx, hipMalloc((void**)&ctx->cell, c * 4));
-    CPF_HIP(ctx, hipMalloc((void**)&ctx->gid, c * 8));
-    CPF_HIP(ctx, hipMemsetAsync(ctx->vel, 0, c * 24, ctx->stream));          // src/initCuda.H:148-149
-    CPF_HIP(ctx, hipMemsetAsync(ctx->cell, 0xFF, c * 4, ctx->stream));       // -1, src/initCuda.H:145
-    ctx->cap = capacity;
+    CPF_HIP(ctx, ctx->cloud.cur.alloc(c));
+    CPF_HIP(ctx, ctx->cloud.vel.alloc(c * 3));
+    CPF_HIP(ctx, hipMemsetAsync(ctx->cloud.vel, 0, c * 24, ctx->stream));          // src/initCuda.H:148-149
+    CPF_HIP(ctx, hipMemsetAsync(ctx->cloud.cur.cell, 0xFF, c * 4, ctx->stream));       // -1, src/initCuda.H:145
+    ctx->cloud.cap = capacity;
     return CPF_OK;
 }
 
 int cpf_seed_box(cpf_context* ctx, int64_t n, const double lower[3], const double upper[3], int order) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, lower && upper && n > 0, CPF_ERR_ARG, "cpf_seed_box: bad arguments");
-    if (ctx->cap < n) { int r = cpf_alloc_particles(ctx, n); if (r) return r; }
+    if (ctx->cloud.cap < n) { int r = cpf_alloc_particles(ctx, n); if (r) return r; }
     CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, cpf::launch_seed_box(ctx->stream, ctx->x, ctx->y, ctx->z, 0, n, lower, upper, order));
-    CPF_HIP(ctx, cpf::launch_iota64(ctx->stream, ctx->gid, n, 0));
-    CPF_HIP(ctx, hipMemsetAsync(ctx->cell, 0xFF, (size_t)n * 4, ctx->stream));
-    ctx->n = n; ctx->located = false; ctx->zSettled = false;
+    CPF_HIP(ctx, cpf::launch_seed_box(ctx->stream, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, 0, n, lower, upper, order));
+    CPF_HIP(ctx, cpf::launch_iota64(ctx->stream, ctx->cloud.cur.gid, n, 0));
+    CPF_HIP(ctx, hipMemsetAsync(ctx->cloud.cur.cell, 0xFF, (size_t)n * 4, ctx->stream));
+    ctx->cloud.n = n; ctx->cloud.located = false; ctx->cloud.zSettled = false;
     return CPF_OK;
 }
 
 int cpf_set_particles(cpf_context* ctx, int64_t n, const double* xyz, const int32_t* cell) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, xyz && n > 0, CPF_ERR_ARG, "cpf_set_particles: bad arguments");
-    if (ctx->cap < n) { int r = cpf_alloc_particles(ctx, n); if (r) return r; }
+    if (ctx->cloud.cap < n) { int r = cpf_alloc_particles(ctx, n); if (r) return r; }
     CPF_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->zSettled = false;
+    ctx->cloud.zSettled = false;
     int r = ensureScratch(ctx, (size_t)n * 24);
     if (r) return r;
     CPF_HIP(ctx, hipMemcpyAsync(ctx->scratch, xyz, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
-    CPF_HIP(ctx, cpf::launch_unpack_xyz(ctx->stream, (const double*)ctx->scratch, ctx->x, ctx->y, ctx->z, n));
-    CPF_HIP(ctx, cpf::launch_iota64(ctx->stream, ctx->gid, n, 0));
+    CPF_HIP(ctx, cpf::launch_unpack_xyz(ctx->stream, (const double*)ctx->scratch.get(), ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, n));
+    CPF_HIP(ctx, cpf::launch_iota64(ctx->stream, ctx->cloud.cur.gid, n, 0));
     std::vector<int32_t> sub;
-    if (cell && ctx->d_parentOf) {                     // parent cells -> the derived cell of each that holds the point
+    if (cell && ctx->mesh.parentOf) {                     // parent cells -> the derived cell of each that holds the point
         std::string why = resolveSubCells(ctx, n, xyz, cell, sub);
         if (!why.empty()) { (void)hipStreamSynchronize(ctx->stream); return fail(ctx, CPF_ERR_ARG, "cpf_set_particles: " + why); }
         cell = sub.data();
     }
-    if (cell) CPF_HIP(ctx, hipMemcpyAsync(ctx->cell, cell, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    else CPF_HIP(ctx, hipMemsetAsync(ctx->cell, 0xFF, (size_t)n * 4, ctx->stream));
+    if (cell) CPF_HIP(ctx, hipMemcpyAsync(ctx->cloud.cur.cell, cell, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    else CPF_HIP(ctx, hipMemsetAsync(ctx->cloud.cur.cell, 0xFF, (size_t)n * 4, ctx->stream));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->n = n; ctx->located = cell != nullptr;
+    ctx->cloud.n = n; ctx->cloud.located = cell != nullptr;
     return CPF_OK;
 }
 
 int cpf_locate_initial_dev(cpf_context* ctx, const double* x, const double* y, const double* z, int32_t* cell,
                            int64_t n) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_locate_initial: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_locate_initial: call cpf_set_mesh first");
     CPF_REQUIRE(ctx, n >= 0 && (n == 0 || (x && y && z && cell)), CPF_ERR_ARG, "cpf_locate_initial: null array");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, cpf::launch_locate_initial(ctx->stream, x, y, z, cell, n, meshView(ctx), gridView(ctx)));
@@ -847,46 +892,32 @@ int cpf_locate_initial_dev(cpf_context* ctx, const double* x, const double* y, c
 
 int cpf_locate_initial(cpf_context* ctx, int64_t* nOutside) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->n > 0, CPF_ERR_STATE, "cpf_locate_initial: no particles (seed or set them first)");
-    ctx->zSettled = false;                    // (a frozen particle found inside the mesh is live again, with whatever z it had)
-    int r = cpf_locate_initial_dev(ctx, ctx->x, ctx->y, ctx->z, ctx->cell, ctx->n);
+    CPF_REQUIRE(ctx, ctx->cloud.n > 0, CPF_ERR_STATE, "cpf_locate_initial: no particles (seed or set them first)");
+    ctx->cloud.zSettled = false;                    // (a frozen particle found inside the mesh is live again, with whatever z it had)
+    int r = cpf_locate_initial_dev(ctx, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell, ctx->cloud.n);
     if (r) return r;
-    ctx->located = true;
-    if (nOutside) {
-        unsigned long long* cnt = ctx->d_counters + cpf::kCounterSlots * 4;
-        CPF_HIP(ctx, hipMemsetAsync(cnt, 0, 8, ctx->stream));
-        CPF_HIP(ctx, cpf::launch_count_negative(ctx->stream, ctx->cell, ctx->n, cnt));
-        unsigned long long h = 0;
-        CPF_HIP(ctx, hipMemcpyAsync(&h, cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
-        CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        *nOutside = (int64_t)h;
-    }
-    return CPF_OK;
+    ctx->cloud.located = true;
+    return nOutside ? countNegative(ctx, ctx->cloud.cur.cell, ctx->cloud.n, nOutside) : CPF_OK;
 }
 
 // the "VertexVelocity" cycle's tables (the cone-locate records only with "vertex_fast")
 static cpf::VertexField vertexField(const cpf_context* ctx) {
-    return {ctx->d_tetPos, ctx->d_tets, ctx->d_vertVel, ctx->tetsPerCell, ctx->vertexFast ? ctx->d_vertCone : nullptr,
-            reinterpret_cast<const double4*>(ctx->d_vertApex)};
+    return {ctx->tet.pos, ctx->tet.tets, ctx->tet.vel, ctx->tet.tetsPerCell, ctx->vertexFast ? ctx->tet.cone.get() : nullptr,
+            reinterpret_cast<const double4*>(ctx->tet.apex.get())};
 }
-
-// (device-scope release is all a time stamp needs; measured against the default flags: no difference)
-#ifndef CPF_TIMING_EVENT_FLAGS
-#define CPF_TIMING_EVENT_FLAGS hipEventReleaseToDevice
-#endif
 
 int cpf_step_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cell, const int64_t* gid, double* vel,
                  int64_t n, double dt, double D, uint32_t step0, int nCycles, unsigned flags) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_step: call cpf_set_mesh first");
-    CPF_REQUIRE(ctx, ctx->haveU, CPF_ERR_STATE, "cpf_step: call cpf_set_velocity first");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_step: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->mesh.haveU, CPF_ERR_STATE, "cpf_step: call cpf_set_velocity first");
     CPF_REQUIRE(ctx, n >= 0 && nCycles >= 0, CPF_ERR_ARG, "cpf_step: negative count");
     CPF_REQUIRE(ctx, n == 0 || (x && y && z && cell), CPF_ERR_ARG, "cpf_step: null particle array");
     CPF_REQUIRE(ctx, std::isfinite(dt) && std::isfinite(D) && D >= 0.0, CPF_ERR_ARG, "cpf_step: dt/D not finite or D < 0");
     CPF_REQUIRE(ctx, !(flags & CPF_STEP_STORE_VEL) || vel, CPF_ERR_ARG, "cpf_step: CPF_STEP_STORE_VEL needs a vel array");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     const bool vertexU = (flags & CPF_STEP_VERTEX_VELOCITY) != 0;
-    CPF_REQUIRE(ctx, !vertexU || (ctx->haveVertVel && ctx->nTets == (int64_t)ctx->tetsPerCell * ctx->host.nCells), CPF_ERR_STATE,
+    CPF_REQUIRE(ctx, !vertexU || (ctx->tet.haveVel && ctx->tet.nTets == (int64_t)ctx->tet.tetsPerCell * ctx->mesh.host.nCells), CPF_ERR_STATE,
                 "cpf_step: CPF_STEP_VERTEX_VELOCITY needs cpf_set_tets and cpf_set_vertex_velocity for the current mesh");
     const cpf::MeshView m = meshView(ctx);
     const cpf::VertexField vf = vertexField(ctx);
@@ -910,28 +941,23 @@ int cpf_step_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cel
         // ("flat_z" 0: nobody asks.  A verdict still pending belongs to an older launch of the same kind: its 1 may stand)
         const bool reportsZ = n > 0 && cycPerLaunch > 0 && plan.flat() && !settled && ctx->streamState.flatZ != 0;
         if (reportsZ && !ctx->zBadPending) *static_cast<volatile unsigned*>(ctx->h_zBad) = 0u;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        const bool timed = ctx->timing && (ctx->timingLaunch++ % (uint64_t)ctx->timingStride) == 0;
+        Event e0, e1;
+        const bool timed = ctx->timing.on && (ctx->timing.launch++ % (uint64_t)ctx->timing.stride) == 0;
         // the streaming kernels stamp the events with the dispatch's own begin / end (StepPlan::stamped); any other kernel,
         // and a launch without particles (nothing is dispatched), is bracketed by two event records
         const bool stamped = timed && n > 0 && plan.stamped();
         if (timed) {
-            auto take = [&](hipEvent_t& ev) -> hipError_t {
-                if (!ctx->eventPool.empty()) { ev = ctx->eventPool.back(); ctx->eventPool.pop_back(); return hipSuccess; }
-                return hipEventCreateWithFlags(&ev, CPF_TIMING_EVENT_FLAGS);
-            };
-            CPF_HIP(ctx, take(e0)); CPF_HIP(ctx, take(e1));
+            CPF_HIP(ctx, ctx->timing.take(e0)); CPF_HIP(ctx, ctx->timing.take(e1));
             if (!stamped) CPF_HIP(ctx, hipEventRecord(e0, ctx->stream));
         }
         ctx->lastStepN = n; ctx->lastStepCycles = cycPerLaunch;
         const hipError_t le = cpf::launch_step(plan, ctx->stream, x, y, z, cell, gid, vel, n, dt, D, step0 + (uint32_t)c, cycPerLaunch,
-                                               ctx->seed, m, ctx->stats ? ctx->d_counters : nullptr, vertexU ? &vf : nullptr,
-                                               ctx->streamState, settled, stamped ? e0 : nullptr, stamped ? e1 : nullptr);
+                                               ctx->seed, m, ctx->stats ? ctx->counters : nullptr, vertexU ? &vf : nullptr,
+                                               ctx->streamState, settled, stamped ? e0.get() : nullptr, stamped ? e1.get() : nullptr);
         if (le != hipSuccess) {
             // a launch that did not go out (occupancy query, tile count, missing spill area): the two events go back to the
             // pool instead of leaking
-            if (e0) ctx->eventPool.push_back(e0);
-            if (e1) ctx->eventPool.push_back(e1);
+            ctx->timing.give_back(e0); ctx->timing.give_back(e1);
         }
         CPF_HIP(ctx, le);
         if (n > 0 && cycPerLaunch > 0) settled = plan.flat();
@@ -941,7 +967,7 @@ int cpf_step_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cel
         }
         if (timed) {
             if (!stamped) CPF_HIP(ctx, hipEventRecord(e1, ctx->stream));
-            ctx->events.emplace_back(e0, e1);
+            ctx->timing.recorded.emplace_back(std::move(e0), std::move(e1));
         }
     }
     ctx->lastStepZSettled = settled;
@@ -950,21 +976,21 @@ int cpf_step_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cel
 
 int cpf_step(cpf_context* ctx, double dt, double D, int nCycles, unsigned flags) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->n > 0, CPF_ERR_STATE, "cpf_step: no particles");
-    CPF_REQUIRE(ctx, ctx->located, CPF_ERR_STATE, "cpf_step: particles have no cells yet (call cpf_locate_initial)");
+    CPF_REQUIRE(ctx, ctx->cloud.n > 0, CPF_ERR_STATE, "cpf_step: no particles");
+    CPF_REQUIRE(ctx, ctx->cloud.located, CPF_ERR_STATE, "cpf_step: particles have no cells yet (call cpf_locate_initial)");
     // a frame holds the velocities of the particles this call steps; one that is not stepped -- lost, frozen -- has none (the
     // reference's array keeps the velocity of such a particle's last advect, cuda/particles.cu:316-373; with the velocities stored
     // on frame cycles only that would be the one of its last FRAME, and a sharded cloud does not carry it along at all)
-    if ((flags & CPF_STEP_STORE_VEL) && ctx->vel) {
+    if ((flags & CPF_STEP_STORE_VEL) && ctx->cloud.vel) {
         CPF_HIP(ctx, hipSetDevice(ctx->device));
-        CPF_HIP(ctx, hipMemsetAsync(ctx->vel, 0, (size_t)ctx->n * 24, ctx->stream));
+        CPF_HIP(ctx, hipMemsetAsync(ctx->cloud.vel, 0, (size_t)ctx->cloud.n * 24, ctx->stream));
     }
-    const bool settled = ctx->zSettled;
-    ctx->zSettled = false;
-    int r = cpf_step_dev(ctx, ctx->x, ctx->y, ctx->z, ctx->cell, ctx->gid, ctx->vel, ctx->n, dt, D, ctx->stepCounter,
+    const bool settled = ctx->cloud.zSettled;
+    ctx->cloud.zSettled = false;
+    int r = cpf_step_dev(ctx, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->cloud.vel, ctx->cloud.n, dt, D, ctx->stepCounter,
                          nCycles, (flags & ~CPF_STEP_Z_SETTLED) | (settled ? CPF_STEP_Z_SETTLED : 0u));
     if (r != CPF_OK) return r;
-    ctx->zSettled = ctx->lastStepZSettled;
+    ctx->cloud.zSettled = ctx->lastStepZSettled;
     // a cycle of zero length without a kick moves nothing: it is the frame-0 idiom (velocities of one advect in the
     // first output file, out-of-domain particles frozen; src/initCuda.H:184-201) and not a step of the run, so the
     // counter-based Brownian stream and the sort cadence do not see it
@@ -991,26 +1017,26 @@ namespace {
 // in place (ox == nullptr) or into the out arrays
 int sortImpl(cpf_context* ctx, double* x, double* y, double* z, int32_t* cell, int64_t* gid, int64_t n, double* ox, double* oy,
              double* oz, int32_t* ocell, int64_t* ogid, double* vel3) {
-    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_sort_by_cell: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_sort_by_cell: call cpf_set_mesh first");
     CPF_REQUIRE(ctx, n >= 0 && n < ((int64_t)1 << 31) && (n == 0 || (x && y && z && cell)), CPF_ERR_ARG, "cpf_sort_by_cell: bad arguments");
-    CPF_REQUIRE(ctx, ctx->host.nCells < ((int64_t)1 << 26) - 2, CPF_ERR_STATE, "cpf_sort_by_cell: more than 2^26 cells");
+    CPF_REQUIRE(ctx, ctx->mesh.host.nCells < ((int64_t)1 << 26) - 2, CPF_ERR_STATE, "cpf_sort_by_cell: more than 2^26 cells");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     const int endBit = sortEndBit(ctx);
-    const bool census = ctx->streamState.densityLookup != 0 && ctx->d_occupied && ctx->h_occupied;
+    const bool census = ctx->streamState.densityLookup != 0 && ctx->occupied && ctx->h_occupied;
     // sparse clouds (the regime of the streaming kernel's LOOKUP 4: fewer than 8 particles per cell) are ordered along the mesh
     // layer's Morton curve instead of by cell id: measured 0.164 -> 0.153 ms per step at 0.6 particles per cell on the 2.1e6-cell
     // box; dense clouds on a 3-D mesh LOSE 7 % with it (blockMesh's numbering runs along the flow), hence by regime
-    const bool curve = ctx->d_curveRank != nullptr && (ctx->sortCurve == 1 || (ctx->sortCurve < 0 && n < 8 * ctx->host.nCells));
+    const bool curve = ctx->mesh.curveRank != nullptr && (ctx->sortCurve == 1 || (ctx->sortCurve < 0 && n < 8 * ctx->mesh.host.nCells));
     int r = ensureScratch(ctx, cpf::sort_scratch_bytes(n, endBit));
     if (r) return r;
-    CPF_HIP(ctx, cpf::sort_by_cell(ctx->stream, x, y, z, cell, gid, vel3, n, endBit, ctx->d_cellBox, ctx->host.subBits,
-                                   ctx->host.subOrder, ctx->scratch, ctx->scratchBytes, ox, oy, oz, ocell, ogid, census ? ctx->d_occupied : nullptr,
-                                   curve ? ctx->d_curveRank : nullptr, ctx->sortMethod));
+    CPF_HIP(ctx, cpf::sort_by_cell(ctx->stream, x, y, z, cell, gid, vel3, n, endBit, ctx->mesh.cellBox, ctx->mesh.host.subBits,
+                                   ctx->mesh.host.subOrder, ctx->scratch, ctx->scratchBytes, ox, oy, oz, ocell, ogid, census ? ctx->occupied : nullptr,
+                                   curve ? ctx->mesh.curveRank : nullptr, ctx->sortMethod));
     // how many cells hold particles: what the streaming kernel's lookup method goes by with "stream_lookup_by_density"
     // (StreamState::occupiedHost).  Only then: the 16-byte device-to-host copy behind the sort costs 0.9 ms on this stack
     // (measured: 1.50 against 0.60 ms per sort of 1e7 particles) -- more than the sort itself.
     if (census)
-        CPF_HIP(ctx, hipMemcpyAsync(ctx->h_occupied, ctx->d_occupied, 16, hipMemcpyDeviceToHost, ctx->stream));
+        CPF_HIP(ctx, hipMemcpyAsync(ctx->h_occupied, ctx->occupied, 16, hipMemcpyDeviceToHost, ctx->stream));
     return CPF_OK;
 }
 }  // namespace
@@ -1042,55 +1068,43 @@ int cpf_sort_by_cell_dev_to(cpf_context* ctx, const double* x, const double* y, 
 
 int cpf_sort_by_cell(cpf_context* ctx) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->n > 0 && ctx->located, CPF_ERR_STATE, "cpf_sort_by_cell: no located particles");
-    if (ctx->n <= 1) return CPF_OK;
+    CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_sort_by_cell: no located particles");
+    if (ctx->cloud.n <= 1) return CPF_OK;
     // the context's own cloud: sorted into its second set of arrays, then the sets swap roles
-    if (ctx->x2 == nullptr) {
+    CloudArrays &cur = ctx->cloud.cur, &spare = ctx->cloud.spare;
+    if (spare.x == nullptr) {
         CPF_HIP(ctx, hipSetDevice(ctx->device));
-        const size_t c = (size_t)ctx->cap;
-        // all five or none: a failure part-way must not leave x2 set and the later pointers null (the next call would
-        // skip this block and scatter into null pointers)
-        void* b[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        const size_t bytes[5] = {c * 8, c * 8, c * 8, c * 4, c * 8};
-        hipError_t e = hipSuccess;
-        for (int k = 0; k < 5 && e == hipSuccess; ++k) e = hipMalloc(&b[k], bytes[k]);
-        if (e == hipSuccess) e = hipMemsetAsync(b[3], 0xFF, bytes[3], ctx->stream);
-        if (e != hipSuccess) {
-            for (int k = 0; k < 5; ++k) if (b[k]) (void)hipFree(b[k]);
-            CPF_HIP(ctx, e);
-        }
-        ctx->x2 = (double*)b[0]; ctx->y2 = (double*)b[1]; ctx->z2 = (double*)b[2];
-        ctx->cell2 = (int32_t*)b[3]; ctx->gid2 = (int64_t*)b[4];
+        CloudArrays s;                         // moved in whole: a failure part-way leaves no second set behind
+        CPF_HIP(ctx, s.alloc((size_t)ctx->cloud.cap));
+        CPF_HIP(ctx, hipMemsetAsync(s.cell, 0xFF, (size_t)ctx->cloud.cap * 4, ctx->stream));
+        spare = std::move(s);
     }
-    int r = sortImpl(ctx, ctx->x, ctx->y, ctx->z, ctx->cell, ctx->gid, ctx->n, ctx->x2, ctx->y2, ctx->z2, ctx->cell2, ctx->gid2,
-                     ctx->vel);
+    int r = sortImpl(ctx, cur.x, cur.y, cur.z, cur.cell, cur.gid, ctx->cloud.n, spare.x, spare.y, spare.z, spare.cell, spare.gid, ctx->cloud.vel);
     if (r) return r;
-    std::swap(ctx->x, ctx->x2); std::swap(ctx->y, ctx->y2); std::swap(ctx->z, ctx->z2);
-    std::swap(ctx->cell, ctx->cell2); std::swap(ctx->gid, ctx->gid2);
+    std::swap(cur, spare);
     return CPF_OK;
 }
 
 int cpf_num_particles(const cpf_context* ctx, int64_t* n) {
     CPF_REQUIRE(ctx, ctx && n, CPF_ERR_ARG, "null argument");
-    *n = ctx->n;
+    *n = ctx->cloud.n;
     return CPF_OK;
 }
 
 int cpf_get_particles(cpf_context* ctx, double* xyzw, int32_t* cell, double* vel) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->n > 0, CPF_ERR_STATE, "cpf_get_particles: no particles");
+    CPF_REQUIRE(ctx, ctx->cloud.n > 0, CPF_ERR_STATE, "cpf_get_particles: no particles");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)ctx->n;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    int r = ensureScratch(ctx, al(n * 32) + al(n * 4) + al(n * 32));
+    const size_t n = (size_t)ctx->cloud.n;
+    const PackLayout lay(n);
+    int r = ensureScratch(ctx, lay.bytes);
     if (r) return r;
-    char* p = (char*)ctx->scratch;
-    double* dX = (double*)p; p += al(n * 32);
-    int32_t* dC = (int32_t*)p; p += al(n * 4);
-    double* dV = (double*)p;
-    CPF_HIP(ctx, cpf::launch_pack_by_gid(ctx->stream, ctx->x, ctx->y, ctx->z, ctx->cell, ctx->gid, ctx->vel,
-                                         xyzw ? dX : nullptr, cell ? dC : nullptr, vel ? dV : nullptr, ctx->n));
-    if (cell && ctx->d_parentOf) CPF_HIP(ctx, cpf::launch_cells_to_parent(ctx->stream, dC, dC, ctx->d_parentOf, ctx->n, ctx->host.nCells));
+    double* dX = (double*)ctx->scratch.get();
+    int32_t* dC = (int32_t*)(ctx->scratch + lay.offC);
+    double* dV = (double*)(ctx->scratch + lay.offV);
+    CPF_HIP(ctx, cpf::launch_pack_by_gid(ctx->stream, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->cloud.vel,
+                                         xyzw ? dX : nullptr, cell ? dC : nullptr, vel ? dV : nullptr, ctx->cloud.n));
+    if (cell && ctx->mesh.parentOf) CPF_HIP(ctx, cpf::launch_cells_to_parent(ctx->stream, dC, dC, ctx->mesh.parentOf, ctx->cloud.n, ctx->mesh.host.nCells));
     if (xyzw) CPF_HIP(ctx, hipMemcpyAsync(xyzw, dX, n * 32, hipMemcpyDeviceToHost, ctx->stream));
     if (cell) CPF_HIP(ctx, hipMemcpyAsync(cell, dC, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (vel) CPF_HIP(ctx, hipMemcpyAsync(vel, dV, n * 32, hipMemcpyDeviceToHost, ctx->stream));
@@ -1102,7 +1116,7 @@ int cpf_get_counters(cpf_context* ctx, int64_t out[4]) {
     CPF_REQUIRE(ctx, ctx && out, CPF_ERR_ARG, "null argument");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<unsigned long long> h((size_t)cpf::kCounterSlots * 4);
-    CPF_HIP(ctx, hipMemcpyAsync(h.data(), ctx->d_counters, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipMemcpyAsync(h.data(), ctx->counters, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < 4; ++k) {
         unsigned long long sum = 0;
@@ -1112,139 +1126,84 @@ int cpf_get_counters(cpf_context* ctx, int64_t out[4]) {
     return CPF_OK;
 }
 
+}  // extern "C"
+namespace {
+// "sort_key_bits": sub-cell sort key layout: 100*bx + 10*by + bz bits for the position inside the cell's box along x, y, z
+// (most significant axis first as chosen at mesh ingest); default chosen by cpf_set_mesh
+int setSortKeyBits(cpf_context* ctx, double value) {
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "sort_key_bits: call cpf_set_mesh first");
+    const int v = (int)value, nb[3] = {v / 100, (v / 10) % 10, v % 10};
+    CPF_REQUIRE(ctx, value == v && v >= 0 && nb[0] <= 9 && nb[0] + nb[1] + nb[2] <= 12, CPF_ERR_ARG, "sort_key_bits: at most 12 bits");
+    cpf::HostTables& h = ctx->mesh.host;
+    for (int a = 0; a < 3; ++a) {
+        const float f = std::ldexp(1.0f, nb[a] - h.subBits[a]);
+        for (size_t c = 0; c < h.cellBox.size() / 6; ++c) h.cellBox[6 * c + 3 + a] *= f;
+        h.subBits[a] = nb[a];
+    }
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemcpyAsync(ctx->mesh.cellBox, h.cellBox.data(), h.cellBox.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPF_OK;
+}
+int setStepVariant(cpf_context* ctx, double value) {
+#ifndef CPF_EXPERIMENTS
+    CPF_REQUIRE(ctx, value != 1 && value != 2 && value != 5, CPF_ERR_ARG,
+                "step_variant 1, 2 and 5 are experiments (measured slower on every mesh) and not in this build: make EXPERIMENTS=1");
+#endif
+    ctx->stepVariant = (int)value;
+    return CPF_OK;
+}
+
+// cpf_set_option's keys.  A value is accepted if lo <= value <= hi and, with step > 0, it is one of lo, lo + step, ...; a refused
+// one gets CPF_ERR_ARG and `message`.  No message: any value goes (the setter may still refuse).
+struct Option {
+    const char* key;
+    double lo, hi, step;
+    const char* message;
+    int (*set)(cpf_context*, double);
+};
+#define CPF_OPT(lvalue, expr) [](cpf_context* c, double v) -> int { c->lvalue = (expr); return CPF_OK; }
+constexpr double kTiny = std::numeric_limits<double>::denorm_min(), kHuge = std::numeric_limits<double>::max();
+const Option kOptions[] = {
+    {"step_variant", -1, 5, 1, "step_variant must be -1..5", setStepVariant},
+    {"vertex_fast", 0, 1, 1, "vertex_fast must be 0 or 1", CPF_OPT(vertexFast, v != 0)},
+    {"z_fold", 0, 1, 1, "z_fold must be 0 or 1", CPF_OPT(zFold, v != 0)},
+    {"mixed_records", 0, 1, 1, "mixed_records must be 0 or 1", CPF_OPT(mixedRecords, v != 0)},
+    {"flat_walk", 0, 1, 1, "flat_walk must be 0 or 1", CPF_OPT(streamState.flat, (int)v)},
+    {"flat_z", 0, 1, 1, "flat_z must be 0 or 1", CPF_OPT(streamState.flatZ, (int)v)},
+    {"box_records", 0, 1, 1, "box_records must be 0 or 1", CPF_OPT(boxRecords, v != 0)},
+    {"stream_tiles_per_chunk", 1, 1024, 1, "stream_tiles_per_chunk must be 1..1024", CPF_OPT(streamState.tilesPerChunk, (int)v)},
+    {"sort_key_bits", 0, 0, 0, nullptr, setSortKeyBits},
+    {"stream_tail_fraction", 0, 1, 0, "stream_tail_fraction must be in [0, 1]", CPF_OPT(streamState.tailFraction, v)},
+    {"coop_max_cells", 0, 1 << 24, 0, "coop_max_cells must be in [0, 2^24]", CPF_OPT(streamState.coopMaxCells, (int)v)},
+    // (2, 3, 5 on an all-hex mesh: diagnostics -- what the mixed-mesh instantiations cost by themselves; same results.
+    // 8: chosen by the library, "flat_walk".  -1, auto, sits right below the first mode)
+    {"stream_lookup", cpf::kLookupLoop - 1, cpf::kLookupBox, 1, "stream_lookup must be -1 (auto) or 0 ... 6", CPF_OPT(streamState.lookup, (int)v)},
+    {"stream_lookup_by_density", 0, 1, 1, "stream_lookup_by_density must be 0 or 1", CPF_OPT(streamState.densityLookup, (int)v)},
+    {"sort_method", 0, 2, 2, "sort_method must be 2 (this library's radix sort) or 0 (hipcub's)", CPF_OPT(sortMethod, (int)v)},
+    {"sort_curve", -1, 1, 1, "sort_curve must be -1 (by regime), 0 (cell id) or 1 (Morton rank)", CPF_OPT(sortCurve, (int)v)},
+    {"vtu_binary", 0, 1, 1, "vtu_binary must be 0 or 1", CPF_OPT(vtuBinary, v != 0)},
+    {"stream_debug", 0, 0, 0, nullptr, CPF_OPT(streamState.debug, (int)v)},
+    {"stream_waves_per_cu", 0, 32, 1, "stream_waves_per_cu must be 0..32 (0 = auto)", CPF_OPT(streamState.wavesPerCU, (int)v)},
+    {"sort_interval", 0, 1e9, 0, "sort_interval must be >= 0 (0 = never)", CPF_OPT(sortInterval, (int)v)},
+    {"timing_stride", 1, 1e6, 1, "timing_stride must be an integer >= 1", CPF_OPT(timing.stride, (int)v)},
+    {"stats", 0, 0, 0, nullptr, CPF_OPT(stats, v != 0)},
+    {"nonplanar_tol", kTiny, kHuge, 0, "nonplanar_tol must be a positive number", CPF_OPT(nonplanarTol, v)},    // (> 0 and finite)
+    {"split_nonplanar", 0, 1, 1, "split_nonplanar must be 0 or 1", CPF_OPT(splitNonplanar, v != 0)},
+};
+#undef CPF_OPT
+}  // namespace
+extern "C" {
+
 int cpf_set_option(cpf_context* ctx, const char* key, double value) {
     CPF_REQUIRE(ctx, ctx && key, CPF_ERR_ARG, "null argument");
-    const std::string k(key);
-    if (k == "step_variant") {
-        CPF_REQUIRE(ctx, value >= -1 && value <= 5 && value == (int)value, CPF_ERR_ARG, "step_variant must be -1..5");
-#ifndef CPF_EXPERIMENTS
-        CPF_REQUIRE(ctx, value != 1 && value != 2 && value != 5, CPF_ERR_ARG,
-                    "step_variant 1, 2 and 5 are experiments (measured slower on every mesh) and not in this build: make EXPERIMENTS=1");
-#endif
-        ctx->stepVariant = (int)value;
-        return CPF_OK;
+    for (const Option& o : kOptions) {
+        if (std::strcmp(key, o.key) != 0) continue;
+        CPF_REQUIRE(ctx, !o.message || (value >= o.lo && value <= o.hi && (o.step == 0 || std::fmod(value - o.lo, o.step) == 0)),
+                    CPF_ERR_ARG, o.message);
+        return o.set(ctx, value);
     }
-    if (k == "vertex_fast") {
-        CPF_REQUIRE(ctx, value == 0 || value == 1, CPF_ERR_ARG, "vertex_fast must be 0 or 1");
-        ctx->vertexFast = value != 0;
-        return CPF_OK;
-    }
-    if (k == "z_fold") {
-        CPF_REQUIRE(ctx, value == 0 || value == 1, CPF_ERR_ARG, "z_fold must be 0 or 1");
-        ctx->zFold = value != 0;
-        return CPF_OK;
-    }
-    if (k == "mixed_records") {
-        CPF_REQUIRE(ctx, value == 0 || value == 1, CPF_ERR_ARG, "mixed_records must be 0 or 1");
-        ctx->mixedRecords = value != 0;
-        return CPF_OK;
-    }
-    if (k == "flat_walk") {
-        CPF_REQUIRE(ctx, value == 0 || value == 1, CPF_ERR_ARG, "flat_walk must be 0 or 1");
-        ctx->streamState.flat = (int)value;
-        return CPF_OK;
-    }
-    if (k == "flat_z") {
-        CPF_REQUIRE(ctx, value == 0 || value == 1, CPF_ERR_ARG, "flat_z must be 0 or 1");
-        ctx->streamState.flatZ = (int)value;
-        return CPF_OK;
-    }
-    if (k == "box_records") {
-        CPF_REQUIRE(ctx, value == 0 || value == 1, CPF_ERR_ARG, "box_records must be 0 or 1");
-        ctx->boxRecords = value != 0;
-        return CPF_OK;
-    }
-    if (k == "stream_tiles_per_chunk") {
-        CPF_REQUIRE(ctx, value >= 1 && value <= 1024 && value == (int)value, CPF_ERR_ARG, "stream_tiles_per_chunk must be 1..1024");
-        ctx->streamState.tilesPerChunk = (int)value;
-        return CPF_OK;
-    }
-    if (k == "sort_key_bits") {
-        // sub-cell sort key layout: 100*bx + 10*by + bz bits for the position inside the cell's box along x, y, z
-        // (most significant axis first as chosen at mesh ingest); default chosen by cpf_set_mesh
-        CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "sort_key_bits: call cpf_set_mesh first");
-        const int v = (int)value, nb[3] = {v / 100, (v / 10) % 10, v % 10};
-        CPF_REQUIRE(ctx, value == v && v >= 0 && nb[0] <= 9 && nb[0] + nb[1] + nb[2] <= 12, CPF_ERR_ARG, "sort_key_bits: at most 12 bits");
-        for (int a = 0; a < 3; ++a) {
-            const float f = std::ldexp(1.0f, nb[a] - ctx->host.subBits[a]);
-            for (size_t c = 0; c < ctx->host.cellBox.size() / 6; ++c) ctx->host.cellBox[6 * c + 3 + a] *= f;
-            ctx->host.subBits[a] = nb[a];
-        }
-        CPF_HIP(ctx, hipSetDevice(ctx->device));
-        CPF_HIP(ctx, hipMemcpyAsync(ctx->d_cellBox, ctx->host.cellBox.data(), ctx->host.cellBox.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return CPF_OK;
-    }
-    if (k == "stream_tail_fraction") {
-        CPF_REQUIRE(ctx, value >= 0 && value <= 1, CPF_ERR_ARG, "stream_tail_fraction must be in [0, 1]");
-        ctx->streamState.tailFraction = value;
-        return CPF_OK;
-    }
-    if (k == "coop_max_cells") {
-        CPF_REQUIRE(ctx, value >= 0 && value <= (1 << 24), CPF_ERR_ARG, "coop_max_cells must be in [0, 2^24]");
-        ctx->streamState.coopMaxCells = (int)value;
-        return CPF_OK;
-    }
-    if (k == "stream_lookup") {
-        // (2, 3, 5 on an all-hex mesh: diagnostics -- what the mixed-mesh instantiations cost by themselves; same results)
-        CPF_REQUIRE(ctx, value == -1 || (value >= cpf::kLookupLoop && value <= cpf::kLookupBox && value == (int)value), CPF_ERR_ARG, "stream_lookup must be -1 (auto) or 0 ... 6");  // (8: chosen by the library, "flat_walk")
-        ctx->streamState.lookup = (int)value;
-        return CPF_OK;
-    }
-    if (k == "stream_lookup_by_density") {
-        CPF_REQUIRE(ctx, value == 0 || value == 1, CPF_ERR_ARG, "stream_lookup_by_density must be 0 or 1");
-        ctx->streamState.densityLookup = (int)value;
-        return CPF_OK;
-    }
-    if (k == "sort_method") {
-        CPF_REQUIRE(ctx, value == 0 || value == 2, CPF_ERR_ARG, "sort_method must be 2 (this library's radix sort) or 0 (hipcub's)");
-        ctx->sortMethod = (int)value;
-        return CPF_OK;
-    }
-    if (k == "sort_curve") {
-        CPF_REQUIRE(ctx, value == -1 || value == 0 || value == 1, CPF_ERR_ARG, "sort_curve must be -1 (by regime), 0 (cell id) or 1 (Morton rank)");
-        ctx->sortCurve = (int)value;
-        return CPF_OK;
-    }
-    if (k == "vtu_binary") {
-        CPF_REQUIRE(ctx, value == 0 || value == 1, CPF_ERR_ARG, "vtu_binary must be 0 or 1");
-        ctx->vtuBinary = value != 0;
-        return CPF_OK;
-    }
-    if (k == "stream_debug") {
-        ctx->streamState.debug = (int)value;
-        return CPF_OK;
-    }
-    if (k == "stream_waves_per_cu") {
-        CPF_REQUIRE(ctx, value >= 0 && value <= 32 && value == (int)value, CPF_ERR_ARG, "stream_waves_per_cu must be 0..32 (0 = auto)");
-        ctx->streamState.wavesPerCU = (int)value;
-        return CPF_OK;
-    }
-    if (k == "sort_interval") {
-        CPF_REQUIRE(ctx, value >= 0 && value <= 1e9, CPF_ERR_ARG, "sort_interval must be >= 0 (0 = never)");
-        ctx->sortInterval = (int)value;
-        return CPF_OK;
-    }
-    if (k == "timing_stride") {
-        CPF_REQUIRE(ctx, value >= 1 && value <= 1e6 && value == (int)value, CPF_ERR_ARG, "timing_stride must be an integer >= 1");
-        ctx->timingStride = (int)value;
-        return CPF_OK;
-    }
-    if (k == "stats") {
-        ctx->stats = value != 0;
-        return CPF_OK;
-    }
-    if (k == "nonplanar_tol") {
-        CPF_REQUIRE(ctx, value > 0.0 && std::isfinite(value), CPF_ERR_ARG, "nonplanar_tol must be a positive number");
-        ctx->nonplanarTol = value;
-        return CPF_OK;
-    }
-    if (k == "split_nonplanar") {
-        CPF_REQUIRE(ctx, value == 0 || value == 1, CPF_ERR_ARG, "split_nonplanar must be 0 or 1");
-        ctx->splitNonplanar = value != 0;
-        return CPF_OK;
-    }
-    return fail(ctx, CPF_ERR_ARG, "cpf_set_option: unknown key '" + k + "'");
+    return fail(ctx, CPF_ERR_ARG, std::string("cpf_set_option: unknown key '") + key + "'");
 }
 
 }  // extern "C"   (helper for the other translation units, C++ linkage)
@@ -1257,7 +1216,7 @@ extern "C" {
 
 int cpf_step_kernel_name(cpf_context* ctx, double D, unsigned flags, char* buf, size_t bufBytes) {
     CPF_REQUIRE(ctx, ctx && buf && bufBytes > 0, CPF_ERR_ARG, "null argument");
-    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_step_kernel_name: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_step_kernel_name: call cpf_set_mesh first");
     const cpf::MeshView m = meshView(ctx);
     const cpf::VertexField vf = vertexField(ctx);
     pollFieldFlag(ctx);
@@ -1265,7 +1224,7 @@ int cpf_step_kernel_name(cpf_context* ctx, double D, unsigned flags, char* buf, 
     // kernels' record lookup on the particle count: the most recent launch's stand in, else the owned cloud's (the
     // "VertexVelocity" cycle's also after a launch without particles)
     const bool vertexU = (flags & CPF_STEP_VERTEX_VELOCITY) != 0;
-    const int64_t n = (vertexU ? ctx->lastStepN > 0 : ctx->lastStepN >= 0) ? ctx->lastStepN : ctx->n;
+    const int64_t n = (vertexU ? ctx->lastStepN > 0 : ctx->lastStepN >= 0) ? ctx->lastStepN : ctx->cloud.n;
     const cpf::StepPlan p = cpf::plan_step(m, ctx->streamState, ctx->stepVariant, vertexU ? &vf : nullptr, n,
                                            (flags & CPF_STEP_FUSE_CYCLES) ? ctx->lastStepCycles : 1, D, flags, ctx->stats);
     const char* b[2] = {"false", "true"};
@@ -1275,10 +1234,10 @@ int cpf_step_kernel_name(cpf_context* ctx, double D, unsigned flags, char* buf, 
                  b[p.storeVel], b[p.stats], p.lookup);
     else if (p.kernel == cpf::StepPlan::kVertex)
         snprintf(tmp, sizeof tmp, "cpf::step_kernel_vertex<%s, %s, %s> (%s)", b[p.brown], b[p.reflect], b[p.storeVel],
-                 p.cone ? "cone locate" : (ctx->d_vertCone || ctx->vertConeWhy.empty() ? "all tets" : ("all tets: " + ctx->vertConeWhy).c_str()));
+                 p.cone ? "cone locate" : (ctx->tet.cone || ctx->tet.coneWhy.empty() ? "all tets" : ("all tets: " + ctx->tet.coneWhy).c_str()));
     else if (p.kernel == cpf::StepPlan::kAhead)
         snprintf(tmp, sizeof tmp, "cpf::step_kernel_ahead<%s, %s>", b[p.reflect], b[p.stats]);
-    else if (p.flat_body(ctx->streamState, ctx->zSettled) && !zBadArrived(ctx))       // (what cpf_step launches next on the context's own cloud)
+    else if (p.flat_body(ctx->streamState, ctx->cloud.zSettled) && !zBadArrived(ctx))       // (what cpf_step launches next on the context's own cloud)
         snprintf(tmp, sizeof tmp, "cpf::step_kernel_stream_flat<%s, %s, %s, %d>", b[p.reflect], b[p.storeVel], b[p.stats], p.lookup);
     else if (p.kernel == cpf::StepPlan::kStream)
         snprintf(tmp, sizeof tmp, "cpf::step_kernel_stream<%s, %s, %s, %s, %d>", b[p.brown], b[p.reflect], b[p.storeVel], b[p.stats], p.lookup);
@@ -1303,7 +1262,7 @@ int cpf_pack_leavers_dev(cpf_context* ctx, double* x, double* y, double* z, int3
                 CPF_ERR_ARG, "cpf_pack_leavers_dev: bad sizes (1 .. CPF_MAX_RANKS ranks)");
     CPF_REQUIRE(ctx, cellLo_dev && counts_dev && nStay_dev && (sendbuf || sendCapacity == 0) && (n == 0 || (x && y && z && cell)),
                 CPF_ERR_ARG, "cpf_pack_leavers_dev: null array");
-    CPF_REQUIRE(ctx, !ctx->d_parentOf, CPF_ERR_MESH, "cpf_pack_leavers_dev: the mesh has cells decomposed into tets "
+    CPF_REQUIRE(ctx, !ctx->mesh.parentOf, CPF_ERR_MESH, "cpf_pack_leavers_dev: the mesh has cells decomposed into tets "
                 "(cpf_get_mesh_quality): ownership ranges are parent ids, the cloud's cells derived ids");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     int r = ensureScratch(ctx, cpf::handoff_scratch_bytes(n, nRanks));
@@ -1315,33 +1274,33 @@ int cpf_pack_leavers_dev(cpf_context* ctx, double* x, double* y, double* z, int3
 
 int cpf_cell_histogram_dev(cpf_context* ctx, const int32_t* cell, int64_t n, double scale, double* weights_dev) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_cell_histogram_dev: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_cell_histogram_dev: call cpf_set_mesh first");
     CPF_REQUIRE(ctx, n >= 0 && weights_dev && (cell || n == 0), CPF_ERR_ARG, "cpf_cell_histogram_dev: bad arguments");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->d_parentOf) {                             // weights per PARENT cell: the ids are mapped first, into the scratch's head
+    if (ctx->mesh.parentOf) {                             // weights per PARENT cell: the ids are mapped first, into the scratch's head
         const size_t head = ((size_t)n * 4 + 255) & ~(size_t)255;
-        int r = ensureScratch(ctx, head + cpf::histogram_scratch_bytes(ctx->nParent));
+        int r = ensureScratch(ctx, head + cpf::histogram_scratch_bytes(ctx->mesh.nParent));
         if (r != CPF_OK) return r;
-        int32_t* parent = (int32_t*)ctx->scratch;
-        CPF_HIP(ctx, cpf::launch_cells_to_parent(ctx->stream, cell, parent, ctx->d_parentOf, n, ctx->host.nCells));
-        CPF_HIP(ctx, cpf::cell_histogram(ctx->stream, parent, n, ctx->nParent, scale, weights_dev, (char*)ctx->scratch + head,
+        int32_t* parent = (int32_t*)ctx->scratch.get();
+        CPF_HIP(ctx, cpf::launch_cells_to_parent(ctx->stream, cell, parent, ctx->mesh.parentOf, n, ctx->mesh.host.nCells));
+        CPF_HIP(ctx, cpf::cell_histogram(ctx->stream, parent, n, ctx->mesh.nParent, scale, weights_dev, ctx->scratch + head,
                                          ctx->scratchBytes - head));
         return CPF_OK;
     }
-    int r = ensureScratch(ctx, cpf::histogram_scratch_bytes(ctx->host.nCells));
+    int r = ensureScratch(ctx, cpf::histogram_scratch_bytes(ctx->mesh.host.nCells));
     if (r != CPF_OK) return r;
-    CPF_HIP(ctx, cpf::cell_histogram(ctx->stream, cell, n, ctx->host.nCells, scale, weights_dev, ctx->scratch,
+    CPF_HIP(ctx, cpf::cell_histogram(ctx->stream, cell, n, ctx->mesh.host.nCells, scale, weights_dev, ctx->scratch,
                                      ctx->scratchBytes));
     return CPF_OK;
 }
 
 int cpf_cell_ranges_dev(cpf_context* ctx, const double* weights_dev, int nRanks, int32_t* cellLo_dev) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_cell_ranges_dev: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_cell_ranges_dev: call cpf_set_mesh first");
     CPF_REQUIRE(ctx, weights_dev && cellLo_dev && nRanks >= 1 && nRanks <= CPF_MAX_RANKS, CPF_ERR_ARG,
                 "cpf_cell_ranges_dev: bad arguments (1 <= nRanks <= CPF_MAX_RANKS)");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, cpf::cell_ranges(ctx->stream, weights_dev, ctx->nParent, nRanks, cellLo_dev));   // (weights: per parent cell)
+    CPF_HIP(ctx, cpf::cell_ranges(ctx->stream, weights_dev, ctx->mesh.nParent, nRanks, cellLo_dev));   // (weights: per parent cell)
     return CPF_OK;
 }
 
@@ -1406,10 +1365,10 @@ int cpf_copy_dev(cpf_context* ctx, void* dst, const void* src, size_t bytes) {
 // ---- stage-by-stage entry points (reference layouts) --------------------------------------------
 #define CPF_STAGE_PRE(name, needU)                                                                      \
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");                                                 \
-    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, name ": call cpf_set_mesh first");                   \
-    CPF_REQUIRE(ctx, !ctx->d_parentOf, CPF_ERR_MESH, name ": the mesh has warped or concave cells decomposed " \
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, name ": call cpf_set_mesh first");                   \
+    CPF_REQUIRE(ctx, !ctx->mesh.parentOf, CPF_ERR_MESH, name ": the mesh has warped or concave cells decomposed " \
                 "into tets (cpf_get_mesh_quality); the reference-layout stages take the mesh's own cells only"); \
-    CPF_REQUIRE(ctx, !(needU) || ctx->haveU, CPF_ERR_STATE, name ": call cpf_set_velocity first");      \
+    CPF_REQUIRE(ctx, !(needU) || ctx->mesh.haveU, CPF_ERR_STATE, name ": call cpf_set_velocity first");      \
     CPF_REQUIRE(ctx, n >= 0, CPF_ERR_ARG, name ": negative particle count");                            \
     CPF_HIP(ctx, hipSetDevice(ctx->device))
 
@@ -1420,7 +1379,7 @@ int cpf_stage_seed_box(cpf_context* ctx, double* particles, int64_t n, const dou
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     int r = ensureScratch(ctx, (size_t)std::max<int64_t>(n, 1) * 24);
     if (r) return r;
-    double* x = (double*)ctx->scratch; double* y = x + n; double* z = y + n;
+    double* x = (double*)ctx->scratch.get(); double* y = x + n; double* z = y + n;
     CPF_HIP(ctx, cpf::launch_seed_box(ctx->stream, x, y, z, 0, n, lower, upper, order));
     CPF_HIP(ctx, cpf::launch_soa_to_aos(ctx->stream, x, y, z, particles, n));
     return CPF_OK;
@@ -1430,7 +1389,7 @@ int cpf_stage_locate_initial(cpf_context* ctx, const double* particles, int32_t*
     CPF_REQUIRE(ctx, n == 0 || (particles && ids), CPF_ERR_ARG, "cpf_stage_locate_initial: null array");
     int r = ensureScratch(ctx, (size_t)std::max<int64_t>(n, 1) * 24);
     if (r) return r;
-    double* x = (double*)ctx->scratch; double* y = x + n; double* z = y + n;
+    double* x = (double*)ctx->scratch.get(); double* y = x + n; double* z = y + n;
     CPF_HIP(ctx, cpf::launch_aos_to_soa(ctx->stream, particles, x, y, z, n));
     CPF_HIP(ctx, cpf::launch_locate_initial(ctx->stream, x, y, z, ids, n, meshView(ctx), gridView(ctx)));
     return CPF_OK;
@@ -1438,14 +1397,7 @@ int cpf_stage_locate_initial(cpf_context* ctx, const double* particles, int32_t*
 int cpf_stage_count_outside(cpf_context* ctx, const int32_t* ids, int64_t n, int64_t* nNegative) {
     CPF_REQUIRE(ctx, ctx && nNegative && (ids || n == 0) && n >= 0, CPF_ERR_ARG, "cpf_stage_count_outside: bad arguments");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
-    unsigned long long* cnt = ctx->d_counters + cpf::kCounterSlots * 4;
-    CPF_HIP(ctx, hipMemsetAsync(cnt, 0, 8, ctx->stream));
-    CPF_HIP(ctx, cpf::launch_count_negative(ctx->stream, ids, n, cnt));
-    unsigned long long h = 0;
-    CPF_HIP(ctx, hipMemcpyAsync(&h, cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *nNegative = (int64_t)h;
-    return CPF_OK;
+    return countNegative(ctx, ids, n, nNegative);
 }
 int cpf_stage_advect(cpf_context* ctx, double* particles, const int32_t* ids, double* vels, double* disps, double dt,
                      int64_t n) {
@@ -1464,54 +1416,57 @@ int cpf_stage_advect_const(cpf_context* ctx, double* particles, const int32_t* i
 int cpf_set_tets(cpf_context* ctx, const double* positions, int64_t nVerts, const int32_t* tets, int64_t nTets,
                  int tetsPerCell) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->haveMesh, CPF_ERR_STATE, "cpf_set_tets: call cpf_set_mesh first");
-    CPF_REQUIRE(ctx, !ctx->d_parentOf, CPF_ERR_MESH, "cpf_set_tets: the mesh has warped or concave cells decomposed into tets "
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_set_tets: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, !ctx->mesh.parentOf, CPF_ERR_MESH, "cpf_set_tets: the mesh has warped or concave cells decomposed into tets "
                 "(cpf_get_mesh_quality); the \"VertexVelocity\" mode needs the mesh's own cells (set option \"split_nonplanar\" 0)");
     CPF_REQUIRE(ctx, positions && tets && nVerts > 0 && tetsPerCell > 0, CPF_ERR_ARG, "cpf_set_tets: bad arguments");
-    CPF_REQUIRE(ctx, nTets == (int64_t)tetsPerCell * ctx->host.nCells, CPF_ERR_MESH,
+    CPF_REQUIRE(ctx, nTets == (int64_t)tetsPerCell * ctx->mesh.host.nCells, CPF_ERR_MESH,
                 "cpf_set_tets: nTets must be tetsPerCell x nCells (tets in cell order, src/initCuda.H:99-105)");
     for (int64_t k = 0; k < 4 * nTets; ++k)
         CPF_REQUIRE(ctx, tets[k] >= 0 && tets[k] < nVerts, CPF_ERR_MESH, "cpf_set_tets: tet vertex out of range");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    freeDev(ctx->d_tetPos); freeDev(ctx->d_tets); freeDev(ctx->d_vertVel); freeDev(ctx->d_vertCone); freeDev(ctx->d_vertApex);
-    ctx->haveVertVel = false;
-    CPF_HIP(ctx, hipMalloc((void**)&ctx->d_tetPos, (size_t)nVerts * 24));
-    CPF_HIP(ctx, hipMalloc((void**)&ctx->d_tets, (size_t)nTets * 16));
-    CPF_HIP(ctx, hipMalloc((void**)&ctx->d_vertVel, (size_t)nVerts * 24));
-    CPF_HIP(ctx, hipMemcpyAsync(ctx->d_tetPos, positions, (size_t)nVerts * 24, hipMemcpyHostToDevice, ctx->stream));
-    CPF_HIP(ctx, hipMemcpyAsync(ctx->d_tets, tets, (size_t)nTets * 16, hipMemcpyHostToDevice, ctx->stream));
+    ctx->tet = TetField{};
+    // built into a local and moved in once nothing can fail any more: a call that fails leaves the context without a tet
+    // field -- never with nTets set, a lone cone table or unbuilt records for cpf_set_vertex_velocity to write into
+    TetField t;
+    CPF_HIP(ctx, t.pos.alloc((size_t)nVerts * 3));
+    CPF_HIP(ctx, t.tets.alloc((size_t)nTets * 4));
+    CPF_HIP(ctx, t.vel.alloc((size_t)nVerts * 3));
+    CPF_HIP(ctx, hipMemcpyAsync(t.pos, positions, (size_t)nVerts * 24, hipMemcpyHostToDevice, ctx->stream));
+    CPF_HIP(ctx, hipMemcpyAsync(t.tets, tets, (size_t)nTets * 16, hipMemcpyHostToDevice, ctx->stream));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->nTetVerts = nVerts; ctx->nTets = nTets; ctx->tetsPerCell = tetsPerCell;
     // the cone locate (cpf_kernels.hip, VertexField) is exact only on a decomposition whose tets cannot overlap: decided here
-    ctx->vertConeWhy = tetFanDefect(positions, tets, ctx->host.nCells, tetsPerCell);
-    if (ctx->vertConeWhy.empty()) {
-        CPF_HIP(ctx, hipMalloc((void**)&ctx->d_vertCone, (size_t)nTets * 256));
-        CPF_HIP(ctx, hipMalloc((void**)&ctx->d_vertApex, (size_t)ctx->host.nCells * 32));
-        CPF_HIP(ctx, cpf::launch_vertex_cone_tables(ctx->stream, ctx->d_tetPos, ctx->d_tets, nTets, tetsPerCell, ctx->d_vertCone, ctx->d_vertApex));
+    t.coneWhy = tetFanDefect(positions, tets, ctx->mesh.host.nCells, tetsPerCell);
+    if (t.coneWhy.empty()) {
+        CPF_HIP(ctx, t.cone.alloc((size_t)nTets * 32));
+        CPF_HIP(ctx, t.apex.alloc((size_t)ctx->mesh.host.nCells * 4));
+        CPF_HIP(ctx, cpf::launch_vertex_cone_tables(ctx->stream, t.pos, t.tets, nTets, tetsPerCell, t.cone, t.apex));
         CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
+    t.nVerts = nVerts; t.nTets = nTets; t.tetsPerCell = tetsPerCell;
+    ctx->tet = std::move(t);
     return CPF_OK;
 }
 int cpf_set_vertex_velocity(cpf_context* ctx, const double* vertexU, int64_t nVerts) {
     CPF_REQUIRE(ctx, ctx && vertexU, CPF_ERR_ARG, "null argument");
-    CPF_REQUIRE(ctx, ctx->d_tets, CPF_ERR_STATE, "cpf_set_vertex_velocity: call cpf_set_tets first");
-    CPF_REQUIRE(ctx, nVerts == ctx->nTetVerts, CPF_ERR_ARG, "cpf_set_vertex_velocity: one velocity per tet-mesh vertex");
+    CPF_REQUIRE(ctx, ctx->tet.tets, CPF_ERR_STATE, "cpf_set_vertex_velocity: call cpf_set_tets first");
+    CPF_REQUIRE(ctx, nVerts == ctx->tet.nVerts, CPF_ERR_ARG, "cpf_set_vertex_velocity: one velocity per tet-mesh vertex");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(ctx->d_vertVel, vertexU, (size_t)nVerts * 24, hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->d_vertCone) CPF_HIP(ctx, cpf::launch_vertex_record_velocity(ctx->stream, ctx->d_tets, ctx->d_vertVel, ctx->nTets, ctx->d_vertCone));
+    CPF_HIP(ctx, hipMemcpyAsync(ctx->tet.vel, vertexU, (size_t)nVerts * 24, hipMemcpyHostToDevice, ctx->stream));
+    if (ctx->tet.cone) CPF_HIP(ctx, cpf::launch_vertex_record_velocity(ctx->stream, ctx->tet.tets, ctx->tet.vel, ctx->tet.nTets, ctx->tet.cone));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->haveVertVel = true;
+    ctx->tet.haveVel = true;
     return CPF_OK;
 }
 int cpf_stage_advect_vertex(cpf_context* ctx, double* particles, const int32_t* ids, double* vels, double* disps,
                             double dt, int64_t n) {
     CPF_STAGE_PRE("cpf_stage_advect_vertex", false);
-    CPF_REQUIRE(ctx, ctx->haveVertVel && ctx->nTets == (int64_t)ctx->tetsPerCell * ctx->host.nCells, CPF_ERR_STATE,
+    CPF_REQUIRE(ctx, ctx->tet.haveVel && ctx->tet.nTets == (int64_t)ctx->tet.tetsPerCell * ctx->mesh.host.nCells, CPF_ERR_STATE,
                 "cpf_stage_advect_vertex: call cpf_set_tets and cpf_set_vertex_velocity (for the current mesh) first");
     CPF_REQUIRE(ctx, n == 0 || (particles && ids && vels && disps), CPF_ERR_ARG, "cpf_stage_advect_vertex: null array");
-    CPF_HIP(ctx, cpf::launch_stage_advect_vertex(ctx->stream, particles, ids, vels, disps, dt, n, ctx->d_tetPos, ctx->d_tets,
-                                                 ctx->tetsPerCell, ctx->d_vertVel, ctx->vertexFast ? ctx->d_vertCone : nullptr, ctx->d_vertApex));
+    CPF_HIP(ctx, cpf::launch_stage_advect_vertex(ctx->stream, particles, ids, vels, disps, dt, n, ctx->tet.pos, ctx->tet.tets,
+                                                 ctx->tet.tetsPerCell, ctx->tet.vel, ctx->vertexFast ? ctx->tet.cone.get() : nullptr, ctx->tet.apex));
     return CPF_OK;
 }
 int cpf_stage_brownian(cpf_context* ctx, const double* particles, double* disps, double dt, int64_t n, double D,
@@ -1544,16 +1499,16 @@ int cpf_stage_move(cpf_context* ctx, double* particles, double* disps, int64_t n
 
 int cpf_write_vtu_wait(cpf_context* ctx) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    if (!ctx->writerLive) return CPF_OK;
-    ctx->writer.join();
-    ctx->writerLive = false;
+    if (!ctx->frame.live) return CPF_OK;
+    ctx->frame.thread.join();
+    ctx->frame.live = false;
     {
         std::lock_guard<std::mutex> lk(g_mutex);
         auto& v = g_writers.live;
         v.erase(std::remove(v.begin(), v.end(), ctx), v.end());
     }
-    const int r = ctx->writerStatus;
-    ctx->writerStatus = CPF_OK;
+    const int r = ctx->frame.status;
+    ctx->frame.status = CPF_OK;
     if (r != CPF_OK && r != CPF_WARN_NAN) return fail(ctx, r, "cpf_write_vtu_async: the frame could not be written");
     return r;
 }
@@ -1562,70 +1517,70 @@ int cpf_write_vtu_async(cpf_context* ctx, const char* path, double* totalKE) {
     CPF_REQUIRE(ctx, ctx && path, CPF_ERR_ARG, "null argument");
     int r = cpf_write_vtu_wait(ctx);                       // one frame in flight; reports the previous frame's failure
     if (r != CPF_OK && r != CPF_WARN_NAN) return r;
-    CPF_REQUIRE(ctx, ctx->n > 0, CPF_ERR_STATE, "cpf_write_vtu_async: no particles");
+    CPF_REQUIRE(ctx, ctx->cloud.n > 0, CPF_ERR_STATE, "cpf_write_vtu_async: no particles");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)ctx->n;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t offC = al(n * 32), offV = offC + al(n * 4), need = offV + al(n * 32);
-    if (!ctx->ioStream) {
-        CPF_HIP(ctx, hipStreamCreateWithFlags(&ctx->ioStream, hipStreamNonBlocking));
-        CPF_HIP(ctx, hipEventCreateWithFlags(&ctx->evSnap, hipEventDisableTiming));
-        CPF_HIP(ctx, hipEventCreateWithFlags(&ctx->evCopied, hipEventDisableTiming));
+    const size_t n = (size_t)ctx->cloud.n;
+    const PackLayout lay(n);
+    const size_t offC = lay.offC, offV = lay.offV, need = lay.bytes;
+    if (!ctx->frame.io) {
+        CPF_HIP(ctx, ctx->frame.io.create(hipStreamNonBlocking));
+        CPF_HIP(ctx, ctx->frame.evSnap.create(hipEventDisableTiming));
+        CPF_HIP(ctx, ctx->frame.evCopied.create(hipEventDisableTiming));
     }
-    if (need > ctx->snapBytes) {                           // (the previous frame's worker has been joined: nobody reads these)
-        if (ctx->snapDev) { (void)hipFree(ctx->snapDev); ctx->snapDev = nullptr; }
-        if (ctx->snapHost) { (void)hipHostFree(ctx->snapHost); ctx->snapHost = nullptr; }
-        ctx->snapBytes = 0;
+    if (need > ctx->frame.snapBytes) {                           // (the previous frame's worker has been joined: nobody reads these)
+        ctx->frame.snapDev.reset();
+        ctx->frame.snapHost.reset();
+        ctx->frame.snapBytes = 0;
         const size_t want = need + need / 8;
-        hipError_t e = hipMalloc(&ctx->snapDev, want);
-        if (e == hipSuccess) e = hipHostMalloc(&ctx->snapHost, want, hipHostMallocDefault);
+        hipError_t e = ctx->frame.snapDev.alloc(want);
+        if (e == hipSuccess) e = ctx->frame.snapHost.alloc(want);
         if (e != hipSuccess) {
-            if (ctx->snapDev) { (void)hipFree(ctx->snapDev); ctx->snapDev = nullptr; }
+            ctx->frame.snapDev.reset();
             return fail(ctx, e == hipErrorOutOfMemory ? CPF_ERR_NOMEM : CPF_ERR_HIP, std::string("cpf_write_vtu_async: snapshot buffers: ") + hipGetErrorString(e));
         }
-        ctx->snapBytes = want;
+        ctx->frame.snapBytes = want;
     }
     // ---- the snapshot: ONE kernel on the compute stream (particle-id order, the layouts the writer reads); everything else --
     // PCIe, the energy sum, formatting, the file -- happens behind the caller's back
-    char* d = (char*)ctx->snapDev;
-    CPF_HIP(ctx, cpf::launch_pack_by_gid(ctx->stream, ctx->x, ctx->y, ctx->z, ctx->cell, ctx->gid, ctx->vel, (double*)d, (int32_t*)(d + offC),
-                                         (double*)(d + offV), ctx->n));
-    if (ctx->d_parentOf)
-        CPF_HIP(ctx, cpf::launch_cells_to_parent(ctx->stream, (const int32_t*)(d + offC), (int32_t*)(d + offC), ctx->d_parentOf, ctx->n,
-                                                 ctx->host.nCells));
-    CPF_HIP(ctx, hipEventRecord(ctx->evSnap, ctx->stream));
-    CPF_HIP(ctx, hipStreamWaitEvent(ctx->ioStream, ctx->evSnap, 0));
-    CPF_HIP(ctx, hipMemcpyAsync(ctx->snapHost, ctx->snapDev, need, hipMemcpyDeviceToHost, ctx->ioStream));
-    CPF_HIP(ctx, hipEventRecord(ctx->evCopied, ctx->ioStream));
+    char* d = ctx->frame.snapDev;
+    CPF_HIP(ctx, cpf::launch_pack_by_gid(ctx->stream, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->cloud.vel, (double*)d, (int32_t*)(d + offC),
+                                         (double*)(d + offV), ctx->cloud.n));
+    if (ctx->mesh.parentOf)
+        CPF_HIP(ctx, cpf::launch_cells_to_parent(ctx->stream, (const int32_t*)(d + offC), (int32_t*)(d + offC), ctx->mesh.parentOf, ctx->cloud.n,
+                                                 ctx->mesh.host.nCells));
+    CPF_HIP(ctx, hipEventRecord(ctx->frame.evSnap, ctx->stream));
+    CPF_HIP(ctx, hipStreamWaitEvent(ctx->frame.io, ctx->frame.evSnap, 0));
+    CPF_HIP(ctx, hipMemcpyAsync(ctx->frame.snapHost, ctx->frame.snapDev, need, hipMemcpyDeviceToHost, ctx->frame.io));
+    CPF_HIP(ctx, hipEventRecord(ctx->frame.evCopied, ctx->frame.io));
     const std::string file(path);
     { std::lock_guard<std::mutex> lk(g_mutex); g_writers.live.push_back(ctx); }
-    ctx->writerLive = true;
-    ctx->keReady = false;
+    ctx->frame.live = true;
+    ctx->frame.keReady = false;
     const bool binary = ctx->vtuBinary;
-    ctx->writer = std::thread([ctx, file, n, binary, offC, offV] {
+    ctx->frame.thread = std::thread([ctx, file, n, binary, offC, offV] {
         (void)hipSetDevice(ctx->device);
-        const hipError_t e = hipEventSynchronize(ctx->evCopied);
-        const char* h = (const char*)ctx->snapHost;
+        const hipError_t e = hipEventSynchronize(ctx->frame.evCopied);
+        const char* h = ctx->frame.snapHost;
         const double* xyzw = (const double*)h; const int32_t* cell = (const int32_t*)(h + offC); const double* vel = (const double*)(h + offV);
         double total = 0.0;                                // in index order, like the reference's running sum
         if (e == hipSuccess)
             for (size_t i = 0; i < n; ++i) total += 0.5 * (vel[4 * i] * vel[4 * i] + vel[4 * i + 1] * vel[4 * i + 1] + vel[4 * i + 2] * vel[4 * i + 2]);
-        { std::lock_guard<std::mutex> lk(ctx->keMutex); ctx->frameKE = total; ctx->keReady = true; }
-        ctx->keCv.notify_all();
-        ctx->writerStatus = e != hipSuccess ? CPF_ERR_HIP
+        { std::lock_guard<std::mutex> lk(ctx->frame.keMutex); ctx->frame.ke = total; ctx->frame.keReady = true; }
+        ctx->frame.keCv.notify_all();
+        ctx->frame.status = e != hipSuccess ? CPF_ERR_HIP
                                             : (binary ? cpf_write_vtu_arrays_binary : cpf_write_vtu_arrays)(file.c_str(), (int64_t)n, xyzw, cell, vel, nullptr);
     });
     if (!totalKE) return CPF_OK;                           // the caller is back in its step loop after the one kernel launch
     // the energy at once (a host that prints it where the reference does): that host waits for the copy and one pass over it
-    std::unique_lock<std::mutex> lk(ctx->keMutex);
-    ctx->keCv.wait(lk, [ctx] { return ctx->keReady; });
-    *totalKE = ctx->frameKE;
-    return std::isnan(ctx->frameKE) ? CPF_WARN_NAN : CPF_OK;
+    std::unique_lock<std::mutex> lk(ctx->frame.keMutex);
+    ctx->frame.keCv.wait(lk, [ctx] { return ctx->frame.keReady; });
+    *totalKE = ctx->frame.ke;
+    return std::isnan(ctx->frame.ke) ? CPF_WARN_NAN : CPF_OK;
 }
 
 int cpf_timing_enable(cpf_context* ctx, int on) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    ctx->timing = on != 0;
+    ctx->timing.on = on != 0;
     return CPF_OK;
 }
 
@@ -1633,37 +1588,14 @@ int cpf_timing_read(cpf_context* ctx, int64_t* launches, double* total_ms) {
     CPF_REQUIRE(ctx, ctx && launches && total_ms, CPF_ERR_ARG, "null argument");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    double tot = 0.0;
-    for (auto& p : ctx->events) {
-        float ms = 0.f;
-        CPF_HIP(ctx, hipEventElapsedTime(&ms, p.first, p.second));
-        tot += (double)ms;
-        ctx->eventPool.push_back(p.first); ctx->eventPool.push_back(p.second);
-    }
-    *launches = (int64_t)ctx->events.size();
-    *total_ms = tot;
-    ctx->events.clear();
+    CPF_HIP(ctx, ctx->timing.drain(false, launches, total_ms));
     return CPF_OK;
 }
 
 int cpf_timing_poll(cpf_context* ctx, int64_t* launches, double* total_ms) {
     CPF_REQUIRE(ctx, ctx && launches && total_ms, CPF_ERR_ARG, "null argument");
     CPF_HIP(ctx, hipSetDevice(ctx->device));
-    double tot = 0.0;
-    size_t done = 0;
-    for (; done < ctx->events.size(); ++done) {          // launches complete in stream order
-        auto& p = ctx->events[done];
-        const hipError_t q = hipEventQuery(p.second);
-        if (q == hipErrorNotReady) break;
-        CPF_HIP(ctx, q);
-        float ms = 0.f;
-        CPF_HIP(ctx, hipEventElapsedTime(&ms, p.first, p.second));
-        tot += (double)ms;
-        ctx->eventPool.push_back(p.first); ctx->eventPool.push_back(p.second);
-    }
-    ctx->events.erase(ctx->events.begin(), ctx->events.begin() + (std::ptrdiff_t)done);
-    *launches = (int64_t)done;
-    *total_ms = tot;
+    CPF_HIP(ctx, ctx->timing.drain(true, launches, total_ms));
     return CPF_OK;
 }
 
