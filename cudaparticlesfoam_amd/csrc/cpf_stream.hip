@@ -783,7 +783,7 @@ __device__ __forceinline__ void stream_body(
                     D3 E = {S_.x + disp.x, S_.y + disp.y, ZSET ? 0.0 : S_.z + disp.z};
                     if (BROWNIAN && REFLECT && zFold) {                           // one cell thick in z: cpf_walk.h, fold_z
                         bool clear;
-                        const int nb = fold_z(E.z, rec[BOX ? 0 : 4], rec[BOX ? 0 : 5], clear);      // (never with box records: zFold)
+                        const int nb = fold_z(E.z, S_.z, rec[BOX ? 0 : 4], rec[BOX ? 0 : 5], clear);      // (never with box records: zFold)
                         zUnclear |= ballot64(!clear) != 0ull;                      // (wave-uniform; the advecting lanes vote)
                         if (STATS) st.refl += nb;
                         if (STORE_VEL && (nb & 1)) v.z = -v.z;
@@ -1195,8 +1195,12 @@ static int stream_lookup_mode(int64_t n, const MeshView& m, const StreamState& s
         if (occ > 0 && occ <= cells && live > 0 && live <= 2 * n && n <= 2 * live) cells = occ;
     }
     // the "VertexVelocity" cycle: the loop or the fixed lookup on the 256-byte records (no flat walk: the interpolated velocity
-    // may have a z component whatever the cell field says)
-    if (vertex) return n < 128 * cells ? kLookupFixed : kLookupLoop;
+    // may have a z component whatever the cell field says); "stream_lookup" 0 / 1 overrides here as it does below, any other
+    // mode is not instantiated for this kernel and leaves the choice to the density
+    if (vertex) {
+        if (ss.lookup == kLookupLoop || ss.lookup == kLookupFixed) return ss.lookup;
+        return n < 128 * cells ? kLookupFixed : kLookupLoop;
+    }
     // not all-hex: with / without big cells (more than six slots); without them and with many particles per cell, the loop lookup
     // (every cell a box although the mesh has face groups -- 2:1-refined boxes: box records with group slots)
     if (m.mixed == 1 && m.boxRec != nullptr && m.zThin == 0 && ss.lookup < 0) return kLookupBoxGroups;

@@ -95,6 +95,18 @@ __device__ __forceinline__ int fold_z(double& ez, const double4& pa, const doubl
     clear = ez > lo + margin && ez < hi - margin;
     return nb;
 }
+// ... with the START point of the segment.  The argument above is about a segment that starts between the planes ("from inside").
+// A particle that begins its cycle beyond one of them -- by a rounding of the last move's hit + (E - hit), or because its caller
+// put it there -- heads back in with fd and den of equal signs and a tiny |fd|: the reference's walk accepts that z face, so a
+// wave that leaves the z faces out would give such a lane other bits than a wave that tests them, and the result would depend
+// on which particles share a wave (tests/test_gpu_vertex_cycle.py: a sorted cloud against an unsorted one).  Such a lane is
+// not clear, whatever its end point; on a plane (sz == lo or hi) fd is 0 and the face is rejected as from inside.
+__device__ __forceinline__ int fold_z(double& ez, const double sz, const double4& pa, const double4& pb, bool& clear) {
+    const int nb = fold_z(ez, pa, pb, clear);
+    const double za = pa.w * pa.z, zb = pb.w * pb.z;
+    clear = clear && sz >= fmin(za, zb) && sz <= fmax(za, zb);
+    return nb;
+}
 
 // One cell of the walk: traceIntet (query/ConvexQuery.cu:32-131) on a polyhedral cell.
 // Exit through the face slot with the smallest admissible dT in (tol, 1]; the slot we came in

@@ -33,3 +33,18 @@ def test_step_kernel_resources():
     assert len(vertex) == 32 and all(n.endswith((", 0>", ", 1>")) for n in vertex)
     v0 = vertex["void cpf::step_kernel_stream_vertex<false, true, false, false, 0>"]
     assert int(v0[1]) <= 128 and int(v0[4]) == 0 and int(v0[8]) <= 160 * 1024 // 16, v0       # (LDS: + three cells' cone rows)
+    # ... and all eight instantiations a run without frames and counters launches, <*, *, false, false, *> (__launch_bounds__ asks
+    # for CPF_STREAM_WAVES_VERTEX waves of these only): no scratch, no VGPR spills, <= 128 VGPRs -- 4 waves per SIMD, 16 single-wave
+    # workgroups per CU -- and the LDS that lets 16 of them share a CU's 160 KB.  One does not: with the kick, reflecting walls and the
+    # fixed lookup (hit pool + six record slots + sCone's four cells of cone rows) a workgroup takes more than 10 240 B, and 14 fit,
+    # not 16.  The bound asserted for the two Brownian, reflecting entries is that true one.
+    b = ("false", "true")
+    lean = {(k, r, lf): vertex["void cpf::step_kernel_stream_vertex<%s, %s, false, false, %d>" % (b[k], b[r], lf)]
+            for k in (0, 1) for r in (0, 1) for lf in (0, 1)}
+    assert len(lean) == 8
+    for (k, r, lf), row in lean.items():
+        assert int(row[4]) == 0 and int(row[7]) == 0 and int(row[1]) <= 128, row
+        if k and r:
+            assert int(row[8]) <= 160 * 1024 // 14, row
+        if (k, r, lf) != (1, 1, 1):
+            assert int(row[8]) <= 160 * 1024 // 16, row
