@@ -140,6 +140,12 @@ SIGNATURES = {
     "cpf_mesh_quality_host": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _dbl, _int, C.POINTER(MeshQuality)]),
     "cpf_build_derived_mesh_host": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cpf_cells_to_parent_dev": (_int, [_ctx, _vp, _vp, _i64]),
+    "cpf_get_cell_volumes": (_int, [_ctx, _vp]),
+    "cpf_cell_volumes_host": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp]),
+    "cpf_occupancy_sample": (_int, [_ctx]),
+    "cpf_occupancy_sample_dev": (_int, [_ctx, _vp, _i64]),
+    "cpf_occupancy_reset": (_int, [_ctx]),
+    "cpf_get_occupancy": (_int, [_ctx, _vp, C.POINTER(_i64)]),
     "cpf_set_velocity": (_int, [_ctx, _vp, _i64]),
     "cpf_set_velocity_dev": (_int, [_ctx, _vp, _i64]),
     "cpf_alloc_particles": (_int, [_ctx, _i64]),

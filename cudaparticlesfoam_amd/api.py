@@ -227,6 +227,38 @@ class Context:
     def cell_histogram_dev(self, cell, n, scale, weights):
         self._ck(self.lib.cpf_cell_histogram_dev(self.h, cell, n, scale, weights))
 
+    # -- per-cell occupancy: the concentration field (include/cpf.h "per-cell occupancy")
+    def occupancy_sample(self):
+        """One sample of the context-owned cloud: every cell's accumulator grows by the number of particles in it now."""
+        self._ck(self.lib.cpf_occupancy_sample(self.h))
+
+    def occupancy_sample_dev(self, cell_ptr, n):
+        """The same from a device int32 array of DERIVED ids (what ``step_dev`` leaves in its cell array)."""
+        self._ck(self.lib.cpf_occupancy_sample_dev(self.h, cell_ptr, n))
+
+    def occupancy_reset(self):
+        self._ck(self.lib.cpf_occupancy_reset(self.h))
+
+    def occupancy(self):
+        """(counts uint64 [n_cells] per parent cell, n_samples) accumulated since the last reset; synchronises."""
+        counts = np.zeros(self.n_cells, np.uint64)
+        ns = C.c_int64(0)
+        self._ck(self.lib.cpf_get_occupancy(self.h, _ptr(counts), C.byref(ns)))
+        return counts, ns.value
+
+    def cell_volumes(self) -> np.ndarray:
+        """OpenFOAM's cell volumes of the mesh as given ([n_cells], parent cells; cpf_get_cell_volumes)."""
+        V = np.empty(self.n_cells, np.float64)
+        self._ck(self.lib.cpf_get_cell_volumes(self.h, _ptr(V)))
+        return V
+
+    def concentration(self) -> np.ndarray:
+        """Time-averaged particles per unit volume in every cell: counts / (n_samples * V)."""
+        counts, ns = self.occupancy()
+        if ns == 0:
+            raise ValueError("concentration: no occupancy sample yet (occupancy_sample)")
+        return counts.astype(np.float64) / (float(ns) * self.cell_volumes())
+
     def cell_ranges_dev(self, weights, n_ranks, cell_lo):
         self._ck(self.lib.cpf_cell_ranges_dev(self.h, weights, n_ranks, cell_lo))
 
@@ -347,6 +379,18 @@ def mesh_quality_host(mesh, tol: float = L.NONPLANAR_TOL, split: bool = True):
     return _quality_dict(q)
 
 
+def cell_volumes_host(mesh) -> np.ndarray:
+    """What ``Context.cell_volumes()`` would return after ``set_mesh(mesh)``, on the host alone (cpf_cell_volumes_host)."""
+    lib = L.load()
+    a = _mesh_args(mesh)
+    V = np.empty(mesh.n_cells, np.float64)
+    st = lib.cpf_cell_volumes_host(_ptr(a[0]), mesh.n_points, _ptr(a[1]), _ptr(a[2]), mesh.n_faces, _ptr(a[3]), _ptr(a[4]),
+                                   mesh.n_internal, mesh.n_cells, _ptr(V))
+    if st != L.CPF_OK:
+        raise L.CpfError(st, "cpf_cell_volumes_host")
+    return V
+
+
 def build_derived_mesh_host(mesh, tol: float = L.NONPLANAR_TOL):
     """The mesh ``Context.set_mesh(mesh)`` walks (cpf_build_derived_mesh_host): (PolyMesh of the derived mesh, first
     [n_cells + 1] -- the derived cells of parent c are first[c] .. first[c+1] --, apex points [n_decomposed][3])."""
@@ -413,12 +457,30 @@ DICT_DEFAULTS = dict(                       # src/initCuda.H:49-57 (getOrDefault
     dt=1e-4, diffusionCoeff=5.7e-6, saveInterval=10)
 
 
+def _next_chunk(step: int, remaining: int, save_interval: int, occupancy_interval: int, has_writer: bool,
+                will_write: bool) -> int:
+    """Cycles the next launch of ``CudaParticles.advect`` fuses: a cycle that writes a frame runs alone; otherwise everything up
+    to the next output point (with a writer), the next occupancy sample (``occupancy_interval`` > 0) and the end of the call."""
+    if will_write:
+        return 1
+    chunk = remaining
+    if has_writer:
+        chunk = min(chunk, save_interval - (step % save_interval))
+    if occupancy_interval > 0:
+        chunk = min(chunk, occupancy_interval - (step % occupancy_interval))
+    return max(1, chunk)
+
+
 class CudaParticles:
     """What ``initCuda.H`` sets up and ``advect.H`` advances, for one solver process.
 
     ``writer(step, xyzw, vel, cell)`` is called with the cadence of
     ``writeParticles2VTU`` (frame 0 at init, then ``step % saveInterval == 0`` or at
     ``endTime``, src/initCuda.H:201, src/advect.H:166-169).
+
+    One dictionary key is this library's own, not the reference's: ``occupancyInterval`` (cycles; default 0 = off).  When
+    positive, every cycle count that is a multiple of it adds one sample to the per-cell occupancy on the device
+    (``Context.occupancy_sample``), and ``concentration()`` gives the time-averaged concentration field.
     """
 
     def __init__(self, mesh, U, particle_dict: Optional[dict] = None, device: int = 0,
@@ -431,6 +493,7 @@ class CudaParticles:
         self.dt = float(d["dt"])
         self.diffusionCoeff = float(d["diffusionCoeff"])
         self.saveInterval = int(d["saveInterval"])
+        self.occupancyInterval = int(d.get("occupancyInterval", 0))     # this library's own key (not in DICT_DEFAULTS)
         self.seedingBox = d["seedingBox"]
         # hard-coded switches of the fragment (src/initCuda.H:64-72)
         self.usingAdvection = True
@@ -483,22 +546,25 @@ class CudaParticles:
         while done < n_cycles:                                                         # advect.H:86
             will_write = self.writer is not None and (
                 self.step % self.saveInterval == 0 or run_time_value == self.particleEndTime)
-            if will_write:
-                chunk = 1
-            else:
-                # cycles until the next output point run inside ONE launch (U is frozen during the loop)
-                to_next = self.saveInterval - (self.step % self.saveInterval) if self.writer is not None else n_cycles
-                chunk = max(1, min(n_cycles - done, to_next))
+            # cycles until the next output point run inside ONE launch (U is frozen during the loop)
+            chunk = _next_chunk(self.step, n_cycles - done, self.saveInterval, self.occupancyInterval,
+                                self.writer is not None, will_write)
             flags = self._flags(will_write) | (L.STEP_FUSE_CYCLES if chunk > 1 else 0)
             self.ctx.step(cycle_dt, D, chunk, flags)
             if will_write:                                                             # advect.H:166-169
                 self._write(self.step + 1)
             self.step += chunk                                                         # advect.H:182
             done += chunk
+            if self.occupancyInterval > 0 and self.step % self.occupancyInterval == 0:
+                self.ctx.occupancy_sample()
         return n_cycles
 
     def particles(self):
         return self.ctx.get_particles()
+
+    def concentration(self):
+        """Time-averaged concentration per cell from the samples ``occupancyInterval`` took (``Context.concentration``)."""
+        return self.ctx.concentration()
 
     def close(self):
         self.ctx.close()

@@ -52,6 +52,10 @@ struct Mesh {
     std::vector<int32_t> first;         // [nParent+1] derived cells of parent c: first[c] .. first[c+1] (decomposed meshes only)
     DevBuf<int32_t> parentOf;           // [host.nCells] parent of every derived cell; null: no cell decomposed
     DevBuf<double> Uparent;             // [nParent][3] staging of cpf_set_velocity on a decomposed mesh
+    std::vector<double> volume;         // [nParent] OpenFOAM's cell volumes of the mesh as given (cpf_get_cell_volumes)
+    // per-cell occupancy (cpf_occupancy_sample*; cpf_occupancy.hip): it belongs to the mesh and goes with it
+    DevBuf<unsigned long long> occupancy;   // [nParent] accumulated counts; null until the first sample
+    int64_t occupancySamples = 0;           // samples added since the last reset
 };
 
 // "VertexVelocity" advect only: the tet decomposition and one velocity per tet-mesh vertex.  It belongs to the mesh it was made
@@ -313,6 +317,7 @@ int setMeshImpl(cpf_context* ctx, const double* points, int64_t nPoints, const L
     ctx->mesh.host = std::move(t);
     ctx->mesh.nParent = nCells;
     ctx->mesh.quality = toQuality(q, ctx->mesh.host.nCells);
+    ctx->mesh.volume = std::move(q.volume);
     nCells = ctx->mesh.host.nCells;                         // from here on: the cells the walk runs on
     const cpf::HostTables& h = ctx->mesh.host;
     auto up = [&](auto& buf, const auto& src) -> hipError_t {      // (planes: four doubles of `src` per element of `buf`)
@@ -736,6 +741,25 @@ int cpf_build_derived_mesh_host(const double* points, int64_t nPoints, const int
         if (first) std::memcpy(first, dm.first.data(), dm.first.size() * 4);
         return CPF_OK;
     });
+}
+
+int cpf_cell_volumes_host(const double* points, int64_t nPoints, const int32_t* faceOffsets, const int32_t* faceVerts,
+                          int64_t nFaces, const int32_t* owner, const int32_t* neighbour, int64_t nInternal, int64_t nCells, double* V) {
+    return hostMesh(points, faceOffsets, faceVerts, owner, neighbour, nInternal, V != nullptr, [&] {
+        cpf::MeshQuality q;
+        if (!cpf::measure_mesh<int32_t>(points, nPoints, faceOffsets, faceVerts, nFaces, owner, neighbour, nInternal, nCells,
+                                        cpf::kNonPlanarTolDefault, q).empty())
+            return CPF_ERR_MESH;
+        std::memcpy(V, q.volume.data(), q.volume.size() * 8);
+        return CPF_OK;
+    });
+}
+
+int cpf_get_cell_volumes(const cpf_context* ctx, double* V) {
+    CPF_REQUIRE(ctx, ctx && V, CPF_ERR_ARG, "null argument");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_get_cell_volumes: call cpf_set_mesh first");
+    std::memcpy(V, ctx->mesh.volume.data(), ctx->mesh.volume.size() * 8);
+    return CPF_OK;
 }
 
 int cpf_get_mesh_quality(const cpf_context* ctx, cpf_mesh_quality* out) {
@@ -1291,6 +1315,53 @@ int cpf_cell_histogram_dev(cpf_context* ctx, const int32_t* cell, int64_t n, dou
     if (r != CPF_OK) return r;
     CPF_HIP(ctx, cpf::cell_histogram(ctx->stream, cell, n, ctx->mesh.host.nCells, scale, weights_dev, ctx->scratch,
                                      ctx->scratchBytes));
+    return CPF_OK;
+}
+
+int cpf_occupancy_sample_dev(cpf_context* ctx, const int32_t* cell, int64_t n) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_occupancy_sample: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, n >= 0 && (cell || n == 0), CPF_ERR_ARG, "cpf_occupancy_sample_dev: bad arguments");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->mesh.occupancy) {                          // first use: allocated and zeroed
+        DevBuf<unsigned long long> acc;
+        CPF_HIP(ctx, acc.alloc((size_t)ctx->mesh.nParent));
+        CPF_HIP(ctx, hipMemsetAsync(acc, 0, (size_t)ctx->mesh.nParent * 8, ctx->stream));
+        ctx->mesh.occupancy = std::move(acc);
+        ctx->mesh.occupancySamples = 0;
+    }
+    CPF_HIP(ctx, cpf::occupancy_accumulate(ctx->stream, cell, n, ctx->mesh.parentOf, ctx->mesh.host.nCells, ctx->mesh.occupancy));
+    ++ctx->mesh.occupancySamples;
+    return CPF_OK;
+}
+
+int cpf_occupancy_sample(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_occupancy_sample: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_occupancy_sample: no located particles");
+    return cpf_occupancy_sample_dev(ctx, ctx->cloud.cur.cell, ctx->cloud.n);
+}
+
+int cpf_occupancy_reset(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    ctx->mesh.occupancySamples = 0;
+    if (ctx->mesh.occupancy) {
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        CPF_HIP(ctx, hipMemsetAsync(ctx->mesh.occupancy, 0, (size_t)ctx->mesh.nParent * 8, ctx->stream));
+    }
+    return CPF_OK;
+}
+
+int cpf_get_occupancy(cpf_context* ctx, uint64_t* counts, int64_t* nSamples) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_get_occupancy: call cpf_set_mesh first");
+    if (nSamples) *nSamples = ctx->mesh.occupancySamples;
+    if (counts && !ctx->mesh.occupancy) std::memset(counts, 0, (size_t)ctx->mesh.nParent * 8);      // before any sample
+    if (ctx->mesh.occupancy) {
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        if (counts) CPF_HIP(ctx, hipMemcpyAsync(counts, ctx->mesh.occupancy, (size_t)ctx->mesh.nParent * 8, hipMemcpyDeviceToHost, ctx->stream));
+        CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
     return CPF_OK;
 }
 

@@ -276,6 +276,10 @@ size_t histogram_scratch_bytes(int64_t nCells);
 hipError_t cell_histogram(hipStream_t st, const int32_t* cell, int64_t n, int64_t nCells, double scale, double* weights,
                           void* scratch, size_t scratchBytes);
 hipError_t cell_ranges(hipStream_t st, const double* weights, int64_t nCells, int nRanks, int32_t* cellLo);
+// per-cell occupancy (cpf_occupancy.hip): acc[parent of cell[i]] += 1 for every i with 0 <= cell[i] < nDerived, in place, one launch;
+// parentOf null: the ids are parent ids already.  acc: 64-bit integers per PARENT cell
+hipError_t occupancy_accumulate(hipStream_t st, const int32_t* cell, int64_t n, const int32_t* parentOf, int64_t nDerived,
+                                unsigned long long* acc);
 hipError_t unpack_arrivals(hipStream_t st, double* x, double* y, double* z, int32_t* cell, int64_t* gid,
                            int64_t nStay, const double* recvbuf, int64_t nRecv);
 // output of a sharded cloud (cpf_shard_gather): records of kOutputDoubles doubles = x, y, z, cell, gid, vx, vy, vz

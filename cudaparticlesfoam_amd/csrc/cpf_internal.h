@@ -63,6 +63,7 @@ struct MeshQuality {
     int64_t worstFace = -1, worstCell = -1, nCells = 0, nFlagged = 0, nBad = 0;
     std::vector<char> flagged;          // [nCells]
     std::vector<double> centre;         // [nCells][3]  OpenFOAM's cell centres (the apexes)
+    std::vector<double> volume;         // [nCells]     ... and cell volumes (mesh.V(); cpf_get_cell_volumes)
     std::vector<int64_t> cellOff, cellFaces;   // mesh.cells(): owned faces ascending, then neighbour faces ascending
     int64_t nSplit() const { return nFlagged - nBad; }
     // Decompose only when EVERY flagged cell has a positive fan: a flagged cell left whole next to decomposed ones would see

@@ -549,6 +549,7 @@ std::string measure_mesh(const double* points, int64_t nPoints, const Label* fac
         q.centre[3 * c] = C.x; q.centre[3 * c + 1] = C.y; q.centre[3 * c + 2] = C.z;
         vol[(size_t)c] = V / 3.0;
     }
+    q.volume = vol;
     // non-convexity xi_c = (largest distance of a vertex of the cell outside one of its own face planes) / cbrt(volume), the
     // flag rule, and which flagged cells have a fan of positive tets (star-shaped from the centre)
     q.flagged.assign((size_t)nCells, 0);

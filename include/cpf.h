@@ -233,6 +233,16 @@ int cpf_build_derived_mesh_host(const double* points, int64_t nPoints, const int
  * out may alias.  Asynchronous on the context stream.  A copy on meshes without decomposed cells. */
 int cpf_cells_to_parent_dev(cpf_context* ctx, const int32_t* in, int32_t* out, int64_t n);
 
+/* Cell volumes of the mesh as the caller gave it, V[nCells] per PARENT cell: OpenFOAM's mesh.V() (primitiveMeshCellCentresAndVols:
+ * the pyramids from every face to the face-centre average of the cell), which the mesh layer computes for the quality measure and
+ * keeps.  NO REFERENCE COUNTERPART (the reference never asks for a volume); what cpf_get_occupancy's counts are divided by to give
+ * a concentration.  cpf_cell_volumes_host: the same on the host alone, no context, no GPU; CPF_ERR_MESH for a mesh cpf_set_mesh
+ * would refuse. */
+int cpf_get_cell_volumes(const cpf_context* ctx, double* V /* [nCells] */);
+int cpf_cell_volumes_host(const double* points, int64_t nPoints, const int32_t* faceOffsets, const int32_t* faceVerts,
+                          int64_t nFaces, const int32_t* owner, const int32_t* neighbour, int64_t nInternal, int64_t nCells,
+                          double* V /* [nCells] */);
+
 /* Cell-constant velocity U[nCells][3] (host, zero-copy from U.primitiveField()).  Replaces the
  * 12x replication loop + cudaUpdateVelocity of src/advect.H:44-57 (cuda/particles.cu:718-749):
  * nCells*24 B cross PCIe instead of 12*nCells*24 B. */
@@ -365,6 +375,31 @@ int cpf_set_option(cpf_context* ctx, const char* key, double value);
  * the streaming kernel), as a profiler prints it (e.g. "cpf::step_kernel_stream<false, true, false, false, 0>"):
  * lets a benchmark label its roofline with what actually ran. */
 int cpf_step_kernel_name(cpf_context* ctx, double D, unsigned flags, char* buf, size_t bufBytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * per-cell occupancy: the concentration field of the tracer, accumulated on the device
+ * NO REFERENCE COUNTERPART for any entry of this group: the reference hands particles out (writeParticles2VTU, cuda/utils.cpp:
+ * 144-283) and leaves the binning to the post-processor.  Here a sample is one kernel over the 4-byte cell ids and the field is
+ * 8 bytes per cell, instead of 36 bytes per particle across PCIe.
+ * The accumulators are 64-bit INTEGERS per PARENT cell: integer sums do not depend on the order in which they arrive, so the
+ * counts are the same bits from run to run and whatever the order of the cloud.  They belong to a mesh: cpf_set_mesh* drops them.
+ * concentration[c] = counts[c] / (nSamples * V[c]), V from cpf_get_cell_volumes.
+ * ------------------------------------------------------------------------------------------- */
+/* NO REFERENCE COUNTERPART.  One sample of the context-owned cloud: for every cell, the number of particles that claim it now
+ * (cell >= 0; CPF_CELL_LOST, CPF_CELL_FROZEN and any other negative id are skipped) is added to the cell's accumulator, and the
+ * sample count goes up by one.  Asynchronous on the context's stream; the accumulators are allocated and zeroed at first use.
+ * CPF_ERR_STATE without a mesh or without located particles. */
+int cpf_occupancy_sample(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  The same from a caller-owned device array of DERIVED ids (the convention of the other _dev entries:
+ * what cpf_step_dev leaves in its cell array; ids that are not cells of the mesh are skipped like negative ones).  A host with a
+ * sharded cloud samples each rank's slice (cpf_shard_arrays) on that rank's context and sums the ranks' counts itself.  n == 0
+ * is legal and still counts a sample. */
+int cpf_occupancy_sample_dev(cpf_context* ctx, const int32_t* cell, int64_t n);
+/* NO REFERENCE COUNTERPART.  Zeroes the accumulators and the sample count (asynchronous on the context's stream). */
+int cpf_occupancy_reset(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  Waits for the context's stream and copies out: counts[nCells] per PARENT cell (nullable), *nSamples
+ * (nullable) = samples since the last reset.  Before any sample: zeros and 0. */
+int cpf_get_occupancy(cpf_context* ctx, uint64_t* counts, int64_t* nSamples);
 
 /* ---------------------------------------------------------------------------------------------
  * device-array level (framework hosts that own the particle arrays, multi-GPU sharding)
