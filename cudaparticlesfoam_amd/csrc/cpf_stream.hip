@@ -110,7 +110,7 @@ constexpr int kKernArgStep0 = (int)offsetof(StreamKernArgs, step0), kKernArgSeed
 // the zero-denominator vote per face in the flat walk: off -- a 2-D mesh whose side faces are exactly parallel to everybody's
 // displacement is a mesh of boxes in axis-aligned flow; pitzDaily's trapezoids never are, and the vote costs the headline 2.3 %
 // (0.1048-0.1063 -> 0.1032-0.1033 ms, analytic field 0.0986-0.0999 -> 0.0985-0.0986).  Same results either way.
-// the flat walk under the Brownian kick (cpf_walk.h, trace_lds4_flat_z): 0 = off (A/B builds)
+// the flat walk under the Brownian kick (cpf_walk.h, trace_lds4_flat<.., KEEP_Z>): 0 = off (A/B builds)
 #ifndef CPF_STREAM_FLAT_KICK
 #define CPF_STREAM_FLAT_KICK 0
 #endif
@@ -315,7 +315,7 @@ __device__ __forceinline__ void stream_body(
     const bool zFold = !BOX && BROWNIAN && REFLECT && m.zThin != 0;      // (stream_lookup_mode: no box records on a mesh one cell thick)
     const bool zLast = !FLAT && !BROWNIAN && m.zPairLast != 0;   // (with the kick every particle moves in z: the test would be wasted)
     // the kick on a one-cell-thick mesh whose side faces have nz == 0 exactly: the four side faces with two-term dot products
-    // whenever every lane's mirrored end point is clear of the z planes (cpf_walk.h, trace_lds4_flat_z)
+    // whenever every lane's mirrored end point is clear of the z planes (cpf_walk.h, trace_lds4_flat<.., KEEP_Z>)
     const bool flatKick = zFold && m.zSide0 != 0;
     // tile and chunk numbers are 32-bit (the launcher refuses clouds of 2^31 tiles = 1.4e11 particles): half the scalar
     // registers and none of the 64-bit multiply sequences of the first version.  Chunk numbers past the end of the cloud
@@ -848,7 +848,7 @@ __device__ __forceinline__ void stream_body(
                             if (BOX) next = trace_box<!BROWNIAN, mixed>(S_, E, cur, rec, token, outSlot);
                             else if (FLAT) next = trace_lds4_flat<(CPF_STREAM_FLAT_ZERO_SKIP != 0)>(S_, E, cur, rec, token, outSlot);
                             else if (CPF_STREAM_FLAT_KICK && BROWNIAN && !mixed && flatKick && !zUnclear)
-                            next = trace_lds4_flat_z<false>(S_, E, cur, rec, token, outSlot);     // (cpf_walk.h: flat walk under the kick)
+                            next = trace_lds4_flat<false, true>(S_, E, cur, rec, token, outSlot);     // (cpf_walk.h: flat walk under the kick)
                             else
                             next = (CPF_STREAM_PAIRED && LOOKUP_FIXED && !BROWNIAN && !mixed) ? trace_lds6_paired(S_, E, cur, rec, token, outSlot, zLast)
                                                                 : trace_lds6<(!BROWNIAN && (CPF_STREAM_L1_ZERO_SKIP || LOOKUP != kLookupFixed)), mixed>(S_, E, cur, rec, token, outSlot, zLast, zFold && !zUnclear);

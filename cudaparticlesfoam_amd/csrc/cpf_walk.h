@@ -2,6 +2,7 @@
 // cell visit in its three data-source flavours, the Philox/Box-Muller deviates and the statistics reduction.
 // Arithmetic contract: see the head of cpf_kernels.hip (explicit fma() only, -ffp-contract=off, IEEE division).
 #pragma once
+#include "cpf_accept.h"      // kTol, is_group, face_accept: the acceptance rule itself
 #include "cpf_device.h"
 
 namespace cpf {
@@ -29,22 +30,12 @@ __device__ __forceinline__ D3 axpy(double s, const D3& a, const D3& b) {
     return {fma(s, a.x, b.x), fma(s, a.y, b.y), fma(s, a.z, b.z)};
 }
 
-constexpr double kTol = 1e-13;     // query/ConvexQuery.cu:42
 constexpr int kMaxHops = 50;       // query/ConvexQuery.cu:169
 constexpr int kMaxReflect = 5;     // query/ConvexQuery.cu:353
 
-// FACE GROUPS (cpf_mesh.cpp): the coplanar faces of a cell -- the pieces of a face split by a 2:1 refinement next door --
-// share ONE slot, whose neighbour code names the group.  Two additions to the reference's rule, only where a slot is a
-// group (no reference semantics exist for such cells, src/initCuda.H:64: hexes only; stated independently in
-// oracle/cellwalk.c):
-//   1. OUTWARD CROSSINGS ONLY (den < 0).  A particle that came in through one piece sits on the group's plane, a rounding
-//      error outside it (fd = +4e-16), moving inward: the reference's acceptance test takes that for an exit at
-//      dT ~ 2e-13 > tol, and the token cannot skip the slot (it names the piece's cell, not the group).  A convex cell
-//      is left against the face's inward normal, so den < 0 loses no real exit.
-//   2. the cell entered is chosen at the exit point X: the piece whose CELL holds X best -- the smallest maximum, over
-//      that cell's slots, of X's signed plane distance; the first piece on equal scores (resolve_group; a rare path:
-//      per-lane reads of the CSR tables).
-__device__ __forceinline__ bool is_group(int nb) { return nb < -(1 << 30); }
+// FACE GROUPS, rule 2 (cpf_accept.h): the cell entered through a group slot is chosen at the exit point X -- the piece whose
+// CELL holds X best: the smallest maximum, over that cell's slots, of X's signed plane distance; the first piece on equal
+// scores (a rare path: per-lane reads of the CSR tables).
 __device__ __forceinline__ int resolve_group(int code, const D3& X, const int32_t* __restrict__ cellOff, const double4* __restrict__ planes,
                                              const int32_t* __restrict__ groupOff, const int32_t* __restrict__ groupNbr) {
     const int g = code - kGroupBase;
@@ -106,40 +97,6 @@ __device__ __forceinline__ int fold_z(double& ez, const double sz, const double4
     const double za = pa.w * pa.z, zb = pb.w * pb.z;
     clear = clear && sz >= fmin(za, zb) && sz <= fmax(za, zb);
     return nb;
-}
-
-// One cell of the walk: traceIntet (query/ConvexQuery.cu:32-131) on a polyhedral cell.
-// Exit through the face slot with the smallest admissible dT in (tol, 1]; the slot we came in
-// through (nbr == token) is skipped.  Returns the next cell (== cur: segment ends here; < 0:
-// boundary code) and advances S to the exit point.
-__device__ __forceinline__ int trace_in_cell(D3& S, const D3& E, int cur, const MeshView& m, int token,
-                                             int& outSlot) {
-    const D3 P0 = S;
-    const D3 Pd = {E.x - P0.x, E.y - P0.y, E.z - P0.z};
-    int next = cur, best = -1;
-    double dTmin = 1.1;
-    const int s0 = m.cellOff[cur], s1 = m.cellOff[cur + 1];
-    for (int s = s0; s < s1; ++s) {
-        const double4 pl = m.planes[s];
-        const double fd = plane_dist(pl, P0);           // (Cf - P0).n  (<= 0 inside)
-        const double den = dot3(pl, Pd);
-        double dT = fd / den;
-        if (__builtin_isinf(dT)) dT = -1.0;             // segment parallel to the face
-        const int nb = m.nbr[s];
-        if (nb == token) continue;
-        if (is_group(nb) && !(den < 0.0)) continue;     // face groups: outward crossings only (see above)
-        if (fd < kTol && dT > kTol && dT <= 1.0 && dT < dTmin) {
-            dTmin = dT;
-            next = nb;
-            S = axpy(dT, Pd, P0);
-            best = s;
-        }
-    }
-    if (best >= 0) {
-        if (is_group(next)) next = resolve_group(next, S, m.cellOff, m.planes, m.groupOff, m.groupNbr);
-        outSlot = best;
-    }
-    return next;
 }
 
 // Same test for meshes whose cells all have NF faces (every mesh the reference can run is all-hex,
@@ -215,29 +172,22 @@ __device__ __forceinline__ int trace_fixed(D3& S, const D3& E, int cur, const do
 // chain, not by instruction issue).
 // ZERO_SKIP: try the zero-denominator skip at all -- pointless (a compare and a branch per face) once every particle
 // has a displacement along every axis, i.e. with the Brownian kick; results are the same with or without it.
-template <bool ZERO_SKIP, bool GROUPS = false>
+// FLAT: the two-term den and fd of the flat walk (see below): the plane's nz == +-0 exactly and is not read.
+// The wave vote is cheap and a superset, the exact test runs only where it can matter.  A lane can be accepted only if
+// |fd| <= |den| with equal signs and fd < tol: from inside (fd < 0) that means den <= fd; every other acceptable lane has
+// fd >= 0 (on or outside the plane: the face it came in through, or an entry point rounded across a neighbouring face).
+// (den <= fd) | (fd >= 0) is therefore a superset of the candidates -- two compares per face instead of five, two scalar
+// operations instead of five -- and the exact predicate (cpf_accept.h, face_accept) decides inside the branch.
+__device__ __forceinline__ unsigned long long face_vote(double den, double fd, int bs, int token) {
+    return (ballot64(den <= fd) | ballot64(fd >= 0.0)) & __builtin_amdgcn_uicmp((unsigned)bs, (unsigned)token, 33 /* ne */);
+}
+template <bool ZERO_SKIP, bool GROUPS = false, bool FLAT = false>
 __device__ __forceinline__ void face_test(const double4& p, int bs, const D3& P0, const D3& Pd, int token, int s,
                                           double& dTmin, int& next, int& best) {
-    const double den = dot3(p, Pd);
+    const double den = FLAT ? fma(p.y, Pd.y, p.x * Pd.x) : dot3(p, Pd);
     if (ZERO_SKIP && ballot64(den != 0.0) == 0ull) return;          // see trace_fixed: nobody crosses this plane
-    const double fd = plane_dist(p, P0);
-    // Cheap wave-uniform skip, exact test only where it can matter.  A lane can be accepted only if |fd| <= |den| with
-    // equal signs and fd < tol: from inside (fd < 0) that means den <= fd; every other acceptable lane has fd >= 0
-    // (on or outside the plane: the face it came in through, or an entry point rounded across a neighbouring face).
-    // (den <= fd) | (fd >= 0) is therefore a superset of the candidates -- two compares per face instead of five, two
-    // scalar operations instead of five -- and the exact predicate below decides inside the branch.
-    if (((ballot64(den <= fd) | ballot64(fd >= 0.0)) & __builtin_amdgcn_uicmp((unsigned)bs, (unsigned)token, 33 /* ne */)) != 0ull) {
-        // c2 only prunes divisions (a face the lane moves away from): "den < 0 or fd >= 0" holds whenever the exact
-        // condition "equal sign bits" can still lead to an accepted face, and whatever else slips through has a
-        // quotient <= 0 and fails dT > tol below, exactly as in the reference
-        // (GROUPS: a face-group slot is only left with den < 0 -- see "face groups" above)
-        const bool c1 = fabs(fd) <= fabs(den), c2 = den < 0.0 || (fd >= 0.0 && !(GROUPS && is_group(bs)));
-        const bool c3 = fd < kTol, c4 = bs != token;
-        if (c1 && c2 && c3 && c4) {
-            const double dT = fd / den;
-            if (dT > kTol && dT < dTmin) { dTmin = dT; next = bs; best = s; }
-        }
-    }
+    const double fd = FLAT ? fma(-p.y, P0.y, fma(-p.x, P0.x, p.w)) : plane_dist(p, P0);
+    if (face_vote(den, fd, bs, token) != 0ull) face_accept<GROUPS>(den, fd, bs, token, s, dTmin, next, best);
 }
 
 // The plane offsets are requested together with the normals (the empty asm pins them): left alone, the compiler sinks
@@ -245,6 +195,14 @@ __device__ __forceinline__ void face_test(const double4& p, int bs, const D3& P0
 // chain per pair.  Measured at steady clocks: 1-2 % on the 3-D meshes (no face is skipped there before its offset is
 // needed), nothing either way on pitzDaily.
 #define CPF_PIN_W(a, b) asm volatile("" : "+v"(a.w), "+v"(b.w));
+// ONE PAIR of a cell record (see "cell records" below): the two face tests of slots s and s + 1, whose planes and int2 of
+// neighbours the caller has just fetched -- in its own straight-line code, which is what keeps the two LDS reads together.
+template <bool ZERO_SKIP, bool GROUPS, bool FLAT = false>
+__device__ __forceinline__ void record_pair(double4& pa, double4& pb, const int2 b, int s, const D3& P0, const D3& Pd, int token, double& dTmin, int& next, int& best) {
+    CPF_PIN_W(pa, pb)
+    face_test<ZERO_SKIP, GROUPS, FLAT>(pa, b.x, P0, Pd, token, s, dTmin, next, best);
+    face_test<ZERO_SKIP, GROUPS, FLAT>(pb, b.y, P0, Pd, token, s + 1, dTmin, next, best);
+}
 // zLast (wave-uniform; MeshView::zPairLast): slots 4 and 5 are the cell's two faces with an exactly z-parallel normal.
 // When no active lane moves in z (Pd.z == +-0 exactly: 2-D flow on a z-extruded mesh, no diffusion) both denominators
 // are exactly +-0 for every lane -- nx == ny == 0 leaves den = nz * 0 -- so neither face can be accepted
@@ -260,26 +218,10 @@ __device__ __forceinline__ int trace_lds6(D3& S, const D3& E, int cur, const dou
     int next = cur, best = -1;
     double dTmin = 2.0;                 // any start value > 1 is equivalent (candidates have dT <= 1); 2.0 is an inline constant
     const int2* nb = reinterpret_cast<const int2*>(rec + 7);
-    {
-        double4 p0 = rec[0], p1 = rec[1];
-        const int2 b = nb[0];
-        CPF_PIN_W(p0, p1)
-        face_test<ZERO_SKIP, GROUPS>(p0, b.x, P0, Pd, token, 0, dTmin, next, best);
-        face_test<ZERO_SKIP, GROUPS>(p1, b.y, P0, Pd, token, 1, dTmin, next, best);
-    }
-    {
-        double4 p2 = rec[2], p3 = rec[3];
-        const int2 b = nb[1];
-        CPF_PIN_W(p2, p3)
-        face_test<ZERO_SKIP, GROUPS>(p2, b.x, P0, Pd, token, 2, dTmin, next, best);
-        face_test<ZERO_SKIP, GROUPS>(p3, b.y, P0, Pd, token, 3, dTmin, next, best);
-    }
+    { double4 p0 = rec[0], p1 = rec[1]; record_pair<ZERO_SKIP, GROUPS>(p0, p1, nb[0], 0, P0, Pd, token, dTmin, next, best); }
+    { double4 p2 = rec[2], p3 = rec[3]; record_pair<ZERO_SKIP, GROUPS>(p2, p3, nb[1], 2, P0, Pd, token, dTmin, next, best); }
     if (!(zNever || (zLast && ballot64(Pd.z != 0.0) == 0ull))) {
-        double4 p4 = rec[4], p5 = rec[5];
-        const int2 b = nb[2];
-        CPF_PIN_W(p4, p5)
-        face_test<ZERO_SKIP, GROUPS>(p4, b.x, P0, Pd, token, 4, dTmin, next, best);
-        face_test<ZERO_SKIP, GROUPS>(p5, b.y, P0, Pd, token, 5, dTmin, next, best);
+        double4 p4 = rec[4], p5 = rec[5]; record_pair<ZERO_SKIP, GROUPS>(p4, p5, nb[2], 4, P0, Pd, token, dTmin, next, best);
     }
     if (best >= 0) {
         S = axpy(dTmin, Pd, P0);
@@ -297,27 +239,9 @@ __device__ __forceinline__ int trace_lds6(D3& S, const D3& E, int cur, const dou
 template <bool ZERO_SKIP, bool GROUPS>
 __device__ __forceinline__ void trace_lds6_record(const D3& P0, const D3& Pd, const double4* rec, int token, int base, double& dTmin, int& next, int& best) {
     const int2* nb = reinterpret_cast<const int2*>(rec + 7);
-    {
-        double4 p0 = rec[0], p1 = rec[1];
-        const int2 b = nb[0];
-        CPF_PIN_W(p0, p1)
-        face_test<ZERO_SKIP, GROUPS>(p0, b.x, P0, Pd, token, base + 0, dTmin, next, best);
-        face_test<ZERO_SKIP, GROUPS>(p1, b.y, P0, Pd, token, base + 1, dTmin, next, best);
-    }
-    {
-        double4 p2 = rec[2], p3 = rec[3];
-        const int2 b = nb[1];
-        CPF_PIN_W(p2, p3)
-        face_test<ZERO_SKIP, GROUPS>(p2, b.x, P0, Pd, token, base + 2, dTmin, next, best);
-        face_test<ZERO_SKIP, GROUPS>(p3, b.y, P0, Pd, token, base + 3, dTmin, next, best);
-    }
-    {
-        double4 p4 = rec[4], p5 = rec[5];
-        const int2 b = nb[2];
-        CPF_PIN_W(p4, p5)
-        face_test<ZERO_SKIP, GROUPS>(p4, b.x, P0, Pd, token, base + 4, dTmin, next, best);
-        face_test<ZERO_SKIP, GROUPS>(p5, b.y, P0, Pd, token, base + 5, dTmin, next, best);
-    }
+    { double4 p0 = rec[0], p1 = rec[1]; record_pair<ZERO_SKIP, GROUPS>(p0, p1, nb[0], base + 0, P0, Pd, token, dTmin, next, best); }
+    { double4 p2 = rec[2], p3 = rec[3]; record_pair<ZERO_SKIP, GROUPS>(p2, p3, nb[1], base + 2, P0, Pd, token, dTmin, next, best); }
+    { double4 p4 = rec[4], p5 = rec[5]; record_pair<ZERO_SKIP, GROUPS>(p4, p5, nb[2], base + 4, P0, Pd, token, dTmin, next, best); }
 }
 
 // FLAT WALK (MeshView::zSide0 + a velocity field without a z component + no Brownian kick: a 2-D case as both tutorials'
@@ -327,22 +251,7 @@ __device__ __forceinline__ void trace_lds6_record(const D3& P0, const D3& Pd, co
 // every lane and are never accepted (the zLast shortcut of trace_lds6, here decided at launch instead of per round), and a
 // side face's den = fma(nz, Pd.z, t) = t and fd = fma(-nz, P0.z, u) = u up to the sign of a zero result, which no comparison
 // sees -- two FMAs per face that need not be issued, a vote and a branch per round that need not be taken, and no z in the walk.
-template <bool ZERO_SKIP>
-__device__ __forceinline__ void face_test_flat(const double4& p, int bs, const D3& P0, const D3& Pd, int token, int s,
-                                               double& dTmin, int& next, int& best) {
-    const double den = fma(p.y, Pd.y, p.x * Pd.x);
-    if (ZERO_SKIP && ballot64(den != 0.0) == 0ull) return;
-    const double fd = fma(-p.y, P0.y, fma(-p.x, P0.x, p.w));
-    if (((ballot64(den <= fd) | ballot64(fd >= 0.0)) & __builtin_amdgcn_uicmp((unsigned)bs, (unsigned)token, 33 /* ne */)) != 0ull) {
-        const bool c1 = fabs(fd) <= fabs(den), c2 = den < 0.0 || fd >= 0.0;
-        const bool c3 = fd < kTol, c4 = bs != token;
-        if (c1 && c2 && c3 && c4) {
-            const double dT = fd / den;
-            if (dT > kTol && dT < dTmin) { dTmin = dT; next = bs; best = s; }
-        }
-    }
-}
-// (S.z is left alone: fma(dT, +-0, P0.z) is P0.z)
+// (face_test<.., FLAT>; S.z is left alone: fma(dT, +-0, P0.z) is P0.z)
 //
 // SETTLED Z (CPF_STEP_Z_SETTLED, StreamArgs::zSettled).  What one flat cycle does to a live particle's z is a function f of z
 // alone: the advect gives Pn.z = z + dt * u.z with u.z == +-0 and dt finite (cpf_step_dev refuses any other), disp.z = Pn.z - z,
@@ -385,65 +294,28 @@ __device__ __forceinline__ void face_test_flat(const double4& p, int bs, const D
 //     x == -0, on a wall through the origin.  Only then could the sign of a stored zero differ.  No comparison reads it either.);
 //   * the velocity mirror, v' = v - 2 dot3(plane, v) n with v.z == +-0, nz == +-0: the same argument term by term; the
 //     body keeps all three components of v as they were (only a launch that stores velocities reads them at all);
-//   * no comparison of the walk reads a z or the sign of a zero (trace_lds4_flat above reads x and y only).
+//   * no comparison of the walk reads a z or the sign of a zero (trace_lds4_flat below reads x and y only).
 // What is left in memory: z untouched, the bits a streaming launch would have written (the fixed-point argument above).
-template <bool ZERO_SKIP>
-__device__ __forceinline__ int trace_lds4_flat(D3& S, const D3& E, int cur, const double4* rec, int token, int& outSlot) {
-    const D3 P0 = S;
-    const D3 Pd = {E.x - P0.x, E.y - P0.y, 0.0};
-    int next = cur, best = -1;
-    double dTmin = 2.0;
-    const int2* nb = reinterpret_cast<const int2*>(rec + 7);
-    {
-        double4 p0 = rec[0], p1 = rec[1];
-        const int2 b = nb[0];
-        CPF_PIN_W(p0, p1)
-        face_test_flat<ZERO_SKIP>(p0, b.x, P0, Pd, token, 0, dTmin, next, best);
-        face_test_flat<ZERO_SKIP>(p1, b.y, P0, Pd, token, 1, dTmin, next, best);
-    }
-    {
-        double4 p2 = rec[2], p3 = rec[3];
-        const int2 b = nb[1];
-        CPF_PIN_W(p2, p3)
-        face_test_flat<ZERO_SKIP>(p2, b.x, P0, Pd, token, 2, dTmin, next, best);
-        face_test_flat<ZERO_SKIP>(p3, b.y, P0, Pd, token, 3, dTmin, next, best);
-    }
-    if (best >= 0) {
-        S.x = fma(dTmin, Pd.x, P0.x); S.y = fma(dTmin, Pd.y, P0.y);
-        outSlot = best;
-    }
-    return next;
-}
-
-// FLAT WALK UNDER THE KICK (round 6).  With the Brownian kick every particle moves in z, so the flat walk above does not apply --
+// KEEP_Z: the flat walk under the kick, below.
+//
+// FLAT WALK UNDER THE KICK (round 6; KEEP_Z).  With the Brownian kick every particle moves in z, so the flat walk above does not apply --
 // but on a one-cell-thick mesh whose side faces have nz == 0 exactly (zThin && zSide0), once fold_z has mirrored every lane's end
 // point clear of the z planes (`zFold && !zUnclear`: the condition that already drops the z pair from trace_lds6), the four
 // side faces are all that is tested, and their dropped terms are 0 * finite: den = fma(0, Pd.z, t) = t and fd = fma(-0, P0.z, u)
 // = u up to the sign of a zero, which no comparison sees (E.z and P0.z are finite: a lane with a NaN or infinite end point is
 // never `clear`).  The exit point keeps its z: S = P0 + dT * Pd with the real Pd.z.  Same bits as trace_lds6(..., zNever = true).
-template <bool ZERO_SKIP>
-__device__ __forceinline__ int trace_lds4_flat_z(D3& S, const D3& E, int cur, const double4* rec, int token, int& outSlot) {
+template <bool ZERO_SKIP, bool KEEP_Z = false>
+__device__ __forceinline__ int trace_lds4_flat(D3& S, const D3& E, int cur, const double4* rec, int token, int& outSlot) {
     const D3 P0 = S;
-    const D3 Pd = {E.x - P0.x, E.y - P0.y, E.z - P0.z};
+    const D3 Pd = {E.x - P0.x, E.y - P0.y, KEEP_Z ? E.z - P0.z : 0.0};
     int next = cur, best = -1;
     double dTmin = 2.0;
     const int2* nb = reinterpret_cast<const int2*>(rec + 7);
-    {
-        double4 p0 = rec[0], p1 = rec[1];
-        const int2 b = nb[0];
-        CPF_PIN_W(p0, p1)
-        face_test_flat<ZERO_SKIP>(p0, b.x, P0, Pd, token, 0, dTmin, next, best);
-        face_test_flat<ZERO_SKIP>(p1, b.y, P0, Pd, token, 1, dTmin, next, best);
-    }
-    {
-        double4 p2 = rec[2], p3 = rec[3];
-        const int2 b = nb[1];
-        CPF_PIN_W(p2, p3)
-        face_test_flat<ZERO_SKIP>(p2, b.x, P0, Pd, token, 2, dTmin, next, best);
-        face_test_flat<ZERO_SKIP>(p3, b.y, P0, Pd, token, 3, dTmin, next, best);
-    }
+    { double4 p0 = rec[0], p1 = rec[1]; record_pair<ZERO_SKIP, false, true>(p0, p1, nb[0], 0, P0, Pd, token, dTmin, next, best); }
+    { double4 p2 = rec[2], p3 = rec[3]; record_pair<ZERO_SKIP, false, true>(p2, p3, nb[1], 2, P0, Pd, token, dTmin, next, best); }
     if (best >= 0) {
-        S = axpy(dTmin, Pd, P0);
+        if (KEEP_Z) S = axpy(dTmin, Pd, P0);
+        else { S.x = fma(dTmin, Pd.x, P0.x); S.y = fma(dTmin, Pd.y, P0.y); }
         outSlot = best;
     }
     return next;
@@ -455,23 +327,14 @@ __device__ __forceinline__ int trace_lds4_flat_z(D3& S, const D3& E, int cur, co
 // rejected by the exact predicate (|fd| <= |den| leaves fd == 0, whose quotient is NaN) exactly as in face_test.  More
 // vector instructions where faces used to be skipped for zero denominators (2-D cases), fewer branches and shorter
 // dependent chains everywhere: used where every face is live anyway (3-D meshes, the Brownian kick).
-__device__ __forceinline__ void face_accept(double den, double fd, int bs, int token, int s, double& dTmin, int& next, int& best) {
-    const bool c1 = fabs(fd) <= fabs(den), c2 = den < 0.0 || fd >= 0.0;
-    const bool c3 = fd < kTol, c4 = bs != token;
-    if (c1 && c2 && c3 && c4) {
-        const double dT = fd / den;
-        if (dT > kTol && dT < dTmin) { dTmin = dT; next = bs; best = s; }
-    }
-}
 __device__ __forceinline__ void face_pair_test(const double4& pa, const double4& pb, int2 b, const D3& P0, const D3& Pd, int token,
                                                int s, double& dTmin, int& next, int& best) {
     const double denA = dot3(pa, Pd), denB = dot3(pb, Pd);
     const double fdA = plane_dist(pa, P0), fdB = plane_dist(pb, P0);
-    const unsigned long long mA = (ballot64(denA <= fdA) | ballot64(fdA >= 0.0)) & __builtin_amdgcn_uicmp((unsigned)b.x, (unsigned)token, 33 /* ne */);
-    const unsigned long long mB = (ballot64(denB <= fdB) | ballot64(fdB >= 0.0)) & __builtin_amdgcn_uicmp((unsigned)b.y, (unsigned)token, 33 /* ne */);
+    const unsigned long long mA = face_vote(denA, fdA, b.x, token), mB = face_vote(denB, fdB, b.y, token);
     if ((mA | mB) != 0ull) {
-        if (mA != 0ull) face_accept(denA, fdA, b.x, token, s, dTmin, next, best);
-        if (mB != 0ull) face_accept(denB, fdB, b.y, token, s + 1, dTmin, next, best);
+        if (mA != 0ull) face_accept<false>(denA, fdA, b.x, token, s, dTmin, next, best);
+        if (mB != 0ull) face_accept<false>(denB, fdB, b.y, token, s + 1, dTmin, next, best);
     }
 }
 __device__ __forceinline__ int trace_lds6_paired(D3& S, const D3& E, int cur, const double4* rec, int token, int& outSlot, bool zLast = false) {
@@ -562,7 +425,7 @@ __device__ __forceinline__ void trace_box_slow(const D3& P0, const D3& Pd, const
         double dT = fd / den;
         if (__builtin_isinf(dT)) dT = -1.0;
         if (nb == token) continue;
-        if (GROUPS && is_group(nb) && !(den < 0.0)) continue;       // face groups: outward crossings only (trace_in_cell)
+        if (GROUPS && is_group(nb) && !(den < 0.0)) continue;       // face groups: outward crossings only (cpf_accept.h)
         if (fd < kTol && dT > kTol && dT <= 1.0 && (dT < dTmin || (dT == dTmin && ord < ordBest))) { dTmin = dT; next = nb; best = k; ordBest = ord; }
     }
 }
@@ -619,8 +482,16 @@ __device__ __forceinline__ int trace_box(D3& S, const D3& E, int cur, const doub
     return next;
 }
 
-// trace_in_cell on the CSR slots [s0, s0 + nf) of one cell; outSlot is returned relative to s0.  A group code may come
-// back as `next`: the caller resolves it (resolve_group), as after the six-slot tests.
+// One cell of the walk in the reference's own form: traceIntet (query/ConvexQuery.cu:32-131) on the CSR slots [s0, s0 + nf) of a
+// polyhedral cell.  Exit through the face slot with the smallest admissible dT in (tol, 1]; the slot we came in through
+// (nbr == token) is skipped.  Returns the next cell (== cur: segment ends here; < 0: boundary code) and advances S to the exit
+// point; outSlot is returned relative to s0.  A group code may come back as `next`: the caller resolves it (resolve_group), as
+// after the six-slot tests.
+// THE REFERENCE'S FORM -- divide, inf -> -1, token skip, group rule, accept -- is written out in this loop, in trace_in_cell
+// below and in trace_box_slow above (there with the tie-break on original slot order).  One helper for the three was tried
+// in several spellings: through it the staged kernels of cpf_kernels.hip (trace_in_cell), two LOOKUP 2 streaming kernels (this
+// loop: more instructions) and four LOOKUP 11 ones (trace_box_slow: one more VGPR) compile to other code than before, and
+// the generated code of the kernels is held fixed -- docs/experiments.md, "the walk's accept predicate".
 __device__ __forceinline__ int trace_csr(D3& S, const D3& E, int cur, const double4* __restrict__ planes, const int32_t* __restrict__ nbr,
                                          int s0, int nf, int token, int& outSlot) {
     const D3 P0 = S;
@@ -630,15 +501,46 @@ __device__ __forceinline__ int trace_csr(D3& S, const D3& E, int cur, const doub
     for (int s = 0; s < nf; ++s) {
         const double4 pl = planes[s0 + s];
         const int nb = nbr[s0 + s];
-        const double fd = plane_dist(pl, P0), den = dot3(pl, Pd);
+        const double fd = plane_dist(pl, P0), den = dot3(pl, Pd);    // (Cf - P0).n  (<= 0 inside)
         double dT = fd / den;
-        if (__builtin_isinf(dT)) dT = -1.0;
+        if (__builtin_isinf(dT)) dT = -1.0;                          // segment parallel to the face
         if (nb == token) continue;
-        if (is_group(nb) && !(den < 0.0)) continue;
+        if (is_group(nb) && !(den < 0.0)) continue;                  // face groups: outward crossings only (cpf_accept.h)
         if (fd < kTol && dT > kTol && dT <= 1.0 && dT < dTmin) { dTmin = dT; next = nb; best = s; }
     }
     if (best >= 0) {
         S = axpy(dTmin, Pd, P0);
+        outSlot = best;
+    }
+    return next;
+}
+// trace_csr on cell `cur` of the CSR tables, with the group resolved, outSlot absolute and the exit point kept up to date
+// inside the loop
+__device__ __forceinline__ int trace_in_cell(D3& S, const D3& E, int cur, const MeshView& m, int token,
+                                             int& outSlot) {
+    const D3 P0 = S;
+    const D3 Pd = {E.x - P0.x, E.y - P0.y, E.z - P0.z};
+    int next = cur, best = -1;
+    double dTmin = 1.1;
+    const int s0 = m.cellOff[cur], s1 = m.cellOff[cur + 1];
+    for (int s = s0; s < s1; ++s) {
+        const double4 pl = m.planes[s];
+        const double fd = plane_dist(pl, P0);           // (Cf - P0).n  (<= 0 inside)
+        const double den = dot3(pl, Pd);
+        double dT = fd / den;
+        if (__builtin_isinf(dT)) dT = -1.0;             // segment parallel to the face
+        const int nb = m.nbr[s];
+        if (nb == token) continue;
+        if (is_group(nb) && !(den < 0.0)) continue;     // face groups: outward crossings only (cpf_accept.h)
+        if (fd < kTol && dT > kTol && dT <= 1.0 && dT < dTmin) {
+            dTmin = dT;
+            next = nb;
+            S = axpy(dT, Pd, P0);
+            best = s;
+        }
+    }
+    if (best >= 0) {
+        if (is_group(next)) next = resolve_group(next, S, m.cellOff, m.planes, m.groupOff, m.groupNbr);
         outSlot = best;
     }
     return next;
