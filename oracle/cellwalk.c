@@ -306,6 +306,10 @@ void cw_normal3(uint64_t gid, uint32_t step, uint32_t seed, double out[3]) {
     cw_philox4x32(ctr, key, CW_PHILOX_ROUNDS, w);
     cw_normal3_words(w, out);
 }
+/* ... for n particle ids at one step: out[n][3] */
+void cw_normal3_many(const int64_t* gid, int64_t n, uint32_t step, uint32_t seed, double* out) {
+    for (int64_t i = 0; i < n; ++i) cw_normal3((uint64_t)gid[i], step, seed, out + 3 * i);
+}
 /* test helper: the (gid, step) in [0, n) x [step0, step0 + nSteps) whose FIRST radius word is smallest, i.e. whose
  * first two deviates lie farthest out */
 void cw_scan_min_radius_word(uint32_t seed, uint32_t step0, int nSteps, int64_t n, int64_t* bestGid, uint32_t* bestStep,
@@ -323,25 +327,53 @@ void cw_scan_min_radius_word(uint32_t seed, uint32_t step0, int nSteps, int64_t 
 
 typedef struct { long long hops, reflections, lost; } cw_stats;
 
-/* advect + locate + reflect + move for one particle (src/advect.H:96-161, D = 0) */
+/* fold_z of csrc/cpf_walk.h in plain C (zfold, below): the end point's z mirrored about the cell's own two planes with normal
+ * (0, 0, +-1) -- slots 4 and 5 of a z-layered mesh (cw_build: z faces last) -- before the walk, at most CW_MAX_REFLECT times.
+ * Returns the number of mirrorings.  The kernels' ORDER OF OPERATIONS, documented there as equal to the reference's (walk to the
+ * plane, mirror at the hit point, walk on) in exact arithmetic and different in the rounding of the hit point: it is stated here so
+ * that the kicked cycle on a mesh one cell thick in z can be compared bit for bit (tests/test_gpu_brownian_cycle.py). */
+static int fold_z_end(double* ez, const double* pa, const double* pb) {
+    const double za = pa[3] * pa[2], zb = pb[3] * pb[2];          /* plane (0, 0, nz, d), nz = +-1: z = d / nz = d * nz, exactly */
+    const double lo = fmin(za, zb), hi = fmax(za, zb);
+    int nb = 0;
+    for (int k = 0; k < CW_MAX_REFLECT && (*ez < lo || *ez > hi); ++k) {
+        if (*ez < lo) { *ez = fma(-2.0, *ez - lo, *ez); ++nb; }
+        else { *ez = fma(-2.0, *ez - hi, *ez); ++nb; }
+    }
+    return nb;
+}
+
+/* advect + [kick] + locate + reflect + move for one particle (src/advect.H:96-161).
+ *   xi       the cycle's three N(0,1) deviates, or NULL: no kick.  disp += sigma * xi (particles.cu:560-569)
+ *   reflect  0: CPF_STEP_NO_REFLECT as particle_cycles (csrc/cpf_kernels.hip) states it -- the walk stops at the first wall, the
+ *            particle moves to P + disp, its cell becomes CW_LOST (and the next cycle makes it CW_FROZEN)
+ *   zfold    1 (with xi and reflect, on a mesh one cell thick in z): fold_z_end before the walk; the mirrorings count as reflections,
+ *            an odd number flips the stored velocity's z, and a folded, otherwise unreflected particle ends at
+ *            {P.x + disp.x, P.y + disp.y, E.z}
+ *   diag     NULL or three counters of this particle-cycle: cells visited, wall reflections, mirrorings of zfold */
 static void step_one(int i, double* px, double* py, double* pz, int* cell, double* vel_out, double dt,
                      const cw_tables* t, const double* U, cw_stats* st,
-                     double D, const int64_t* gid, uint32_t step, uint32_t seed) {
+                     const double* xi, double sigma, int reflect, int zfold, int* diag) {
     const double* planes = t->planes;
     int cur = cell[i];
+    if (diag) diag[0] = diag[1] = diag[2] = 0;
     if (cur < 0) { if (cur == CW_LOST) cell[i] = CW_FROZEN; return; }
     const v3 P = V(px[i], py[i], pz[i]);
     v3 vel = V(U[3 * cur], U[3 * cur + 1], U[3 * cur + 2]);
     const v3 Pn = axpy(dt, vel, P);
     v3 disp = sub(Pn, P);                      /* disp = (P + dt*vel) - P, particles.cu:358-359 */
-    if (D > 0.0) {                             /* disp += xi*sqrt(2 D dt), particles.cu:560-569 */
-        double xi[3];
-        cw_normal3((uint64_t)(gid ? gid[i] : i), step, seed, xi);
-        disp = axpy(sqrt(2.00 * D * dt), V(xi[0], xi[1], xi[2]), disp);
-    }
+    if (xi) disp = axpy(sigma, V(xi[0], xi[1], xi[2]), disp);       /* disp += xi*sqrt(2 D dt), particles.cu:560-569 */
     v3 Pe = add(P, disp);
+    int folds = 0;
+    if (zfold && xi && reflect) {
+        const int s0 = t->cellOff[cur];
+        folds = fold_z_end(&Pe.z, planes + 4 * (s0 + 4), planes + 4 * (s0 + 5));
+        st->reflections += folds;
+        if (folds & 1) vel.z = -vel.z;
+    }
     v3 Ps = P, Phit = P;
     int token = INT_MIN, next = cur, outSlot = -1, reflected = 0;
+    const long long hops0 = st->hops;
     for (int j = 0; j < CW_MAX_REFLECT; ++j) {
         for (int h = 0; h < CW_MAX_HOPS; ++h) {
             next = trace_in_cell(&Ps, Pe, cur, t, token, &outSlot);
@@ -351,9 +383,9 @@ static void step_one(int i, double* px, double* py, double* pz, int* cell, doubl
             token = cur;
             cur = next;
         }
-        if (next >= 0) break;                  /* segment ends inside `next` (or hop cap reached) */
+        if (next >= 0 || !reflect) break;      /* segment ends inside `next` (or hop cap reached); or a wall without reflection */
         /* wall: mirror end point and velocity about the boundary face just hit */
-        Phit = Ps; reflected = 1; st->reflections++;
+        Phit = Ps; reflected++; st->reflections++;
         v3 n = V(planes[4 * outSlot], planes[4 * outSlot + 1], planes[4 * outSlot + 2]);
         double sd = dotf(n, Pe) - planes[4 * outSlot + 3];
         Pe = axpy(-2.0 * sd, n, Pe);
@@ -362,25 +394,54 @@ static void step_one(int i, double* px, double* py, double* pz, int* cell, doubl
     }
     v3 Pnew;
     if (reflected) Pnew = add(Phit, sub(Pe, Phit));   /* p = P_hit; disp = P_end - P_hit; p += disp */
+    else if (folds) Pnew = V(P.x + disp.x, P.y + disp.y, Pe.z);
     else Pnew = add(P, disp);
     px[i] = Pnew.x; py[i] = Pnew.y; pz[i] = Pnew.z;
     if (next < 0) { next = CW_LOST; st->lost++; }
     cell[i] = next;
     if (vel_out) { vel_out[3 * i] = vel.x; vel_out[3 * i + 1] = vel.y; vel_out[3 * i + 2] = vel.z; }
+    if (diag) { diag[0] = (int)(st->hops - hops0); diag[1] = reflected; diag[2] = folds; }
 }
 
+/* D > 0: the deviates are cw_normal3's, reflect = 1, zfold = 0 */
 void cw_step(double* px, double* py, double* pz, int* cell, double* vel_out, int n, double dt, int cycles,
              const int* cellOff, const double* planes, const int* nbr, const int* groupOff, const int* groupNbr,
              const double* U, int nthreads, long long* stats /* [hops, reflections, lost] or NULL */,
              double D, const int64_t* gid, uint32_t step0, uint32_t seed) {
     long long H = 0, R = 0, L = 0;
     const cw_tables tab = {cellOff, planes, nbr, groupOff, groupNbr};
+    const double sigma = D > 0.0 ? sqrt(2.00 * D * dt) : 0.0;
     /* particles are independent: all cycles of one particle back to back, one parallel region */
 #pragma omp parallel for schedule(static) num_threads(nthreads > 0 ? nthreads : 1) reduction(+ : H, R, L)
     for (int i = 0; i < n; ++i) {
         cw_stats st = {0, 0, 0};
-        for (int c = 0; c < cycles; ++c)
-            step_one(i, px, py, pz, cell, vel_out, dt, &tab, U, &st, D, gid, step0 + (uint32_t)c, seed);
+        for (int c = 0; c < cycles; ++c) {
+            double xi[3] = {0.0, 0.0, 0.0};
+            if (D > 0.0 && cell[i] >= 0) cw_normal3((uint64_t)(gid ? gid[i] : i), step0 + (uint32_t)c, seed, xi);
+            step_one(i, px, py, pz, cell, vel_out, dt, &tab, U, &st, D > 0.0 ? xi : NULL, sigma, 1, 0, NULL);
+        }
+        H += st.hops; R += st.reflections; L += st.lost;
+    }
+    if (stats) { stats[0] = H; stats[1] = R; stats[2] = L; }
+}
+
+/* The same cycles with the deviates GIVEN as data -- xi[cycles][n][3], by array position -- and the two switches of step_one:
+ * what the kicked kernels are compared with bit for bit, the deviates being the device's own (tests/browniancycle.py).
+ * sigma = sqrt(2.00 * D * dt) is the caller's; diag: NULL or [cycles][n][3] (step_one). */
+void cw_step_given(double* px, double* py, double* pz, int* cell, double* vel_out, int n, double dt, int cycles,
+                   const int* cellOff, const double* planes, const int* nbr, const int* groupOff, const int* groupNbr,
+                   const double* U, int nthreads, long long* stats /* [hops, reflections, lost] or NULL */,
+                   double sigma, const double* xi, int reflect, int zfold, int* diag) {
+    long long H = 0, R = 0, L = 0;
+    const cw_tables tab = {cellOff, planes, nbr, groupOff, groupNbr};
+#pragma omp parallel for schedule(static) num_threads(nthreads > 0 ? nthreads : 1) reduction(+ : H, R, L)
+    for (int i = 0; i < n; ++i) {
+        cw_stats st = {0, 0, 0};
+        for (int c = 0; c < cycles; ++c) {
+            const size_t k = (size_t)c * (size_t)n + (size_t)i;
+            step_one(i, px, py, pz, cell, vel_out, dt, &tab, U, &st, xi ? xi + 3 * k : NULL, sigma, reflect, zfold,
+                     diag ? diag + 3 * k : NULL);
+        }
         H += st.hops; R += st.reflections; L += st.lost;
     }
     if (stats) { stats[0] = H; stats[1] = R; stats[2] = L; }
@@ -466,7 +527,7 @@ void cw_step_count(double* px, double* py, double* pz, int* cell, int n, double 
 #pragma omp parallel for schedule(static) num_threads(nthreads > 0 ? nthreads : 1)
     for (int i = 0; i < n; ++i) {
         cw_stats st = {0, 0, 0};
-        step_one(i, px, py, pz, cell, NULL, dt, &tab, U, &st, 0.0, NULL, 0, 0);
+        step_one(i, px, py, pz, cell, NULL, dt, &tab, U, &st, NULL, 0.0, 1, 0, NULL);
         visits[i] = (int)st.hops; reflections[i] = (int)st.reflections;
     }
 }

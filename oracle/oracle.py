@@ -252,11 +252,14 @@ class CellWalk:
         L.cw_build.argtypes = [_dp, C.c_int, _ip, _ip, C.c_int, _ip, _ip, C.c_int, C.c_int, _ip, _dp, _ip, _ip, _ip, _ip]
         L.cw_step.argtypes = [_dp, _dp, _dp, _ip, C.c_void_p, C.c_int, C.c_double, C.c_int, _ip, _dp, _ip, _ip, _ip, _dp,
                               C.c_int, _lp, C.c_double, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.cw_step_given.argtypes = [_dp, _dp, _dp, _ip, C.c_void_p, C.c_int, C.c_double, C.c_int, _ip, _dp, _ip, _ip, _ip, _dp,
+                                    C.c_int, _lp, C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.cw_locate_initial.argtypes = [_dp, _dp, _dp, _ip, C.c_int, C.c_int, _ip, _dp, C.c_int]
         L.cw_step_count.argtypes = [_dp, _dp, _dp, _ip, C.c_int, C.c_double, _ip, _dp, _ip, _ip, _ip, _dp, C.c_int, _ip, _ip]
         L.cw_philox4x32_10.argtypes = [_up, _up, _up]
         L.cw_philox4x32.argtypes = [_up, _up, C.c_int, _up]
         L.cw_normal3.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, _dp]
+        L.cw_normal3_many.argtypes = [_lp, C.c_int64, C.c_uint32, C.c_uint32, _dp]
         L.cw_normal3_words.argtypes = [_up, _dp]
         L.cw_scan_min_radius_word.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int64, C.POINTER(C.c_int64),
                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -292,6 +295,28 @@ class CellWalk:
                          U, nthreads, stats, D, gp, step0, seed)
         return stats
 
+    def step_given(self, x, y, z, cell, dt, cycles, t: CellTables, U, sigma, xi, reflect=1, zfold=0,
+                   vel_out: Optional[np.ndarray] = None, nthreads=1, diag: Optional[np.ndarray] = None):
+        """`cycles` cycles in place with the kick's deviates GIVEN: xi [cycles][n][3] by array position (None: no kick), disp +=
+        sigma * xi.  reflect 0: CPF_STEP_NO_REFLECT; zfold 1: fold_z of csrc/cpf_walk.h (a mesh one cell thick in z).
+        diag: None or int32 [cycles][n][3] -- cells visited, wall reflections, z mirrorings per particle-cycle.
+        Returns [cells visited, reflections (z mirrorings included), lost]."""
+        n = x.shape[0]
+        stats = np.zeros(3, np.int64)
+        U = _c(U, np.float64)
+        if xi is not None:
+            xi = _c(xi, np.float64)
+            if xi.shape != (cycles, n, 3):
+                raise ValueError("step_given: xi must be [cycles][n][3]")
+        if diag is not None and (diag.dtype != np.int32 or diag.shape != (cycles, n, 3) or not diag.flags.c_contiguous):
+            raise ValueError("step_given: diag must be a contiguous int32 [cycles][n][3]")
+        vp = None if vel_out is None else vel_out.ctypes.data_as(C.c_void_p)
+        xp = None if xi is None else xi.ctypes.data_as(C.c_void_p)
+        gp = None if diag is None else diag.ctypes.data_as(C.c_void_p)
+        self.lib.cw_step_given(x, y, z, cell, vp, n, dt, cycles, t.cell_off, t.planes, t.nbr, t.group_off, t.group_nbr,
+                               U, nthreads, stats, float(sigma), xp, int(reflect), int(zfold), gp)
+        return stats
+
     def step_count(self, x, y, z, cell, dt, t: CellTables, U, nthreads=1):
         """One cycle (D = 0) in place; returns per-particle (cells visited, wall reflections)."""
         n = x.shape[0]
@@ -315,6 +340,13 @@ class CellWalk:
     def normal3(self, gid, step, seed):
         out = np.zeros(3)
         self.lib.cw_normal3(int(gid), int(step), int(seed), out)
+        return out
+
+    def normal3_many(self, gids, step, seed):
+        """normal3 for an array of particle ids at one step: [n][3]"""
+        g = _c(np.asarray(gids), np.int64)
+        out = np.zeros((g.shape[0], 3))
+        self.lib.cw_normal3_many(g, g.shape[0], int(step), int(seed), out)
         return out
 
     def normal3_words(self, words):

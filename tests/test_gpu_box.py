@@ -117,8 +117,8 @@ def test_box_records_signed_zero_normals(oracle_libs, gpu_ctx_factory):
 
 @pytest.mark.parametrize("D", [1e-3])
 def test_box_records_brownian_same_bits_as_full_records(gpu_ctx_factory, D):
-    """With the kick there is no CPU statement to be bit-identical to (the generator differs: SURVEY.md 8c) -- but box records
-    and full records run the same generator and must agree bit for bit."""
+    """Box records and full records run the same generator and must agree bit for bit with each other.  (Against the CPU statement
+    the kicked cycle is held bit for bit as well, given the device's deviates: tests/test_gpu_brownian_cycle.py, LOOKUP 6 and 1.)"""
     from cudaparticlesfoam_amd.cases import box_mesh
     rng = np.random.default_rng(9)
     mesh = box_mesh(10, 9, 8, upper=(1.0, 0.9, 0.8), grading=(2.0, 1.0, 0.5))
@@ -183,7 +183,8 @@ def test_refined_box_ties_and_faces(oracle_libs, gpu_ctx_factory, field):
 
 
 def test_refined_box_kick_and_velocity_refresh_same_bits(gpu_ctx_factory):
-    """(with the kick there is no CPU statement to match: box records with group slots against the ordinary mixed records)"""
+    """Box records with group slots against the ordinary mixed records, with the kick and a velocity refresh.  (The CPU statement
+    for the kicked cycle -- bit for bit, given the device's deviates -- is tests/test_gpu_brownian_cycle.py, LOOKUP 11, 3 and 5.)"""
     from cudaparticlesfoam_amd.cases import refined_box
     rng = np.random.default_rng(3)
     mesh, _ = refined_box(10, 9, 8, (0.0, 0.0, 0.0), (1.0, 0.9, 0.8), ((0.2, 0.2, 0.2), (0.7, 0.7, 0.6)))

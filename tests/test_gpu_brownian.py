@@ -4,6 +4,9 @@ Parity with the reference's cuRAND XORWOW stream is statistical by contract (no 
 reference's kick guarantees is a free-space mean square displacement of 6 D t with independent increments and
 independent axes, and -- with every boundary reflecting -- that no particle is lost.  Both at the tutorial's
 diffusion coefficient (pitzDaily/system/cudaParticlesDict:17-29: diffusionCoeff 1.5e-5, dt 1e-4).
+
+Against this project's own CPU statement the kicked cycle is not statistical: given the device's deviates as data it is equal bit for
+bit, particle by particle, on every kicked kernel (tests/test_gpu_brownian_cycle.py); the deviates themselves are libm's to 2e-5.
 """
 import numpy as np
 import pytest
@@ -126,6 +129,7 @@ def test_front_and_back_planes_mirrored_before_the_walk_equal_the_reference_orde
     its CPU statement do (ConvexQuery.cu:286-309).  Same trajectory in exact arithmetic, so particle by particle -- the
     ones that bounce off a z plane included -- the two agree to the rounding of the deviates (fp32 hardware transcendentals
     against libm: a few 1e-6 sigma), in position AND cell; with the option off the kernels take the reference's order.
+    (With the DEVICE's deviates both orders are compared with their CPU statements bit for bit: tests/test_gpu_brownian_cycle.py (b).)
     100x the tutorial's D: a third of the particles meets a z plane in one cycle, some of them twice."""
     pz, mesh = pitz["pz"], pitz["mesh"]
     cw = oracle_libs.CellWalk()
