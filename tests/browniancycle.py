@@ -13,7 +13,12 @@ walk, reflect, move -- on them:
   the only route for gids >= 2^32 -- and for gid == NULL.
 
 This module holds what tests/test_brownian_cycle_host.py (no GPU: libm's deviates) and tests/test_gpu_brownian_cycle.py share: the
-meshes with their fields, time steps and diffusion coefficients, the clouds, the CPU run and the two extractors."""
+meshes with their fields, time steps and diffusion coefficients, the clouds, the CPU run and the two extractors.
+
+The UNKICKED cycle (D = 0) is the same statement without deviates (``step_given(xi = None)``: ``run_cpu(..., xi=None)``) and needs no
+extractor; tests/test_plain_cycle_host.py and tests/test_gpu_plain_cycle.py run it on the same meshes and clouds, in the case's
+field and in three more (``Case.U0`` with exact zeros, ``Case.Uflat`` without a z component, ``Case.Ucorner`` towards a corner),
+with the reference results cached here (``plain_ref``) and the conditions on whole 64-particle tiles stated here (``tiles``)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -100,6 +105,37 @@ class Case:
         self.lo, self.hi = self.mesh.bounds()
 
     @functools.cached_property
+    def U0(self):
+        """The second field, with exact zeros (the unkicked cycle's zero-denominator skips, tests/test_gpu_plain_cycle.py): the
+        first third of the cell ids at rest -- all three components zero, +0.0 and -0.0 mixed --, the last third with U.x exactly
+        +-0.0, the rest the case's random field."""
+        n = self.mesh.n_cells
+        rng = np.random.default_rng(7000 + n)
+        U0 = self.U.copy()
+        U0[:n // 3] = rng.choice([0.0, -0.0], size=(n // 3, 3))
+        U0[n - n // 3:, 0] = rng.choice([0.0, -0.0], size=n // 3)
+        U0.setflags(write=False)
+        return U0
+
+    @functools.cached_property
+    def Uflat(self):
+        """the case's field without a z component: the flat walk's (a mesh extruded in z)"""
+        U = self.U.copy()
+        U[:, 2] = 0.0
+        U.setflags(write=False)
+        return U
+
+    @functools.cached_property
+    def Ucorner(self):
+        """one velocity everywhere, towards the corner at self.hi: the cloud piles up against three walls, whole tiles reflect"""
+        U = np.tile(float(np.abs(self.U).max()) * np.array([1.0, 0.9, 0.8]), (self.mesh.n_cells, 1))
+        U.setflags(write=False)
+        return U
+
+    def field(self, which):
+        return {"U": self.U, "U0": self.U0, "Uflat": self.Uflat, "U2": self.U2, "Ucorner": self.Ucorner}[which]
+
+    @functools.cached_property
     def tables(self):
         return cellwalk().build(self.mesh)
 
@@ -151,23 +187,23 @@ class Snapshot:
         self.stats = stats                      # [cells visited, reflections, lost, live particle-cycles] since the last checkpoint
 
 
-def run_cpu(c: Case, xyz, cell0, xi, reflect=1, zfold=0, checkpoints=CHECKPOINTS, refresh_after=None):
-    """({k: Snapshot after k cycles}, diag [cycles][n][3]) of CellWalk.step_given on the deviates xi [cycles][n][3];
-    refresh_after: the checkpoint behind which the field becomes c.U2."""
+def run_cpu(c: Case, xyz, cell0, xi=None, reflect=1, zfold=0, checkpoints=CHECKPOINTS, refresh_after=None, U=None):
+    """({k: Snapshot after k cycles}, diag [cycles][n][3]) of CellWalk.step_given on the deviates xi [cycles][n][3] -- None: the
+    unkicked cycle (D = 0) --; refresh_after: the checkpoint behind which the field becomes c.U2; U: the field (None: c.U)."""
     cw = cellwalk()
     n = xyz.shape[0]
     x, y, z = (xyz[:, k].copy() for k in range(3))
     cell = np.array(cell0, np.int32)
     vel = np.zeros((n, 3))
     diag = np.zeros((max(checkpoints), n, 3), np.int32)
-    out, done, U = {}, 0, c.U
+    out, done, U = {}, 0, (c.U if U is None else U)
     for k in checkpoints:
         live = 0
         st = np.zeros(3, np.int64)
         for cyc in range(done, k):                                       # cycle by cycle: the live count is the fourth counter
             live += int((cell >= 0).sum())
-            st += cw.step_given(x, y, z, cell, c.dt, 1, c.tables, U, c.sigma, xi[cyc:cyc + 1], reflect=reflect, zfold=zfold,
-                                vel_out=vel, nthreads=cw.max_threads, diag=diag[cyc:cyc + 1])
+            st += cw.step_given(x, y, z, cell, c.dt, 1, c.tables, U, c.sigma, None if xi is None else xi[cyc:cyc + 1],
+                                reflect=reflect, zfold=zfold, vel_out=vel, nthreads=cw.max_threads, diag=diag[cyc:cyc + 1])
         done = k
         out[k] = Snapshot(x, y, z, cell, vel, [int(st[0]), int(st[1]), int(st[2]), live])
         if refresh_after == k:
@@ -184,6 +220,51 @@ def hard_paths(diag):
     return dict(crossing=float((visits - walls > 1).sum()) / live, reflecting=float((walls > 0).sum()) / live,
                 two_walls=int((walls >= 2).sum()), three_hops=int((visits - walls >= 4).sum()),
                 folded=float((folds > 0).sum()) / live, folded_twice=int((folds >= 2).sum()), live=live)
+
+
+# ------------------------------------------------------------------------------------------------ the unkicked cycle (D = 0)
+@functools.lru_cache(maxsize=None)
+def flat_cloud(n):
+    """cloud("thin box", n, sort = True) with z == -0.0 for every fifth particle: on the z = 0 plane, where the flat walk (no z
+    component in the field) leaves it for good and the first cycle rewrites the zero's sign"""
+    xyz, cell0, gid = cloud("thin box", n, sort=True)
+    xyz = xyz.copy()
+    xyz[::5, 2] = -0.0
+    xyz.setflags(write=False)
+    return xyz, cell0, gid
+
+
+@functools.lru_cache(maxsize=None)
+def plain_ref(name, field, n, sort, reflect, refresh_after=None, flat=False):
+    """(snapshots, diag) of the CPU statement WITHOUT the kick (step_given(xi = None)) for cloud(name, n, sort) -- flat:
+    flat_cloud(n) -- in the field c.field(field); computed once and shared: nobody writes into it"""
+    xyz, cell0, _ = flat_cloud(n) if flat else cloud(name, n, sort=sort)
+    c = case(name)
+    return run_cpu(c, xyz, cell0, None, reflect=reflect, refresh_after=refresh_after, U=c.field(field))
+
+
+def tiles(a):
+    """[tiles][64]: the whole 64-particle tiles of a per-particle array in storage order (array positions 64 k ... 64 k + 63)"""
+    return a[:(a.shape[0] // 64) * 64].reshape(-1, 64)
+
+
+def at_rest_tiles(c: Case, cell0):
+    """the tiles whose 64 lanes all sit in at-rest cells of c.U0 (its first third of the cell ids)"""
+    t = tiles(cell0)
+    return np.nonzero(((t >= 0) & (t < c.mesh.n_cells // 3)).all(1))[0]
+
+
+def zero_x_crossing_tiles(c: Case, cell0, diag):
+    """the tiles whose 64 lanes all begin in U.x == +-0 cells of c.U0 (its last third of the cell ids) and of which a lane crosses a
+    face in the first cycle -- a y or a z face on a mesh of boxes: nobody there moves in x"""
+    t = tiles(cell0)
+    crossed = tiles((diag[0, :, 0] - diag[0, :, 1] > 1))
+    return np.nonzero((t >= c.mesh.n_cells - c.mesh.n_cells // 3).all(1) & crossed.any(1))[0]
+
+
+def most_lanes_of_a_tile_reflecting(diag):
+    """the largest number of lanes of one tile that meet a wall in one and the same cycle"""
+    return max(int(tiles(diag[cyc, :, 1] > 0).sum(1).max()) for cyc in range(diag.shape[0]))
 
 
 # ------------------------------------------------------------------------------------------------ the device side
