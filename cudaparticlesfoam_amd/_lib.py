@@ -146,6 +146,14 @@ SIGNATURES = {
     "cpf_occupancy_sample_dev": (_int, [_ctx, _vp, _i64]),
     "cpf_occupancy_reset": (_int, [_ctx]),
     "cpf_get_occupancy": (_int, [_ctx, _vp, C.POINTER(_i64)]),
+    "cpf_set_sink_cells": (_int, [_ctx, _vp, _i64]),
+    "cpf_sink_apply": (_int, [_ctx]),
+    "cpf_sink_apply_dev": (_int, [_ctx, _vp, _i64]),
+    "cpf_respawn_box": (_int, [_ctx, _vp, _vp, _i64]),
+    "cpf_respawn_box_dev": (_int, [_ctx, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _u32]),
+    "cpf_get_recycle_counts": (_int, [_ctx, _vp]),
+    "cpf_recycle_reset_counts": (_int, [_ctx]),
+    "cpf_respawn_positions_host": (_int, [_u32, _vp, _i64, _u32, _vp, _vp, _vp]),
     "cpf_set_velocity": (_int, [_ctx, _vp, _i64]),
     "cpf_set_velocity_dev": (_int, [_ctx, _vp, _i64]),
     "cpf_alloc_particles": (_int, [_ctx, _i64]),

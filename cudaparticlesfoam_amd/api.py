@@ -259,6 +259,39 @@ class Context:
             raise ValueError("concentration: no occupancy sample yet (occupancy_sample)")
         return counts.astype(np.float64) / (float(ns) * self.cell_volumes())
 
+    # -- recycling: sink cells and a source box (include/cpf.h "recycling")
+    def set_sink_cells(self, cells):
+        """The sink set: cell ids of the mesh as given (an empty list clears it).  ``PolyMesh.patch_cells`` gives a patch's."""
+        c = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1)
+        self._ck(self.lib.cpf_set_sink_cells(self.h, _ptr(c) if c.size else None, c.size))
+
+    def sink_apply(self):
+        """Every particle of the context-owned cloud that sits in a sink cell becomes lost (cell -1); asynchronous."""
+        self._ck(self.lib.cpf_sink_apply(self.h))
+
+    def sink_apply_dev(self, cell_ptr, n):
+        """The same on a device int32 array of DERIVED ids."""
+        self._ck(self.lib.cpf_sink_apply_dev(self.h, cell_ptr, n))
+
+    def respawn_box(self, lower, upper, max_count: int = -1):
+        """Up to ``max_count`` (< 0: all) dead slots of the context-owned cloud, in array order, get a fresh position in the box
+        and are located; the cloud's epoch counter goes up by one."""
+        lo = np.ascontiguousarray(lower, dtype=np.float64); hi = np.ascontiguousarray(upper, dtype=np.float64)
+        self._ck(self.lib.cpf_respawn_box(self.h, _ptr(lo), _ptr(hi), int(max_count)))
+
+    def respawn_box_dev(self, x, y, z, cell, gid, n, lower, upper, max_count: int = -1, epoch: int = 0):
+        lo = np.ascontiguousarray(lower, dtype=np.float64); hi = np.ascontiguousarray(upper, dtype=np.float64)
+        self._ck(self.lib.cpf_respawn_box_dev(self.h, x, y, z, cell, gid, n, _ptr(lo), _ptr(hi), int(max_count), int(epoch)))
+
+    def recycle_counts(self) -> Dict[str, int]:
+        """absorbed, drawn, placed since the last reset and the epochs of the context's own cloud; synchronises."""
+        out = np.zeros(4, np.int64)
+        self._ck(self.lib.cpf_get_recycle_counts(self.h, _ptr(out)))
+        return dict(absorbed=int(out[0]), drawn=int(out[1]), placed=int(out[2]), epochs=int(out[3]))
+
+    def recycle_reset_counts(self):
+        self._ck(self.lib.cpf_recycle_reset_counts(self.h))
+
     def cell_ranges_dev(self, weights, n_ranks, cell_lo):
         self._ck(self.lib.cpf_cell_ranges_dev(self.h, weights, n_ranks, cell_lo))
 
@@ -301,6 +334,20 @@ class Context:
         a, b = C.c_int64(), C.c_double()
         self._ck(self.lib.cpf_timing_poll(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+
+def respawn_positions_host(seed: int, gid, epoch: int, lower, upper, n: Optional[int] = None) -> np.ndarray:
+    """Where ``respawn_box`` puts the particles ``gid`` (None: 0 .. n-1) at ``epoch`` under ``seed``: [n][3], computed on the host
+    alone from the kernel's own text (cpf_respawn_positions_host)."""
+    lib = L.load()
+    g = None if gid is None else np.ascontiguousarray(gid, dtype=np.int64).reshape(-1)
+    n = int(n) if g is None else g.size
+    lo = np.ascontiguousarray(lower, dtype=np.float64); hi = np.ascontiguousarray(upper, dtype=np.float64)
+    xyz = np.empty((n, 3), np.float64)
+    st = lib.cpf_respawn_positions_host(seed & 0xFFFFFFFF, _ptr(g), n, int(epoch) & 0xFFFFFFFF, _ptr(lo), _ptr(hi), _ptr(xyz))
+    if st != L.CPF_OK:
+        raise L.CpfError(st, "cpf_respawn_positions_host")
+    return xyz
 
 
 def build_mesh_tables_host(mesh):
@@ -458,9 +505,10 @@ DICT_DEFAULTS = dict(                       # src/initCuda.H:49-57 (getOrDefault
 
 
 def _next_chunk(step: int, remaining: int, save_interval: int, occupancy_interval: int, has_writer: bool,
-                will_write: bool) -> int:
+                will_write: bool, recycle_interval: int = 0) -> int:
     """Cycles the next launch of ``CudaParticles.advect`` fuses: a cycle that writes a frame runs alone; otherwise everything up
-    to the next output point (with a writer), the next occupancy sample (``occupancy_interval`` > 0) and the end of the call."""
+    to the next output point (with a writer), the next occupancy sample (``occupancy_interval`` > 0), the next recycle point
+    (``recycle_interval`` > 0) and the end of the call."""
     if will_write:
         return 1
     chunk = remaining
@@ -468,6 +516,8 @@ def _next_chunk(step: int, remaining: int, save_interval: int, occupancy_interva
         chunk = min(chunk, save_interval - (step % save_interval))
     if occupancy_interval > 0:
         chunk = min(chunk, occupancy_interval - (step % occupancy_interval))
+    if recycle_interval > 0:
+        chunk = min(chunk, recycle_interval - (step % recycle_interval))
     return max(1, chunk)
 
 
@@ -481,6 +531,12 @@ class CudaParticles:
     One dictionary key is this library's own, not the reference's: ``occupancyInterval`` (cycles; default 0 = off).  When
     positive, every cycle count that is a multiple of it adds one sample to the per-cell occupancy on the device
     (``Context.occupancy_sample``), and ``concentration()`` gives the time-averaged concentration field.
+
+    Three more are this library's own as well: ``recycleInterval`` (cycles; default 0 = off), ``sinkCells`` (an array of cell ids;
+    patch names are resolved by the caller, ``mesh.patch_cells("outlet")``) and ``sourceBox`` ((lower, upper); default: the
+    ``seedingBox``).  When ``recycleInterval`` is positive, at every cycle count that is a multiple of it the particles found in a
+    sink cell are absorbed (``Context.sink_apply``) and every dead slot is respawned in the source box
+    (``Context.respawn_box``), before the occupancy sample if one is due: an inlet and an outlet at constant particle count.
     """
 
     def __init__(self, mesh, U, particle_dict: Optional[dict] = None, device: int = 0,
@@ -495,6 +551,9 @@ class CudaParticles:
         self.saveInterval = int(d["saveInterval"])
         self.occupancyInterval = int(d.get("occupancyInterval", 0))     # this library's own key (not in DICT_DEFAULTS)
         self.seedingBox = d["seedingBox"]
+        self.recycleInterval = int(d.get("recycleInterval", 0))         # this library's own keys, like occupancyInterval
+        self.sinkCells = d.get("sinkCells", None)
+        self.sourceBox = d.get("sourceBox", self.seedingBox)
         # hard-coded switches of the fragment (src/initCuda.H:64-72)
         self.usingAdvection = True
         self.usingBrownianMotion = True
@@ -507,6 +566,8 @@ class CudaParticles:
             self.ctx.set_option("sort_interval", 25)
         self.ctx.set_mesh(mesh)
         self.ctx.set_velocity(U)
+        if self.recycleInterval > 0 and self.sinkCells is not None:
+            self.ctx.set_sink_cells(self.sinkCells)
         if positions is not None:            # parity runs inject positions
             self.ctx.set_particles(positions)
             self.numParticles = int(np.asarray(positions).shape[0])
@@ -548,13 +609,16 @@ class CudaParticles:
                 self.step % self.saveInterval == 0 or run_time_value == self.particleEndTime)
             # cycles until the next output point run inside ONE launch (U is frozen during the loop)
             chunk = _next_chunk(self.step, n_cycles - done, self.saveInterval, self.occupancyInterval,
-                                self.writer is not None, will_write)
+                                self.writer is not None, will_write, self.recycleInterval)
             flags = self._flags(will_write) | (L.STEP_FUSE_CYCLES if chunk > 1 else 0)
             self.ctx.step(cycle_dt, D, chunk, flags)
             if will_write:                                                             # advect.H:166-169
                 self._write(self.step + 1)
             self.step += chunk                                                         # advect.H:182
             done += chunk
+            if self.recycleInterval > 0 and self.step % self.recycleInterval == 0:
+                self.ctx.sink_apply()
+                self.ctx.respawn_box(self.sourceBox[0], self.sourceBox[1], -1)
             if self.occupancyInterval > 0 and self.step % self.occupancyInterval == 0:
                 self.ctx.occupancy_sample()
         return n_cycles
@@ -565,6 +629,10 @@ class CudaParticles:
     def concentration(self):
         """Time-averaged concentration per cell from the samples ``occupancyInterval`` took (``Context.concentration``)."""
         return self.ctx.concentration()
+
+    def recycle_counts(self):
+        """absorbed, drawn, placed and epochs of the run so far (``Context.recycle_counts``)."""
+        return self.ctx.recycle_counts()
 
     def close(self):
         self.ctx.close()

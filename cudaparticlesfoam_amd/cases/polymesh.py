@@ -46,6 +46,18 @@ class PolyMesh:
     def n_internal(self) -> int:
         return int(self.neighbour.shape[0])
 
+    # ---------------------------------------------------------------- patches
+    def patch_cells(self, *names: str) -> np.ndarray:
+        """Sorted unique owner cells of the faces of the named boundary patches (e.g. the cells behind an outlet)."""
+        by_name = {name: (start, size) for (name, _, start, size) in self.patches}
+        cells = [np.empty(0, np.int64)]
+        for name in names:
+            if name not in by_name:
+                raise KeyError("patch_cells: no patch %r (the mesh has %s)" % (name, sorted(by_name)))
+            start, size = by_name[name]
+            cells.append(np.asarray(self.owner[start:start + size], dtype=np.int64))
+        return np.unique(np.concatenate(cells)).astype(np.int32)
+
     # ------------------------------------------------------- derived topology
     def cell_faces(self) -> Tuple[np.ndarray, np.ndarray]:
         """CSR (offsets, faces) of ``mesh.cells()`` in ``primitiveMesh::calcCells`` order."""

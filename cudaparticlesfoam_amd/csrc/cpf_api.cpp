@@ -18,6 +18,7 @@
 #include "cpf_device.h"
 #include "cpf_internal.h"
 #include "cpf_own.h"
+#include "cpf_philox.h"    // respawn_position (cpf_respawn_positions_host)
 #include "cpf_walk.h"      // VertexField
 
 // (device-scope release is all a time stamp needs; measured against the default flags: no difference)
@@ -56,6 +57,8 @@ struct Mesh {
     // per-cell occupancy (cpf_occupancy_sample*; cpf_occupancy.hip): it belongs to the mesh and goes with it
     DevBuf<unsigned long long> occupancy;   // [nParent] accumulated counts; null until the first sample
     int64_t occupancySamples = 0;           // samples added since the last reset
+    // recycling (cpf_set_sink_cells; cpf_recycle.hip): the sink set belongs to the mesh and goes with it
+    DevBuf<uint32_t> sinkMask;              // one bit per DERIVED cell, ceil(host.nCells / 32) words; null: no sink set
 };
 
 // "VertexVelocity" advect only: the tet decomposition and one velocity per tet-mesh vertex.  It belongs to the mesh it was made
@@ -91,6 +94,7 @@ struct Cloud {
     // z of the cloud is a fixed point of the flat cycle (CPF_STEP_Z_SETTLED): set behind a flat launch that streamed z, cleared
     // by everything else that writes x, y, z or cell -- except a sort, which only permutes
     bool zSettled = false;
+    uint32_t respawnEpoch = 0;  // cpf_respawn_box calls on this cloud so far: the epoch of the next one's positions
 };
 
 // asynchronous output (cpf_write_vtu_async): one frame in flight.  Lives as long as the context.
@@ -172,6 +176,7 @@ struct cpf_context {
     // [kCounterSlots][4] = steps, hops, reflections, lost, sharded by block id (one hot word would
     // serialise every block of every launch on a single L2 atomic unit), then 4 scratch words
     DevBuf<unsigned long long> counters;
+    DevBuf<unsigned long long> recycleCounts;   // [0] absorbed, [1] drawn, [2] placed (cpf_get_recycle_counts); allocated at first use
     DevBuf<unsigned long long> occupied;        // [0] occupied cells, [1] live particles of the last sort (device) ...
     PinnedBuf<unsigned long long> h_occupied;   // ... and their pinned host copy (StreamState::occupiedHost)
     Event evFieldFlag;                          // recorded behind the read-back of "the field has a z component" (cpf_set_velocity_dev)
@@ -876,7 +881,7 @@ int cpf_seed_box(cpf_context* ctx, int64_t n, const double lower[3], const doubl
     CPF_HIP(ctx, cpf::launch_seed_box(ctx->stream, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, 0, n, lower, upper, order));
     CPF_HIP(ctx, cpf::launch_iota64(ctx->stream, ctx->cloud.cur.gid, n, 0));
     CPF_HIP(ctx, hipMemsetAsync(ctx->cloud.cur.cell, 0xFF, (size_t)n * 4, ctx->stream));
-    ctx->cloud.n = n; ctx->cloud.located = false; ctx->cloud.zSettled = false;
+    ctx->cloud.n = n; ctx->cloud.located = false; ctx->cloud.zSettled = false; ctx->cloud.respawnEpoch = 0;
     return CPF_OK;
 }
 
@@ -900,7 +905,7 @@ int cpf_set_particles(cpf_context* ctx, int64_t n, const double* xyz, const int3
     if (cell) CPF_HIP(ctx, hipMemcpyAsync(ctx->cloud.cur.cell, cell, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     else CPF_HIP(ctx, hipMemsetAsync(ctx->cloud.cur.cell, 0xFF, (size_t)n * 4, ctx->stream));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->cloud.n = n; ctx->cloud.located = cell != nullptr;
+    ctx->cloud.n = n; ctx->cloud.located = cell != nullptr; ctx->cloud.respawnEpoch = 0;
     return CPF_OK;
 }
 
@@ -1362,6 +1367,125 @@ int cpf_get_occupancy(cpf_context* ctx, uint64_t* counts, int64_t* nSamples) {
         if (counts) CPF_HIP(ctx, hipMemcpyAsync(counts, ctx->mesh.occupancy, (size_t)ctx->mesh.nParent * 8, hipMemcpyDeviceToHost, ctx->stream));
         CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
+    return CPF_OK;
+}
+
+// ---- recycling: sink cells and a source box (cpf_recycle.hip) ---------------------------------
+namespace {
+int ensureRecycleCounts(cpf_context* ctx) {
+    if (ctx->recycleCounts) return CPF_OK;
+    DevBuf<unsigned long long> c;
+    CPF_HIP(ctx, c.alloc(4));
+    CPF_HIP(ctx, hipMemsetAsync(c, 0, 4 * 8, ctx->stream));
+    ctx->recycleCounts = std::move(c);
+    return CPF_OK;
+}
+}  // namespace
+
+int cpf_set_sink_cells(cpf_context* ctx, const int32_t* parentCells, int64_t n) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_set_sink_cells: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, n >= 0 && (parentCells || n == 0), CPF_ERR_ARG, "cpf_set_sink_cells: bad arguments");
+    for (int64_t k = 0; k < n; ++k)
+        CPF_REQUIRE(ctx, parentCells[k] >= 0 && parentCells[k] < ctx->mesh.nParent, CPF_ERR_ARG,
+                    "cpf_set_sink_cells: cell " + std::to_string(parentCells[k]) + " is not in [0, nCells)");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass over the old mask may still be running)
+    ctx->mesh.sinkMask = DevBuf<uint32_t>{};
+    if (n == 0) return CPF_OK;
+    // one bit per DERIVED cell: every derived cell of a sink parent is set
+    const int64_t nDerived = ctx->mesh.host.nCells;
+    std::vector<uint32_t> mask((size_t)((nDerived + 31) / 32), 0u);
+    const bool derived = !ctx->mesh.first.empty();
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t c = parentCells[k];
+        const int64_t lo = derived ? ctx->mesh.first[(size_t)c] : c, hi = derived ? ctx->mesh.first[(size_t)c + 1] : c + 1;
+        for (int64_t d = lo; d < hi; ++d) mask[(size_t)(d >> 5)] |= 1u << (d & 31);
+    }
+    DevBuf<uint32_t> dev;
+    CPF_HIP(ctx, dev.alloc(mask.size()));
+    CPF_HIP(ctx, hipMemcpy(dev, mask.data(), mask.size() * 4, hipMemcpyHostToDevice));
+    ctx->mesh.sinkMask = std::move(dev);
+    return CPF_OK;
+}
+
+int cpf_sink_apply_dev(cpf_context* ctx, int32_t* cell, int64_t n) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_sink_apply: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, n >= 0 && (cell || n == 0), CPF_ERR_ARG, "cpf_sink_apply_dev: bad arguments");
+    if (!ctx->mesh.sinkMask) return CPF_OK;                // no sink set: nothing runs
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    int r = ensureRecycleCounts(ctx);
+    if (r) return r;
+    CPF_HIP(ctx, cpf::sink_apply(ctx->stream, cell, n, ctx->mesh.sinkMask, ctx->mesh.host.nCells, ctx->recycleCounts));
+    return CPF_OK;
+}
+
+int cpf_sink_apply(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_sink_apply: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_sink_apply: no located particles");
+    return cpf_sink_apply_dev(ctx, ctx->cloud.cur.cell, ctx->cloud.n);
+}
+
+int cpf_respawn_box_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cell, const int64_t* gid, int64_t n,
+                        const double lower[3], const double upper[3], int64_t maxCount, uint32_t epoch) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_respawn_box: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, lower && upper && n >= 0 && n < ((int64_t)1 << 31) && (n == 0 || (x && y && z && cell)), CPF_ERR_ARG,
+                "cpf_respawn_box: bad arguments");
+    for (int k = 0; k < 3; ++k)
+        CPF_REQUIRE(ctx, std::isfinite(lower[k]) && std::isfinite(upper[k]) && upper[k] >= lower[k], CPF_ERR_ARG,
+                    "cpf_respawn_box: the box needs finite bounds with upper >= lower on every axis");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    int r = ensureRecycleCounts(ctx);
+    if (r) return r;
+    const bool limited = maxCount > 0 && maxCount < n;
+    if (limited) {
+        r = ensureScratch(ctx, cpf::respawn_scratch_bytes(n));
+        if (r) return r;
+    }
+    CPF_HIP(ctx, cpf::respawn_box(ctx->stream, x, y, z, cell, gid, n, lower, upper, maxCount, ctx->seed, epoch, meshView(ctx),
+                                  gridView(ctx), ctx->scratch, ctx->scratchBytes, ctx->recycleCounts));
+    return CPF_OK;
+}
+
+int cpf_respawn_box(cpf_context* ctx, const double lower[3], const double upper[3], int64_t maxCount) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_respawn_box: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_respawn_box: no located particles");
+    int r = cpf_respawn_box_dev(ctx, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell, ctx->cloud.cur.gid,
+                                ctx->cloud.n, lower, upper, maxCount, ctx->cloud.respawnEpoch);
+    if (r) return r;
+    ctx->cloud.zSettled = false;                    // (a respawned particle is live again, with a z the flat cycle never settled)
+    ++ctx->cloud.respawnEpoch;
+    return CPF_OK;
+}
+
+int cpf_get_recycle_counts(cpf_context* ctx, int64_t out[4]) {
+    CPF_REQUIRE(ctx, ctx && out, CPF_ERR_ARG, "null argument");
+    unsigned long long h[3] = {0, 0, 0};
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->recycleCounts) CPF_HIP(ctx, hipMemcpyAsync(h, ctx->recycleCounts, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 3; ++k) out[k] = (int64_t)h[k];
+    out[3] = (int64_t)ctx->cloud.respawnEpoch;
+    return CPF_OK;
+}
+
+int cpf_recycle_reset_counts(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    if (ctx->recycleCounts) {
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        CPF_HIP(ctx, hipMemsetAsync(ctx->recycleCounts, 0, 4 * 8, ctx->stream));
+    }
+    return CPF_OK;
+}
+
+int cpf_respawn_positions_host(uint32_t seed, const int64_t* gid, int64_t n, uint32_t epoch, const double lower[3],
+                               const double upper[3], double* xyz) {
+    if (n < 0 || !lower || !upper || (n > 0 && !xyz)) return CPF_ERR_ARG;
+    for (int64_t i = 0; i < n; ++i) cpf::respawn_position(seed, (uint64_t)(gid ? gid[i] : i), epoch, lower, upper, xyz + 3 * i);
     return CPF_OK;
 }
 

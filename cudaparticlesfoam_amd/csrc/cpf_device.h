@@ -280,6 +280,15 @@ hipError_t cell_ranges(hipStream_t st, const double* weights, int64_t nCells, in
 // parentOf null: the ids are parent ids already.  acc: 64-bit integers per PARENT cell
 hipError_t occupancy_accumulate(hipStream_t st, const int32_t* cell, int64_t n, const int32_t* parentOf, int64_t nDerived,
                                 unsigned long long* acc);
+// recycling (cpf_recycle.hip).  sink_apply: cell[i] = CPF_CELL_LOST for every i with 0 <= cell[i] < nDerived whose bit is set in mask
+// (ceil(nDerived / 32) words over DERIVED cells), *absorbed += their number.  respawn_box: the first maxCount (< 0: all) slots with
+// cell < 0, in array order, get the position respawn_position(seed, gid, epoch) (cpf_philox.h; gid null: the index) and the cell of
+// the initial locate; counters[1] += slots drawn, counters[2] += those found inside.  scratch: respawn_scratch_bytes(n) bytes
+hipError_t sink_apply(hipStream_t st, int32_t* cell, int64_t n, const uint32_t* mask, int64_t nDerived, unsigned long long* absorbed);
+size_t respawn_scratch_bytes(int64_t n);
+hipError_t respawn_box(hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid, int64_t n,
+                       const double lower[3], const double upper[3], int64_t maxCount, uint32_t seed, uint32_t epoch,
+                       const MeshView& m, const GridView& g, void* scratch, size_t scratchBytes, unsigned long long* counters);
 hipError_t unpack_arrivals(hipStream_t st, double* x, double* y, double* z, int32_t* cell, int64_t* gid,
                            int64_t nStay, const double* recvbuf, int64_t nRecv);
 // output of a sharded cloud (cpf_shard_gather): records of kOutputDoubles doubles = x, y, z, cell, gid, vx, vy, vz

@@ -10,6 +10,7 @@
 // divisions are IEEE.  tests/ compare bit-for-bit with an independent CPU statement.
 #include "cpf_device.h"
 
+#include "cpf_locate.h"
 #include "cpf_walk.h"
 
 #include <hipcub/hipcub.hpp>
@@ -648,31 +649,7 @@ __global__ __launch_bounds__(kBlock) void locate_initial_kernel(const double* __
                                                                 GridView g) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    const D3 P = {x[i], y[i], z[i]};
-    int found = CPF_CELL_LOST;
-    const bool inBox = P.x >= g.lo[0] && P.x <= g.hi[0] && P.y >= g.lo[1] && P.y <= g.hi[1] && P.z >= g.lo[2] &&
-                       P.z <= g.hi[2];
-    if (inBox) {
-        int b[3];
-        const double pv[3] = {P.x, P.y, P.z};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            long long q = (long long)floor((pv[k] - g.origin[k]) * g.invBin[k]);
-            q = q < 0 ? 0 : (q > g.dims[k] - 1 ? g.dims[k] - 1 : q);
-            b[k] = (int)q;
-        }
-        const int64_t bin = ((int64_t)b[2] * g.dims[1] + b[1]) * g.dims[0] + b[0];
-        for (int k = g.binOff[bin]; k < g.binOff[bin + 1] && found < 0; ++k) {
-            const int c = g.binCells[k];
-            bool inside = true;
-            for (int s = m.cellOff[c]; s < m.cellOff[c + 1]; ++s) {
-                const double4 pl = m.planes[s];
-                if (!(plane_dist(pl, P) <= 0.0)) { inside = false; break; }
-            }
-            if (inside) found = c;
-        }
-    }
-    cell[i] = found;
+    cell[i] = locate_point(D3{x[i], y[i], z[i]}, m.cellOff, m.planes, g);   // (cpf_locate.h: shared with the respawn kernel)
 }
 
 hipError_t launch_locate_initial(hipStream_t st, const double* x, const double* y, const double* z, int32_t* cell,

@@ -1,0 +1,48 @@
+// Philox4x32 and the respawn position drawn from it: shared by the step kernels' kick (cpf_walk.h, normal3), the recycling
+// kernels (cpf_recycle.hip) and, on the host, cpf_respawn_positions_host (cpf_api.cpp) -- one text for the device and the host.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace cpf {
+
+// Philox4x32-10 (Salmon et al. SC'11) keyed by (seed, "CPF1"), counter (gid, step): replaces the
+// 48-byte-per-particle cuRAND XORWOW state of cuda/particles.cu:524-575 with nothing at all.
+// Philox4x32-R (Salmon et al., SC'11).  R = 7: the variant with the fewest rounds that the paper reports as passing the
+// whole of BigCrush ("Crush-resistant"; R = 10 is Random123's default, with a safety margin).  Each round is two
+// quarter-rate 32 x 32 -> 64 multiplies (v_mad_u64_u32) and four XORs per lane and the streaming kernel is bound by its
+// vector ALU: measured on one box (pitzDaily, D = 1.5e-5, 1e7 particles) 10 -> 7 rounds = 0.1865 -> 0.1825 ms per launch;
+// the deviates as a whole (this + Box-Muller below) are 0.052 of the 0.188 ms (A/B build that returns constants instead).
+// oracle/cellwalk.c states the same function; its known-answer test runs at R = 10, where Random123 publishes vectors.
+#ifndef CPF_PHILOX_ROUNDS
+#define CPF_PHILOX_ROUNDS 7
+#endif
+__host__ __device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < CPF_PHILOX_ROUNDS; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
+        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
+// Where a respawned particle goes (cpf_respawn_box*): a pure function of (seed, gid, epoch) -- one Philox block, counter
+// (gid low, gid high, epoch, 0), key (seed, "CPF2": the kick's stream is keyed "CPF1", so the two never meet); word k gives
+// u_k = w_k * 2^-32 in [0, 1) exactly, and pos_k = lower_k + u_k * (upper_k - lower_k) with every operation rounded on its own
+// (-ffp-contract=off; the host's compile of this text has it too).
+__host__ __device__ __forceinline__ void respawn_position(uint32_t seed, uint64_t gid, uint32_t epoch, const double lower[3],
+                                                          const double upper[3], double pos[3]) {
+    uint32_t c[4] = {(uint32_t)gid, (uint32_t)(gid >> 32), epoch, 0u};
+    philox4x32(c, seed, 0x43504632u);
+    for (int k = 0; k < 3; ++k) {
+        const double u = (double)c[k] * 2.3283064365386963e-10;      // 2^-32
+        const double span = upper[k] - lower[k];
+        const double off = u * span;
+        pos[k] = lower[k] + off;
+    }
+}
+
+}  // namespace cpf

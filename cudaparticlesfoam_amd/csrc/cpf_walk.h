@@ -4,6 +4,7 @@
 #pragma once
 #include "cpf_accept.h"      // kTol, is_group, face_accept: the acceptance rule itself
 #include "cpf_device.h"
+#include "cpf_philox.h"    // philox4x32
 
 namespace cpf {
 
@@ -658,27 +659,7 @@ struct GlobalTracer {
     __device__ __forceinline__ double4 velocity(int cur) const { return m.U[cur]; }
 };
 
-// Philox4x32-10 (Salmon et al. SC'11) keyed by (seed, "CPF1"), counter (gid, step): replaces the
-// 48-byte-per-particle cuRAND XORWOW state of cuda/particles.cu:524-575 with nothing at all.
-// Philox4x32-R (Salmon et al., SC'11).  R = 7: the variant with the fewest rounds that the paper reports as passing the
-// whole of BigCrush ("Crush-resistant"; R = 10 is Random123's default, with a safety margin).  Each round is two
-// quarter-rate 32 x 32 -> 64 multiplies (v_mad_u64_u32) and four XORs per lane and the streaming kernel is bound by its
-// vector ALU: measured on one box (pitzDaily, D = 1.5e-5, 1e7 particles) 10 -> 7 rounds = 0.1865 -> 0.1825 ms per launch;
-// the deviates as a whole (this + Box-Muller below) are 0.052 of the 0.188 ms (A/B build that returns constants instead).
-// oracle/cellwalk.c states the same function; its known-answer test runs at R = 10, where Random123 publishes vectors.
-#ifndef CPF_PHILOX_ROUNDS
-#define CPF_PHILOX_ROUNDS 7
-#endif
-__device__ __forceinline__ void philox4x32(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < CPF_PHILOX_ROUNDS; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
+// philox4x32 (Philox4x32-R, R = CPF_PHILOX_ROUNDS = 7): cpf_philox.h, shared with the recycling kernels and the host
 // Three N(0,1) deviates for (particle gid, step) from ONE Philox4x32-7 block (parity with the reference's cuRAND stream is
 // statistical by contract, SURVEY.md 8c, so the arithmetic is free): Box-Muller evaluated with the fp32 hardware
 // transcendentals (v_log_f32, v_sqrt_f32, v_sin_f32 / v_cos_f32, whose argument is in revolutions: no 2*pi, no range

@@ -402,6 +402,53 @@ int cpf_occupancy_reset(cpf_context* ctx);
 int cpf_get_occupancy(cpf_context* ctx, uint64_t* counts, int64_t* nSamples);
 
 /* ---------------------------------------------------------------------------------------------
+ * recycling: sink cells and a source box -- an open system (inlet, outlet) at constant particle count
+ * NO REFERENCE COUNTERPART for any entry of this group: in the reference every boundary face reflects.  Here, BETWEEN step
+ * launches, a particle found in a sink cell becomes CPF_CELL_LOST -- a dead slot: the step kernels, frames, the sort and the
+ * occupancy samples skip it, as they always did -- and dead slots are given a fresh position in a source box and located anew.
+ * The cloud keeps its size and its particle ids; no step kernel knows of it.  The rule is "found in a sink cell when the sink is
+ * applied", NOT "crossed the patch": a particle that moves more than a cell per cycle can reflect off the outlet and leave the
+ * sink layer between two applications -- mark two layers of cells, or apply every cycle.
+ * Candidates for a respawn are the slots with cell < 0 -- lost, frozen, or never inside the mesh --, taken in ARRAY order up to
+ * maxCount (maxCount < 0: all of them).  For the context's own cloud the array order is whatever the last sort left (dead slots
+ * at the tail, in stable order): a limited respawn chooses WHICH dead particles by that order, their COUNT is exact; an unlimited
+ * one does not depend on order at all.  The position is a pure function of (seed, particle id, epoch): Philox4x32-7, counter
+ * (id low 32, id high 32, epoch, 0), key (seed of cpf_set_seed, 0x43504632); u_k = word_k * 2^-32, pos_k = lower_k + u_k * (upper_k -
+ * lower_k), each operation rounded on its own.  The cell is cpf_locate_initial's; a point outside the mesh leaves the slot dead
+ * (CPF_CELL_LOST, at the drawn point): it is a candidate again at the next epoch.
+ * Three 64-bit counters accumulate on the device: absorbed, drawn, placed (drawn and found inside).
+ * cpf_shard_* does not recycle; the _dev entries and the id-keyed positions are what a host with a sharded cloud would build on.
+ * ------------------------------------------------------------------------------------------- */
+/* NO REFERENCE COUNTERPART.  The sink set: n cell ids of the mesh as given (host memory; on a mesh with decomposed cells every
+ * derived cell of a listed cell is a sink).  n == 0 clears the set.  CPF_ERR_STATE without a mesh, CPF_ERR_ARG for an id outside
+ * [0, nCells).  The set belongs to the mesh: cpf_set_mesh* drops it. */
+int cpf_set_sink_cells(cpf_context* ctx, const int32_t* parentCells, int64_t n);
+/* NO REFERENCE COUNTERPART.  Every particle of the context-owned cloud that sits in a sink cell becomes CPF_CELL_LOST; its position
+ * stays.  Asynchronous on the context's stream.  Without a sink set the call succeeds and does nothing.  CPF_ERR_STATE without a
+ * mesh or without located particles. */
+int cpf_sink_apply(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  The same on a caller-owned device array of DERIVED ids (the convention of the other _dev entries). */
+int cpf_sink_apply_dev(cpf_context* ctx, int32_t* cell, int64_t n);
+/* NO REFERENCE COUNTERPART.  Respawns up to maxCount (< 0: all) dead slots of the context-owned cloud in the box [lower, upper]
+ * with the cloud's own epoch counter, which starts at 0 with a new cloud (cpf_alloc_particles, cpf_seed_box, cpf_set_particles)
+ * and goes up by one with every call.  Asynchronous on the context's stream.  The cloud's z no longer counts as settled
+ * (CPF_STEP_Z_SETTLED), as after cpf_locate_initial.  CPF_ERR_ARG when upper < lower on any axis; CPF_ERR_STATE without a mesh or
+ * without located particles. */
+int cpf_respawn_box(cpf_context* ctx, const double lower[3], const double upper[3], int64_t maxCount);
+/* NO REFERENCE COUNTERPART.  The same on caller-owned device arrays (gid nullable: id = index; n < 2^31) with the caller's epoch. */
+int cpf_respawn_box_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cell, const int64_t* gid, int64_t n,
+                        const double lower[3], const double upper[3], int64_t maxCount, uint32_t epoch);
+/* NO REFERENCE COUNTERPART.  Waits for the context's stream; out = absorbed, drawn, placed since the last reset, and the epochs
+ * (cpf_respawn_box calls) of the context's own cloud. */
+int cpf_get_recycle_counts(cpf_context* ctx, int64_t out[4]);
+/* NO REFERENCE COUNTERPART.  Zeroes absorbed, drawn and placed (asynchronous on the context's stream); the epoch stays. */
+int cpf_recycle_reset_counts(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  The respawn position on the host alone -- no context, no GPU; compiled from the text the kernel is
+ * compiled from: xyz[n][3] for the ids gid[n] (null: 0 .. n-1). */
+int cpf_respawn_positions_host(uint32_t seed, const int64_t* gid, int64_t n, uint32_t epoch, const double lower[3],
+                               const double upper[3], double* xyz);
+
+/* ---------------------------------------------------------------------------------------------
  * device-array level (framework hosts that own the particle arrays, multi-GPU sharding)
  * SoA fp64 positions x,y,z [n]; cell [n] int32; gid [n] int64 global particle id (nullable:
  * gid = index); vel [n][3] (nullable unless CPF_STEP_STORE_VEL).

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Compiler resource usage of every step-kernel instantiation and of the occupancy kernel -> profiles/<label>_resource_usage.txt
+"""Compiler resource usage of every step-kernel instantiation, of the occupancy kernel and of the recycling kernels -> profiles/<label>_resource_usage.txt
 (hipcc -Rpass-analysis=kernel-resource-usage; runs without a GPU).  python tools/resource_usage.py r02
 
 python tools/resource_usage.py --digest <label> [--root <checkout>] [file.hip ...] -> profiles/<label>_code_digest.txt: one line
@@ -15,6 +15,10 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CS = os.path.join(ROOT, "cudaparticlesfoam_amd", "csrc")
+
+
+# the kernels collect() lists, by a part of their names (cpf_recycle.hip: sink_kernel, respawn_count / _scan / _place_kernel)
+LISTED = ("step_kernel", "occupancy_kernel", "sink_kernel", "respawn_")
 
 
 def hipcc_cmd(src, root=ROOT):
@@ -34,7 +38,7 @@ def parse(remarks):
         if not m:
             continue
         name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip().split("(")[0]
-        if "step_kernel" not in name and "occupancy_kernel" not in name:
+        if not any(k in name for k in LISTED):
             continue
         g = lambda k: (re.search(k + r":\s*(\S+)", b) or [None, "?"])[1]   # noqa: E731
         rows.append((name, g("VGPRs"), g("AGPRs"), g("TotalSGPRs"), g(r"ScratchSize \[bytes/lane\]"),
@@ -44,7 +48,7 @@ def parse(remarks):
 
 def collect():
     rows = []
-    for src in ("cpf_stream.hip", "cpf_kernels.hip", "cpf_occupancy.hip"):
+    for src in ("cpf_stream.hip", "cpf_kernels.hip", "cpf_occupancy.hip", "cpf_recycle.hip"):
         r = subprocess.run(hipcc_cmd(src) + ["-c", "-o", "/dev/null"], capture_output=True, text=True)
         rows += parse(r.stderr)
     return rows
@@ -106,7 +110,7 @@ def main():
         return main_digest(sys.argv[2:])
     label = sys.argv[1] if len(sys.argv) > 1 else "r03"
     rows = collect()
-    out = ["# Compiler resource usage of the step kernels and the occupancy kernel: hipcc -O3 --offload-arch=gfx950 -ffp-contract=off",
+    out = ["# Compiler resource usage of the step kernels, the occupancy kernel and the recycling kernels: hipcc -O3 --offload-arch=gfx950 -ffp-contract=off",
            "# -Rpass-analysis=kernel-resource-usage (ROCm 7.2).  tools/resource_usage.py " + label,
            "# kernel | VGPRs | AGPRs | SGPRs | scratch B/lane | waves/SIMD (registers) | SGPR spills | VGPR spills | LDS B/block"]
     out += [" | ".join(r) for r in rows]
