@@ -1,6 +1,6 @@
 // C-ABI layer of libcudaParticleAdvection.so: context, device memory, call-order checks, errors.
-// Every entry point declared in include/cpf.h is defined here; kernels live in cpf_kernels.hip
-// and cpf_handoff.hip, the host-side mesh ingest in cpf_mesh.cpp.
+// Every entry point declared in include/cpf.h is defined here; kernels live in cpf_kernels.hip,
+// cpf_sort.hip and cpf_handoff.hip, the host-side mesh ingest in cpf_mesh.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -156,7 +156,7 @@ struct cpf_context {
     // ---- options: they survive a new mesh and a new cloud
     bool zFold = true;               // "z_fold": mirror the kicked end point about the planes of a one-cell-thick mesh before the walk
     bool boxRecords = true;         // "box_records": 0 = never use them (diagnostics; bit-identical either way)
-    int sortMethod = 2;             // "sort_method": the (key, index) sort: 2 = this library's radix sort (cpf_kernels.hip, rt_sort_pairs), 0 = hipcub's;
+    int sortMethod = 2;             // "sort_method": the (key, index) sort: 2 = this library's radix sort (cpf_sort.hip, rt_sort_pairs), 0 = hipcub's;
                                     // the same order either way
     int sortCurve = -1;             // "sort_curve": -1 = Morton rank when the cloud has fewer than 8 particles per cell, 0 = cell id, 1 = Morton rank
     int sortInterval = 50;                      // "sort_interval": cpf_step re-sorts the owned cloud by cell every N cycles

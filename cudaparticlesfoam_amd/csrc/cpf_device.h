@@ -260,12 +260,13 @@ hipError_t launch_stage_move(hipStream_t st, double* P, double* disps, int64_t n
 hipError_t launch_aos_to_soa(hipStream_t st, const double* P, double* x, double* y, double* z, int64_t n);
 hipError_t launch_soa_to_aos(hipStream_t st, const double* x, const double* y, const double* z, double* P, int64_t n);
 
+// the re-sort by cell (cpf_sort.hip).  ox ... ogid: all null = in place; occupied, rank: may be null; method: "sort_method" -- 0 = the
+// library radix sort (the order tests compare with), otherwise this library's own
 size_t sort_scratch_bytes(int64_t n, int endBit);
 hipError_t sort_by_cell(hipStream_t st, double* x, double* y, double* z, int32_t* cell, int64_t* gid, double* vel3,
                         int64_t n, int endBit, const float* cellBox, const int* subBits, const int* subOrder,
-                        void* scratch, size_t scratchBytes, double* ox = nullptr, double* oy = nullptr, double* oz = nullptr,
-                        int32_t* ocell = nullptr, int64_t* ogid = nullptr, unsigned long long* occupied = nullptr,
-                        const int32_t* rank = nullptr, int method = 1);      // method 0: the library radix sort (the order tests compare with)
+                        void* scratch, size_t scratchBytes, double* ox, double* oy, double* oz, int32_t* ocell, int64_t* ogid,
+                        unsigned long long* occupied, const int32_t* rank, int method);
 
 // multi-GPU hand-off (cpf_handoff.hip)
 size_t handoff_scratch_bytes(int64_t n, int nRanks);

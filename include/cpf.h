@@ -345,7 +345,7 @@ int cpf_set_seed(cpf_context* ctx, uint32_t seed);
  *   "coop_max_cells" test hook: kernel 3 addresses cell records with 32-bit byte offsets and is not used for meshes of
  *                   more than 2^24 cells (kernel 4 runs instead); a smaller limit exercises that switch on small meshes
  *   "sort_method"   (2) the (key, index) sort behind cpf_sort_by_cell*: 2 = this library's stable radix sort with 8-bit digits and an
- *                   LDS tile reorder (csrc/cpf_kernels.hip, rt_sort_pairs), 0 = hipcub::DeviceRadixSort.  The same order either way,
+ *                   LDS tile reorder (csrc/cpf_sort.hip, rt_sort_pairs), 0 = hipcub::DeviceRadixSort.  The same order either way,
  *                   particle for particle (tests).  Measured, round 5, 1e7 particles sorted 25 cycles of diffusion ago: 0.54 / 0.64
  *                   ms per sort -- 0.30 ms of it building the keys and gathering the particle records, which both share; on
  *                   TJunction's 24 key bits (4e6 particles) 0.24 / 0.27 ms
@@ -460,8 +460,8 @@ int cpf_locate_initial_dev(cpf_context* ctx, const double* x, const double* y, c
 /* cudaInitParticles on caller arrays; particle ids first..first+n-1 (sharded seeding) */
 int cpf_seed_box_dev(cpf_context* ctx, double* x, double* y, double* z, int64_t first, int64_t n,
                      const double lower[3], const double upper[3], int order);
-/* perm[n] (int32 scratch, out): stable order by cell; arrays are permuted in place via tmp
- * buffers owned by the context. */
+/* Stable order by cell (lost / frozen particles at the tail), then by position inside the cell; the arrays are permuted in
+ * place through scratch owned by the context.  gid may be NULL. */
 int cpf_sort_by_cell_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cell, int64_t* gid,
                          int64_t n);
 /* The same order written into a second set of arrays (none may alias its input; gid / ogid nullable together); the

@@ -1335,7 +1335,7 @@ def test_sparse_clouds_are_sorted_along_the_morton_curve(gpu_ctx_factory, oracle
 
 @pytest.mark.parametrize("case", ["pitz", "box3d", "box3d_curve", "pitz_census", "tiny"])
 def test_hand_written_key_sort_gives_the_library_sort_order(case, setup, gpu_ctx_factory):
-    """Option "sort_method" 2 (this library's stable radix sort, the default: csrc/cpf_kernels.hip rt_sort_pairs -- three passes of 7
+    """Option "sort_method" 2 (this library's stable radix sort, the default: csrc/cpf_sort.hip rt_sort_pairs -- three passes of 7
     bits on pitzDaily, three of 8 on a 3-D mesh) orders the cloud exactly like hipcub::DeviceRadixSort (method 0): same
     permutation, particle for particle -- lost particles at the tail, sizes that do not fill the last tile, the Morton major
     key, the occupied-cell census, in place and into a second set of arrays."""

@@ -3,7 +3,7 @@
 (hipcc -Rpass-analysis=kernel-resource-usage; runs without a GPU).  python tools/resource_usage.py r02
 
 python tools/resource_usage.py --digest <label> [--root <checkout>] [file.hip ...] -> profiles/<label>_code_digest.txt: one line
-per kernel of cpf_stream.hip and cpf_kernels.hip -- demangled name | instruction count | SHA-256 of its normalised instruction
+per kernel of cpf_stream.hip, cpf_kernels.hip and cpf_sort.hip -- demangled name | instruction count | SHA-256 of its normalised instruction
 stream -- to compare the generated code of two commits (the other one through ``git worktree add`` and --root).  A refactor
 that claims "no instruction changes" shows two listings that ``diff`` finds equal."""
 import hashlib
@@ -55,10 +55,15 @@ def collect():
 
 
 def kernel_bodies(asm):
-    """mangled kernel name -> its instructions (labels, directives and comments dropped)."""
+    """mangled kernel name -> its instructions (labels, directives and comments dropped).  Only what the listing types as a
+    function: a library's constant table (rocprim has one) is a _Z label too, and the text behind the last one is the metadata."""
     out, name = {}, None
+    functions = set(re.findall(r"^\s*\.type\s+(_Z\w+),@function", asm, re.M))
     for line in asm.splitlines():
         m = re.match(r"^(_Z\w+):", line)
+        if m and m.group(1) not in functions:
+            name = None
+            continue
         if m:
             name = m.group(1); out[name] = []
             continue
@@ -89,7 +94,7 @@ def main_digest(argv):
     root = ROOT
     if "--root" in argv:
         i = argv.index("--root"); root = os.path.abspath(argv[i + 1]); del argv[i:i + 2]
-    label, srcs = argv[0], argv[1:] or ["cpf_stream.hip", "cpf_kernels.hip"]
+    label, srcs = argv[0], argv[1:] or ["cpf_stream.hip", "cpf_kernels.hip", "cpf_sort.hip"]
     out = ["# Generated code of the kernels: hipcc -S --cuda-device-only with csrc/Makefile's flags (gfx950), per kernel the",
            "# SHA-256 of its instructions without comments, directives, labels and the function index of .LBB<function>_<block>.",
            "# tools/resource_usage.py --digest " + label,
