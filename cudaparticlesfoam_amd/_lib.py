@@ -154,6 +154,15 @@ SIGNATURES = {
     "cpf_get_recycle_counts": (_int, [_ctx, _vp]),
     "cpf_recycle_reset_counts": (_int, [_ctx]),
     "cpf_respawn_positions_host": (_int, [_u32, _vp, _i64, _u32, _vp, _vp, _vp]),
+    "cpf_age_enable": (_int, [_ctx, _i32, _i32]),
+    "cpf_age_disable": (_int, [_ctx]),
+    "cpf_age_sample": (_int, [_ctx]),
+    "cpf_age_reset": (_int, [_ctx]),
+    "cpf_get_age_histogram": (_int, [_ctx, _vp, _i32]),
+    "cpf_get_age_field": (_int, [_ctx, _vp, _vp, C.POINTER(_i64)]),
+    "cpf_get_ages": (_int, [_ctx, _vp]),
+    "cpf_age_get_births": (_int, [_ctx, _vp]),
+    "cpf_age_set_births": (_int, [_ctx, _vp]),
     "cpf_set_velocity": (_int, [_ctx, _vp, _i64]),
     "cpf_set_velocity_dev": (_int, [_ctx, _vp, _i64]),
     "cpf_alloc_particles": (_int, [_ctx, _i64]),

@@ -292,6 +292,73 @@ class Context:
     def recycle_reset_counts(self):
         self._ck(self.lib.cpf_recycle_reset_counts(self.h))
 
+    # -- tracer age: residence times at the sink, the mean-age field (include/cpf.h "tracer age")
+    def age_enable(self, bin_cycles: int, n_bins: int):
+        """Turns age tracking of the context-owned cloud on (or starts it anew): everybody is born now; ``n_bins`` residence-time
+        bins of ``bin_cycles`` cycles, the last one open-ended."""
+        self._ck(self.lib.cpf_age_enable(self.h, int(bin_cycles), int(n_bins)))
+        self._age_bins = (int(bin_cycles), int(n_bins))
+
+    def age_disable(self):
+        self._ck(self.lib.cpf_age_disable(self.h))
+
+    def age_sample(self):
+        """One sample of the age field: every live particle adds its age to its cell's sum and 1 to its count; asynchronous."""
+        self._ck(self.lib.cpf_age_sample(self.h))
+
+    def age_reset(self):
+        """Zeroes the histogram and the field; the birth stamps stay."""
+        self._ck(self.lib.cpf_age_reset(self.h))
+
+    def age_histogram(self) -> np.ndarray:
+        """uint64 [n_bins]: absorptions since the last reset by age // bin_cycles; synchronises."""
+        n_bins = getattr(self, "_age_bins", (1, 1))[1]
+        bins = np.zeros(n_bins, np.uint64)
+        self._ck(self.lib.cpf_get_age_histogram(self.h, _ptr(bins), n_bins))
+        return bins
+
+    def age_field(self):
+        """(age_sum uint64 [n_cells], count uint64 [n_cells], n_samples) per parent cell since the last reset; synchronises."""
+        s, c = np.zeros(self.n_cells, np.uint64), np.zeros(self.n_cells, np.uint64)
+        ns = C.c_int64(0)
+        self._ck(self.lib.cpf_get_age_field(self.h, _ptr(s), _ptr(c), C.byref(ns)))
+        return s, c, ns.value
+
+    def ages(self) -> np.ndarray:
+        """int64 [n] in particle-id order: age in cycles, -1 for a dead slot; synchronises."""
+        a = np.empty(self.n, np.int64)
+        self._ck(self.lib.cpf_get_ages(self.h, _ptr(a)))
+        return a
+
+    def age_births(self) -> np.ndarray:
+        """uint32 [n] in particle-id order: the cycle count at which each particle last became live."""
+        b = np.empty(self.n, np.uint32)
+        self._ck(self.lib.cpf_age_get_births(self.h, _ptr(b)))
+        return b
+
+    def age_set_births(self, births):
+        b = np.ascontiguousarray(births, dtype=np.uint32).reshape(-1)
+        if b.size != self.n:
+            raise ValueError("age_set_births: %d stamps for %d particles" % (b.size, self.n))
+        self._ck(self.lib.cpf_age_set_births(self.h, _ptr(b)))
+
+    def rtd(self, dt: float):
+        """Residence-time distribution at the sink: (edges in seconds [n_bins + 1], counts uint64 [n_bins]); the last bin is
+        open-ended (its upper edge is inf)."""
+        counts = self.age_histogram()
+        bin_cycles, n_bins = self._age_bins
+        edges = np.arange(n_bins + 1, dtype=np.float64) * (bin_cycles * float(dt))
+        edges[-1] = np.inf
+        return edges, counts
+
+    def mean_age(self, dt: float) -> np.ndarray:
+        """Mean age in seconds of the particles found in every cell over the samples taken: age_sum / count * dt, NaN where no
+        particle was found."""
+        s, c, _ = self.age_field()
+        out = np.full(s.size, np.nan)
+        np.divide(s.astype(np.float64), c.astype(np.float64), out=out, where=c > 0)
+        return out * float(dt)
+
     def cell_ranges_dev(self, weights, n_ranks, cell_lo):
         self._ck(self.lib.cpf_cell_ranges_dev(self.h, weights, n_ranks, cell_lo))
 
@@ -537,6 +604,11 @@ class CudaParticles:
     ``seedingBox``).  When ``recycleInterval`` is positive, at every cycle count that is a multiple of it the particles found in a
     sink cell are absorbed (``Context.sink_apply``) and every dead slot is respawned in the source box
     (``Context.respawn_box``), before the occupancy sample if one is due: an inlet and an outlet at constant particle count.
+
+    Two more, also this library's own: ``ageBins`` (default 0 = off) and ``ageBinCycles`` (default: ``recycleInterval``, else 1).
+    When ``ageBins`` is positive, age tracking (``Context.age_enable``) starts once the cloud is located: every absorption adds a
+    residence time to ``rtd()``, and wherever an occupancy sample is taken the age field is sampled too, after recycling, for
+    ``mean_age()``.
     """
 
     def __init__(self, mesh, U, particle_dict: Optional[dict] = None, device: int = 0,
@@ -554,6 +626,8 @@ class CudaParticles:
         self.recycleInterval = int(d.get("recycleInterval", 0))         # this library's own keys, like occupancyInterval
         self.sinkCells = d.get("sinkCells", None)
         self.sourceBox = d.get("sourceBox", self.seedingBox)
+        self.ageBins = int(d.get("ageBins", 0))
+        self.ageBinCycles = int(d.get("ageBinCycles", self.recycleInterval if self.recycleInterval > 0 else 1))
         # hard-coded switches of the fragment (src/initCuda.H:64-72)
         self.usingAdvection = True
         self.usingBrownianMotion = True
@@ -576,6 +650,8 @@ class CudaParticles:
             self.ctx.seed_box(self.numParticles, lo, hi, seed_order)
         self.outOfDomain = self.ctx.locate_initial()       # RTQuery + cudaReportParticles
         self.ctx.sort_by_cell()
+        if self.ageBins > 0:
+            self.ctx.age_enable(self.ageBinCycles, self.ageBins)
         if self.writer is not None:
             # frame 0 carries the velocities of one advect and out-of-domain particles as inactive, like the reference
             # (src/initCuda.H:184-201): a cycle of zero length (moves nothing, does not count as a step)
@@ -621,6 +697,8 @@ class CudaParticles:
                 self.ctx.respawn_box(self.sourceBox[0], self.sourceBox[1], -1)
             if self.occupancyInterval > 0 and self.step % self.occupancyInterval == 0:
                 self.ctx.occupancy_sample()
+                if self.ageBins > 0:
+                    self.ctx.age_sample()
         return n_cycles
 
     def particles(self):
@@ -633,6 +711,14 @@ class CudaParticles:
     def recycle_counts(self):
         """absorbed, drawn, placed and epochs of the run so far (``Context.recycle_counts``)."""
         return self.ctx.recycle_counts()
+
+    def rtd(self):
+        """Residence-time distribution of the absorbed particles, (edges in seconds, counts), with ``ageBins`` set (``Context.rtd``)."""
+        return self.ctx.rtd(self.dt)
+
+    def mean_age(self):
+        """Mean age in seconds per cell over the samples ``occupancyInterval`` took, with ``ageBins`` set (``Context.mean_age``)."""
+        return self.ctx.mean_age(self.dt)
 
     def close(self):
         self.ctx.close()

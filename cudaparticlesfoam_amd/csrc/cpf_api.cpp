@@ -97,6 +97,17 @@ struct Cloud {
     uint32_t respawnEpoch = 0;  // cpf_respawn_box calls on this cloud so far: the epoch of the next one's positions
 };
 
+// Tracer age of the context's own cloud (cpf_age_*; cpf_age.hip).  The stamps belong to a cloud, the field to a mesh: a new cloud
+// and a new mesh each replace the group with an empty one.
+struct Age {
+    bool on = false;
+    int32_t binCycles = 1, nBins = 0;
+    DevBuf<uint32_t> birth;                 // [cloud.n] by particle id: the cycle counter when the particle last became live
+    DevBuf<unsigned long long> hist;        // [nBins] absorptions by age / binCycles, the last bin open-ended
+    DevBuf<unsigned long long> field;       // [nParent][2] = age sum, count of the samples since the last reset
+    int64_t samples = 0;
+};
+
 // asynchronous output (cpf_write_vtu_async): one frame in flight.  Lives as long as the context.
 struct FrameWriter {
     std::thread thread;
@@ -169,7 +180,7 @@ struct cpf_context {
     bool vertexFast = true;                     // cpf_set_option("vertex_fast")
     uint32_t seed = 1591593751u;                // cuda/particles.cu:544
     // ---- the groups
-    Mesh mesh; TetField tet; Cloud cloud; FrameWriter frame; Timing timing;
+    Mesh mesh; TetField tet; Cloud cloud; Age age; FrameWriter frame; Timing timing;
     // ---- what lives as long as the context
     DevBuf<char> scratch;
     size_t scratchBytes = 0;
@@ -266,6 +277,15 @@ int ensureScratch(cpf_context* ctx, size_t bytes) {
     return CPF_OK;
 }
 
+// age tracking off (cpf_age_disable, a new cloud): a pass over the stamps may still be running
+int dropAge(cpf_context* ctx) {
+    if (!ctx->age.on) return CPF_OK;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->age = Age{};
+    return CPF_OK;
+}
+
 int sortEndBit(const cpf_context* ctx) {
     int bits = 1;
     while (((int64_t)1 << bits) < ctx->mesh.host.nCells + 2) ++bits;   // the all-ones key of lost/frozen sorts last
@@ -318,6 +338,7 @@ int setMeshImpl(cpf_context* ctx, const double* points, int64_t nPoints, const L
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->mesh = Mesh{};
     ctx->tet = TetField{};
+    ctx->age = Age{};
     ctx->streamState.flatField = false;
     ctx->mesh.host = std::move(t);
     ctx->mesh.nParent = nCells;
@@ -864,6 +885,7 @@ int cpf_alloc_particles(cpf_context* ctx, int64_t capacity) {
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->cloud = Cloud{};
+    ctx->age = Age{};
     const size_t c = (size_t)capacity;
     CPF_HIP(ctx, ctx->cloud.cur.alloc(c));
     CPF_HIP(ctx, ctx->cloud.vel.alloc(c * 3));
@@ -877,6 +899,7 @@ int cpf_seed_box(cpf_context* ctx, int64_t n, const double lower[3], const doubl
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, lower && upper && n > 0, CPF_ERR_ARG, "cpf_seed_box: bad arguments");
     if (ctx->cloud.cap < n) { int r = cpf_alloc_particles(ctx, n); if (r) return r; }
+    if (int r = dropAge(ctx)) return r;                     // (a new cloud: the stamps were the old one's)
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, cpf::launch_seed_box(ctx->stream, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, 0, n, lower, upper, order));
     CPF_HIP(ctx, cpf::launch_iota64(ctx->stream, ctx->cloud.cur.gid, n, 0));
@@ -889,9 +912,11 @@ int cpf_set_particles(cpf_context* ctx, int64_t n, const double* xyz, const int3
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, xyz && n > 0, CPF_ERR_ARG, "cpf_set_particles: bad arguments");
     if (ctx->cloud.cap < n) { int r = cpf_alloc_particles(ctx, n); if (r) return r; }
+    int r = dropAge(ctx);                                   // (a new cloud: the stamps were the old one's)
+    if (r) return r;
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     ctx->cloud.zSettled = false;
-    int r = ensureScratch(ctx, (size_t)n * 24);
+    r = ensureScratch(ctx, (size_t)n * 24);
     if (r) return r;
     CPF_HIP(ctx, hipMemcpyAsync(ctx->scratch, xyz, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
     CPF_HIP(ctx, cpf::launch_unpack_xyz(ctx->stream, (const double*)ctx->scratch.get(), ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, n));
@@ -1425,7 +1450,16 @@ int cpf_sink_apply(cpf_context* ctx) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_sink_apply: call cpf_set_mesh first");
     CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_sink_apply: no located particles");
-    return cpf_sink_apply_dev(ctx, ctx->cloud.cur.cell, ctx->cloud.n);
+    if (!ctx->age.on) return cpf_sink_apply_dev(ctx, ctx->cloud.cur.cell, ctx->cloud.n);
+    // age tracking: the same pass, which also bins the age of every particle it absorbs (cpf_age.hip)
+    if (!ctx->mesh.sinkMask) return CPF_OK;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    int r = ensureRecycleCounts(ctx);
+    if (r) return r;
+    CPF_HIP(ctx, cpf::age_absorb(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->age.birth, ctx->cloud.n, ctx->mesh.sinkMask,
+                                 ctx->mesh.host.nCells, ctx->recycleCounts, ctx->stepCounter, ctx->age.binCycles, ctx->age.nBins,
+                                 ctx->age.hist));
+    return CPF_OK;
 }
 
 int cpf_respawn_box_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cell, const int64_t* gid, int64_t n,
@@ -1454,6 +1488,14 @@ int cpf_respawn_box(cpf_context* ctx, const double lower[3], const double upper[
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_respawn_box: call cpf_set_mesh first");
     CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_respawn_box: no located particles");
+    bool boxOk = lower && upper;                    // (a box the respawn is about to refuse: no stamp either)
+    for (int k = 0; k < 3 && boxOk; ++k) boxOk = std::isfinite(lower[k]) && std::isfinite(upper[k]) && upper[k] >= lower[k];
+    if (ctx->age.on && boxOk && maxCount != 0) {
+        // age tracking: every candidate is born now -- the ones this call leaves dead have no age, and are stamped again by the
+        // call that places them
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        CPF_HIP(ctx, cpf::age_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->age.birth, ctx->cloud.n, ctx->stepCounter));
+    }
     int r = cpf_respawn_box_dev(ctx, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell, ctx->cloud.cur.gid,
                                 ctx->cloud.n, lower, upper, maxCount, ctx->cloud.respawnEpoch);
     if (r) return r;
@@ -1486,6 +1528,121 @@ int cpf_respawn_positions_host(uint32_t seed, const int64_t* gid, int64_t n, uin
                                const double upper[3], double* xyz) {
     if (n < 0 || !lower || !upper || (n > 0 && !xyz)) return CPF_ERR_ARG;
     for (int64_t i = 0; i < n; ++i) cpf::respawn_position(seed, (uint64_t)(gid ? gid[i] : i), epoch, lower, upper, xyz + 3 * i);
+    return CPF_OK;
+}
+
+// ---- tracer age: birth stamps by particle id, residence times at the sink, the mean-age field (cpf_age.hip) ----------------
+int cpf_age_enable(cpf_context* ctx, int32_t binCycles, int32_t nBins) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_age_enable: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_age_enable: no located particles");
+    CPF_REQUIRE(ctx, binCycles >= 1 && nBins >= 1 && nBins <= 4096, CPF_ERR_ARG, "cpf_age_enable: binCycles >= 1 and 1 <= nBins <= 4096");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass over the old tables may still be running)
+    ctx->age = Age{};
+    Age a;                                                  // moved in whole: a failure part-way leaves tracking off
+    const size_t n = (size_t)ctx->cloud.n, nField = (size_t)ctx->mesh.nParent * 2;
+    CPF_HIP(ctx, a.birth.alloc(n));
+    CPF_HIP(ctx, a.hist.alloc((size_t)nBins));
+    CPF_HIP(ctx, a.field.alloc(nField));
+    CPF_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.birth.get()), (int)ctx->stepCounter, n, ctx->stream));
+    CPF_HIP(ctx, hipMemsetAsync(a.hist, 0, (size_t)nBins * 8, ctx->stream));
+    CPF_HIP(ctx, hipMemsetAsync(a.field, 0, nField * 8, ctx->stream));
+    a.on = true; a.binCycles = binCycles; a.nBins = nBins;
+    ctx->age = std::move(a);
+    return CPF_OK;
+}
+
+int cpf_age_disable(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    return dropAge(ctx);
+}
+
+int cpf_age_sample(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->age.on, CPF_ERR_STATE, "cpf_age_sample: call cpf_age_enable first");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, cpf::age_field(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->age.birth, ctx->cloud.n, ctx->mesh.parentOf,
+                                ctx->mesh.host.nCells, ctx->stepCounter, ctx->age.field));
+    ++ctx->age.samples;
+    return CPF_OK;
+}
+
+int cpf_age_reset(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->age.on, CPF_ERR_STATE, "cpf_age_reset: call cpf_age_enable first");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemsetAsync(ctx->age.hist, 0, (size_t)ctx->age.nBins * 8, ctx->stream));
+    CPF_HIP(ctx, hipMemsetAsync(ctx->age.field, 0, (size_t)ctx->mesh.nParent * 16, ctx->stream));
+    ctx->age.samples = 0;
+    return CPF_OK;
+}
+
+int cpf_get_age_histogram(cpf_context* ctx, uint64_t* bins, int32_t nBins) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->age.on, CPF_ERR_STATE, "cpf_get_age_histogram: call cpf_age_enable first");
+    CPF_REQUIRE(ctx, bins && nBins == ctx->age.nBins, CPF_ERR_ARG, "cpf_get_age_histogram: nBins is not cpf_age_enable's");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemcpyAsync(bins, ctx->age.hist, (size_t)nBins * 8, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPF_OK;
+}
+
+int cpf_get_age_field(cpf_context* ctx, uint64_t* ageSum, uint64_t* count, int64_t* nSamples) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->age.on, CPF_ERR_STATE, "cpf_get_age_field: call cpf_age_enable first");
+    if (nSamples) *nSamples = ctx->age.samples;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nc = (size_t)ctx->mesh.nParent;
+    std::vector<unsigned long long> h(nc * 2);
+    if (ageSum || count) CPF_HIP(ctx, hipMemcpyAsync(h.data(), ctx->age.field, nc * 16, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t c = 0; c < nc; ++c) {
+        if (ageSum) ageSum[c] = h[2 * c];
+        if (count) count[c] = h[2 * c + 1];
+    }
+    return CPF_OK;
+}
+
+int cpf_age_get_births(cpf_context* ctx, uint32_t* birth) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->age.on, CPF_ERR_STATE, "cpf_age_get_births: call cpf_age_enable first");
+    CPF_REQUIRE(ctx, birth, CPF_ERR_ARG, "cpf_age_get_births: null array");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemcpyAsync(birth, ctx->age.birth, (size_t)ctx->cloud.n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPF_OK;
+}
+
+int cpf_age_set_births(cpf_context* ctx, const uint32_t* birth) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->age.on, CPF_ERR_STATE, "cpf_age_set_births: call cpf_age_enable first");
+    CPF_REQUIRE(ctx, birth, CPF_ERR_ARG, "cpf_age_set_births: null array");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemcpyAsync(ctx->age.birth, birth, (size_t)ctx->cloud.n * 4, hipMemcpyHostToDevice, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPF_OK;
+}
+
+int cpf_get_ages(cpf_context* ctx, int64_t* age) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->age.on, CPF_ERR_STATE, "cpf_get_ages: call cpf_age_enable first");
+    CPF_REQUIRE(ctx, age, CPF_ERR_ARG, "cpf_get_ages: null array");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    // a read-back for checks and restarts, not a hot path: the cells in id order (cpf_get_particles' pass), the rest on the host
+    const size_t n = (size_t)ctx->cloud.n;
+    int r = ensureScratch(ctx, n * 4);
+    if (r) return r;
+    int32_t* dC = (int32_t*)ctx->scratch.get();
+    CPF_HIP(ctx, cpf::launch_pack_by_gid(ctx->stream, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell,
+                                         ctx->cloud.cur.gid, nullptr, nullptr, dC, nullptr, ctx->cloud.n));
+    std::vector<int32_t> cell(n);
+    std::vector<uint32_t> birth(n);
+    CPF_HIP(ctx, hipMemcpyAsync(cell.data(), dC, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipMemcpyAsync(birth.data(), ctx->age.birth, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint32_t now = ctx->stepCounter;
+    for (size_t i = 0; i < n; ++i) age[i] = cell[i] >= 0 ? (int64_t)(uint32_t)(now - birth[i]) : -1;
     return CPF_OK;
 }
 

@@ -290,6 +290,16 @@ size_t respawn_scratch_bytes(int64_t n);
 hipError_t respawn_box(hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid, int64_t n,
                        const double lower[3], const double upper[3], int64_t maxCount, uint32_t seed, uint32_t epoch,
                        const MeshView& m, const GridView& g, void* scratch, size_t scratchBytes, unsigned long long* counters);
+// tracer age (cpf_age.hip).  birth[id] (n entries, id = gid[slot]; gid null: the slot) is the cycle count at which particle id last
+// became live, an age is (uint32_t)(now - birth).  age_absorb: sink_apply, and hist[min(age / binCycles, nBins - 1)] += 1 for every
+// particle it absorbs.  age_stamp: birth[id] = now for every slot with cell < 0.  age_field: for every i with 0 <= cell[i] <
+// nDerived, field[2 * parent] += age and field[2 * parent + 1] += 1 (parentOf null: the ids are parent ids already)
+hipError_t age_absorb(hipStream_t st, int32_t* cell, const int64_t* gid, const uint32_t* birth, int64_t n, const uint32_t* mask,
+                      int64_t nDerived, unsigned long long* absorbed, uint32_t now, int32_t binCycles, int32_t nBins,
+                      unsigned long long* hist);
+hipError_t age_stamp(hipStream_t st, const int32_t* cell, const int64_t* gid, uint32_t* birth, int64_t n, uint32_t now);
+hipError_t age_field(hipStream_t st, const int32_t* cell, const int64_t* gid, const uint32_t* birth, int64_t n,
+                     const int32_t* parentOf, int64_t nDerived, uint32_t now, unsigned long long* field);
 hipError_t unpack_arrivals(hipStream_t st, double* x, double* y, double* z, int32_t* cell, int64_t* gid,
                            int64_t nStay, const double* recvbuf, int64_t nRecv);
 // output of a sharded cloud (cpf_shard_gather): records of kOutputDoubles doubles = x, y, z, cell, gid, vx, vy, vz

@@ -449,6 +449,52 @@ int cpf_respawn_positions_host(uint32_t seed, const int64_t* gid, int64_t n, uin
                                const double upper[3], double* xyz);
 
 /* ---------------------------------------------------------------------------------------------
+ * tracer age: the residence-time distribution at the sink and the local mean age, for a recycled cloud
+ * NO REFERENCE COUNTERPART for any entry of this group.  The state is one 32-bit stamp per PARTICLE ID (the order of
+ * cpf_get_particles), birth[id] = the context's cycle counter when that particle last became live.  The cycle counter is the one
+ * that keys the Brownian stream: it goes up by nCycles with every cpf_step and not with the frame-0 call (dt = 0, D = 0).
+ * age = (uint32_t)(now - birth), in cycles, modulo 2^32; every sum is an integer, so the results are the same bits whatever the
+ * order of the cloud.  Seconds exist only in the caller (cycles * dt).  A table by id is moved by neither sort, and no step kernel
+ * knows of it.
+ * Tracking covers the CONTEXT-OWNED cloud only: cpf_shard_*, the _dev entries (cpf_sink_apply_dev, cpf_respawn_box_dev) and the
+ * replacement fragments neither read nor write a stamp.  While it is on,
+ *   cpf_sink_apply   marks exactly the particles it marks without it, counts them the same, and adds each absorbed particle's age to
+ *                    bin min(age / binCycles, nBins - 1) of the residence-time histogram;
+ *   cpf_respawn_box  places exactly the particles it places without it (positions, cells, counters, epoch), and every particle it
+ *                    makes live has birth = now.  It stamps every CANDIDATE (slot with cell < 0) before it chooses: one that the
+ *                    call leaves dead -- beyond maxCount, or drawn outside the mesh -- has no age, and is stamped again by the
+ *                    call that places it.
+ * A particle that becomes live by another road (cpf_locate_initial finding a frozen one inside) keeps the stamp it has.
+ * While it is off both calls launch exactly what they launch without this group.
+ * The stamps belong to a cloud and the field to a mesh: cpf_alloc_particles, cpf_seed_box, cpf_set_particles and cpf_set_mesh* turn
+ * tracking off.  Every entry but cpf_age_enable and cpf_age_disable returns CPF_ERR_STATE while it is off.
+ * ------------------------------------------------------------------------------------------- */
+/* NO REFERENCE COUNTERPART.  Turns tracking on, or starts it anew: birth[n] = now for every particle, a zeroed histogram of nBins
+ * 64-bit counters, a zeroed age field (age sum and count per cell of the mesh as given) and a sample count of 0.  CPF_ERR_STATE
+ * without a mesh or without located particles; CPF_ERR_ARG unless binCycles >= 1 and 1 <= nBins <= 4096. */
+int cpf_age_enable(cpf_context* ctx, int32_t binCycles, int32_t nBins);
+/* NO REFERENCE COUNTERPART.  Turns tracking off and frees its tables (no error when it is off already). */
+int cpf_age_disable(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  One sample of the age field: every live particle (cell >= 0) adds its age to the sum of its PARENT cell
+ * and 1 to that cell's count; dead slots are skipped; the sample count goes up by one.  Asynchronous on the context's stream. */
+int cpf_age_sample(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  Zeroes the histogram, the field and the sample count (asynchronous); the stamps stay. */
+int cpf_age_reset(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  Waits for the context's stream; bins[nBins] = absorptions since the last reset with age / binCycles ==
+ * b, the last bin taking every age >= (nBins - 1) * binCycles.  CPF_ERR_ARG unless nBins is cpf_age_enable's. */
+int cpf_get_age_histogram(cpf_context* ctx, uint64_t* bins, int32_t nBins);
+/* NO REFERENCE COUNTERPART.  Waits for the context's stream; ageSum[nCells], count[nCells] per PARENT cell and *nSamples since the
+ * last reset, each nullable.  Mean age of cell c in cycles = ageSum[c] / count[c]; count is what cpf_occupancy_sample would have
+ * added at the same points. */
+int cpf_get_age_field(cpf_context* ctx, uint64_t* ageSum, uint64_t* count, int64_t* nSamples);
+/* NO REFERENCE COUNTERPART.  Waits for the context's stream; age[n] in particle-id order, -1 for a dead slot (cell < 0). */
+int cpf_get_ages(cpf_context* ctx, int64_t* age);
+/* NO REFERENCE COUNTERPART.  The stamps, host arrays of n entries in particle-id order, for checkpoint and restart (a restart also
+ * needs the same cycle count: stamps are relative to the context's counter).  Both wait for the context's stream. */
+int cpf_age_get_births(cpf_context* ctx, uint32_t* birth);
+int cpf_age_set_births(cpf_context* ctx, const uint32_t* birth);
+
+/* ---------------------------------------------------------------------------------------------
  * device-array level (framework hosts that own the particle arrays, multi-GPU sharding)
  * SoA fp64 positions x,y,z [n]; cell [n] int32; gid [n] int64 global particle id (nullable:
  * gid = index); vel [n][3] (nullable unless CPF_STEP_STORE_VEL).

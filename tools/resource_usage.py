@@ -29,7 +29,7 @@ def hipcc_cmd(src, root=ROOT):
             ["-I" + os.path.join(root, "include"), "-I" + cs, os.path.join(cs, src), "-Rpass-analysis=kernel-resource-usage"])
 
 
-def parse(remarks):
+def parse(remarks, listed=LISTED):
     """Rows (name, VGPRs, AGPRs, SGPRs, scratch, waves, SGPR spills, VGPR spills, LDS) from the compiler's remarks (stderr)."""
     rows = []
     txt = re.sub(r" \[-Rpass-analysis=kernel-resource-usage\]", "", remarks)
@@ -38,7 +38,7 @@ def parse(remarks):
         if not m:
             continue
         name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip().split("(")[0]
-        if not any(k in name for k in LISTED):
+        if not any(k in name for k in listed):
             continue
         g = lambda k: (re.search(k + r":\s*(\S+)", b) or [None, "?"])[1]   # noqa: E731
         rows.append((name, g("VGPRs"), g("AGPRs"), g("TotalSGPRs"), g(r"ScratchSize \[bytes/lane\]"),
@@ -52,6 +52,13 @@ def collect():
         r = subprocess.run(hipcc_cmd(src) + ["-c", "-o", "/dev/null"], capture_output=True, text=True)
         rows += parse(r.stderr)
     return rows
+
+
+def collect_age():
+    """The same rows for the tracer-age kernels (cpf_age.hip: age_absorb_kernel, age_stamp_kernel, age_field_kernel); collect()
+    does not list them.  The absorb kernel's LDS is its static part: its histogram (4 bytes a bin, 16 KB at most) is dynamic."""
+    r = subprocess.run(hipcc_cmd("cpf_age.hip") + ["-c", "-o", "/dev/null"], capture_output=True, text=True)
+    return parse(r.stderr, ("age_",))
 
 
 def kernel_bodies(asm):
