@@ -54,4 +54,39 @@ CPF_HD inline void face_accept(double den, double fd, int bs, int token, int s, 
     }
 }
 
+// THE CHAIN FORM (GROUPS == false only): what the hand-written face block of the flat walk's body without z executes
+// (cpf_walk.h, face_accept_flat_asm), stated in plain C++ so that the host can compare it with face_accept<false> above
+// (tests/test_flat_face_predicate_host.py).  Three conditions narrow the set of lanes one after the other: c4, c3, and in place
+// of c1 and c2 ONE comparison of the two bit patterns as unsigned 64-bit integers,
+//   c12  bits(fd) <= bits(den).
+// The order of IEEE doubles of one sign is the order of their magnitudes' bit patterns, and a set sign bit is the integer's top
+// bit.  So, for fd not a NaN (c3 has seen to that):
+//   * equal sign bits: c12 <=> |fd| <= |den| = c1, for finite and infinite den alike (a NaN den has the largest patterns of its
+//     sign: c12 holds, c1 does not -- and the quotient is NaN);
+//   * fd negative, den positive: the top bit decides, c12 fails.  Nothing is lost: the quotient is negative, zero or NaN;
+//   * fd positive (or +0), den negative (or -0): c12 HOLDS whatever the magnitudes -- the one case that c1 and c2 prune and c12
+//     lets through to the division.  Its quotient is negative, a zero or NaN as well.
+// What is accepted is the same: a lane is accepted only with dT = fl(fd / den) > tol > 0, and an IEEE quotient is positive only
+// if neither operand is a NaN or a zero and the sign bits are EQUAL (the sign of a quotient is the exclusive-or of its operands'
+// signs, exactly, whatever it rounds to).  So dT > tol implies equal signs on non-zero operands -- where c12 is c1, and where c2
+// holds (both negative: den < 0; both positive: fd > 0) -- and every lane on which c12 and (c1 and c2) differ has unequal signs, a
+// zero or a NaN among its operands and fails dT > tol either way.  dTmin, next and best change for the same lanes, to the same
+// values.  (Which lanes reach the division for nothing: a particle on or outside a plane, 0 <= fd < tol, moving further out --
+// the face it came in through, which c4 has skipped, or a start a rounding error outside its cell.)
+CPF_HD inline bool bits_le(double a, double b) {
+    unsigned long long ia, ib;
+    __builtin_memcpy(&ia, &a, 8);
+    __builtin_memcpy(&ib, &b, 8);
+    return ia <= ib;
+}
+CPF_HD inline void face_accept_chain(double den, double fd, int bs, int token, int s, double& dTmin, int& next, int& best) {
+    if (!(bs != token)) return;                        // c4
+    if (!(fd < kTol)) return;                          // c3
+    if (!bits_le(fd, den)) return;                     // c12
+    const double dT = fd / den;
+    if (!(dT > kTol)) return;
+    if (!(dT < dTmin)) return;
+    dTmin = dT; next = bs; best = s;
+}
+
 }  // namespace cpf

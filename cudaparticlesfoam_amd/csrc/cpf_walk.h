@@ -305,15 +305,82 @@ __device__ __forceinline__ void trace_lds6_record(const D3& P0, const D3& Pd, co
 // side faces are all that is tested, and their dropped terms are 0 * finite: den = fma(0, Pd.z, t) = t and fd = fma(-0, P0.z, u)
 // = u up to the sign of a zero, which no comparison sees (E.z and P0.z are finite: a lane with a NaN or infinite end point is
 // never `clear`).  The exit point keeps its z: S = P0 + dT * Pd with the real Pd.z.  Same bits as trace_lds6(..., zNever = true).
-template <bool ZERO_SKIP, bool KEEP_Z = false>
+//
+// THE FACE BLOCK IN HAND-WRITTEN ISA (FACE_ASM; the body without z only: step_kernel_stream_flat, CPF_FLAT_FACE_ASM).  The C++ face
+// test computes every predicate into a scalar register pair and combines them on the scalar ALU -- a vote of three compares, a
+// scalar compare and a branch, then the exact predicate's four compares, four scalar operations, a saveexec and a branch, then
+// two more compares, an AND and a saveexec: 14 scalar-issue instructions per face with a candidate lane, in a kernel whose
+// scalar pipe is the busier one (docs/experiments.md, round 9).  v_cmpx narrows EXEC itself, so a chain of them is an AND that
+// costs the scalar pipe nothing: save EXEC, c4, c3, c12 (cpf_accept.h, face_accept_chain: c1 and c2 as one comparison of the bit
+// patterns -- the same accepted set, argued there), ONE branch over the division, the division as hipcc expands fd / den (correctly rounded: the same bits), dT > tol,
+// dT < dTmin, three moves, restore EXEC -- three scalar-issue instructions per face, candidate or not, and seven vector
+// instructions for a face without a candidate lane (as many as the C++ vote), 24 for one with (28).  den and fd stay in C++: the
+// compiler interleaves the two chains of a pair.
+// Wait states, by hand (the compiler's hazard recogniser does not look inside the string):
+//   * v_div_scale writes VCC, v_div_fmas reads it: four states wanted, six instructions lie between;
+//   * v_rcp_f64 (transcendental unit) -> its first reader: one independent instruction between, as hipcc schedules it;
+//   * a VALU write of EXEC (v_cmpx) -> a lane-crossing read (DPP, v_readlane, v_readfirstlane, v_permlane): five states.  None
+//     is in the block; behind the last v_cmpx of either path lie a branch and a scalar move at the least before compiler code
+//     resumes, and tests/test_build_resources_flat_face.py holds that no such instruction follows a block within five.
+//   * v_cmpx -> s_cbranch_execz and v_cmpx -> VALU under the new mask need none (hipcc emits both back to back).
+template <int SLOT>
+__device__ __forceinline__ void face_accept_flat_asm(double den, double fd, int bs, int token, double& dTmin, int& next, int& best) {
+    double q0, q1, q2, q3;                 // the division's temporaries; dT ends up in q0
+    unsigned long long keep;
+    const double tol = kTol;
+    asm volatile(
+        "s_mov_b64 %[keep], exec\n\t"
+        "v_cmpx_ne_u32_e32 vcc, %[bs], %[tok]\n\t"               // c4
+        "v_cmpx_gt_f64_e32 vcc, %[tol], %[fd]\n\t"               // c3
+        "v_cmpx_le_u64_e32 vcc, %[fd], %[den]\n\t"               // c12
+        "s_cbranch_execz .Lcpf_face_%=\n\t"
+        "v_div_scale_f64 %[q0], vcc, %[den], %[den], %[fd]\n\t"
+        "v_rcp_f64_e32 %[q1], %[q0]\n\t"
+        "v_div_scale_f64 %[q2], vcc, %[fd], %[den], %[fd]\n\t"
+        "v_fma_f64 %[q3], -%[q0], %[q1], 1.0\n\t"
+        "v_fmac_f64_e32 %[q1], %[q1], %[q3]\n\t"
+        "v_fma_f64 %[q3], -%[q0], %[q1], 1.0\n\t"
+        "v_fmac_f64_e32 %[q1], %[q1], %[q3]\n\t"
+        "v_mul_f64 %[q3], %[q2], %[q1]\n\t"
+        "v_fma_f64 %[q0], -%[q0], %[q3], %[q2]\n\t"
+        "v_div_fmas_f64 %[q0], %[q0], %[q1], %[q3]\n\t"
+        "v_div_fixup_f64 %[q0], %[q0], %[den], %[fd]\n\t"
+        "v_cmpx_lt_f64_e32 vcc, %[tol], %[q0]\n\t"               // dT > tol
+        "v_cmpx_lt_f64_e32 vcc, %[q0], %[dtm]\n\t"               // dT < dTmin
+        "v_mov_b64_e32 %[dtm], %[q0]\n\t"
+        "v_mov_b32_e32 %[nx], %[bs]\n\t"
+        "v_mov_b32_e32 %[bst], %[slot]\n"
+        ".Lcpf_face_%=:\n\t"
+        "s_mov_b64 exec, %[keep]"
+        : [dtm] "+v"(dTmin), [nx] "+v"(next), [bst] "+v"(best), [q0] "=&v"(q0), [q1] "=&v"(q1), [q2] "=&v"(q2), [q3] "=&v"(q3),
+          [keep] "=&s"(keep)
+        : [den] "v"(den), [fd] "v"(fd), [bs] "v"(bs), [tok] "v"(token), [tol] "s"(tol), [slot] "n"(SLOT)
+        : "vcc");
+}
+// ONE PAIR, FACE_ASM: record_pair<.., FLAT> with the face block above -- same planes, same den and fd, same order.
+template <int SLOT>
+__device__ __forceinline__ void record_pair_flat_asm(double4& pa, double4& pb, const int2 b, const D3& P0, const D3& Pd, int token, double& dTmin, int& next, int& best) {
+    CPF_PIN_W(pa, pb)
+    const double denA = fma(pa.y, Pd.y, pa.x * Pd.x), fdA = fma(-pa.y, P0.y, fma(-pa.x, P0.x, pa.w));
+    const double denB = fma(pb.y, Pd.y, pb.x * Pd.x), fdB = fma(-pb.y, P0.y, fma(-pb.x, P0.x, pb.w));
+    face_accept_flat_asm<SLOT>(denA, fdA, b.x, token, dTmin, next, best);
+    face_accept_flat_asm<SLOT + 1>(denB, fdB, b.y, token, dTmin, next, best);
+}
+template <bool ZERO_SKIP, bool KEEP_Z = false, bool FACE_ASM = false>
 __device__ __forceinline__ int trace_lds4_flat(D3& S, const D3& E, int cur, const double4* rec, int token, int& outSlot) {
+    static_assert(!(FACE_ASM && (KEEP_Z || ZERO_SKIP)), "the hand-written face block is the body without z's, without the zero-denominator vote");
     const D3 P0 = S;
     const D3 Pd = {E.x - P0.x, E.y - P0.y, KEEP_Z ? E.z - P0.z : 0.0};
     int next = cur, best = -1;
     double dTmin = 2.0;
     const int2* nb = reinterpret_cast<const int2*>(rec + 7);
+    if constexpr (FACE_ASM) {
+        { double4 p0 = rec[0], p1 = rec[1]; record_pair_flat_asm<0>(p0, p1, nb[0], P0, Pd, token, dTmin, next, best); }
+        { double4 p2 = rec[2], p3 = rec[3]; record_pair_flat_asm<2>(p2, p3, nb[1], P0, Pd, token, dTmin, next, best); }
+    } else {
     { double4 p0 = rec[0], p1 = rec[1]; record_pair<ZERO_SKIP, false, true>(p0, p1, nb[0], 0, P0, Pd, token, dTmin, next, best); }
     { double4 p2 = rec[2], p3 = rec[3]; record_pair<ZERO_SKIP, false, true>(p2, p3, nb[1], 2, P0, Pd, token, dTmin, next, best); }
+    }
     if (best >= 0) {
         if (KEEP_Z) S = axpy(dTmin, Pd, P0);
         else { S.x = fma(dTmin, Pd.x, P0.x); S.y = fma(dTmin, Pd.y, P0.y); }

@@ -1,0 +1,313 @@
+"""GPU: the hand-written face block of the flat walk's body without z (csrc/cpf_walk.h, face_accept_flat_asm; CPF_FLAT_FACE_ASM),
+BIT FOR BIT in x, y and the cell against two statements of the same cycle:
+
+  1. the CPU statement, oracle/cellwalk.c (CellWalk.step_given(xi = None) through tests/browniancycle.py, run_cpu);
+  2. the same library with option "flat_z" 0: the three-coordinate body, whose face test is the C++ one.
+
+What runs: cpf_step on the context's own cloud, never re-sorted ("sort_interval" 0).  The first launch of a cloud set anew streams z
+and is not the kernel under test, so every run begins with one cycle of dt = 0 -- nobody moves, z settles -- and the launches
+behind it, of 1, 3 and 20 cycles, report step_kernel_stream_flat<true, false, false, 8 | 9> (asserted after each launch); a launch
+of zero cycles follows and must leave every particle as it was.
+
+WHICH LOOKUP RUNS is the planner's choice by particles per cell (csrc/cpf_stream.hip, stream_lookup_mode): "stream_lookup" can ask
+for 0 ... 6 only, 8 and 9 are the flat forms of 0 and 1 that the planner picks for itself, and below 8 particles per cell a cloud
+is "sparse" and does not take the flat walk at all.  So the sizes pick the lookup: on the 30-cell meshes 2 000 particles run 9,
+4 096 + 13 and 20 000 run 8; 37 and 64 particles need a mesh of four cells to take the flat walk (9); pitzDaily's 12 225 cells
+take it from 97 800 particles (9).  Every expected name is asserted.  Clouds ordered by cell walk records in LDS; clouds as drawn
+have more distinct cells per tile than record slots and walk gathered records (the gather visit).
+
+Meshes: box_mesh(6, 5, 1) and box_mesh(2, 2, 1) -- unit cells, every coordinate, velocity and the time step dyadic, so that the
+engineered lanes below are exact --, a sheared one-layer block without an axis-aligned side face, and pitzDaily.
+
+The engineered cloud (box_mesh(6, 5, 1), 4 096 + 13 particles, whole tiles built by hand):
+  tile 0   no lane is a candidate for any face: all four blocks of every visit take their execz branch;
+  tile 1   the same but for ONE lane, which crosses a face;
+  tile 2   end points exactly on a face (dT == 1), starts 2^-50 inside and 2^-50 outside the exit face, starts outside their cell
+           moving back in slowly enough to be accepted (fd > 0, fd / den > tol), segments through a cell corner (two faces with
+           equal dT: the lower slot wins), motion exactly parallel to a face pair (den == +-0, both signs of zero);
+  tile 3   NaN, +inf and -inf in x or in y, frozen and lost lanes, among live ones;
+  tile 4   displacements of five domain widths: five wall bounces, then lost; and of three: they survive;
+  every lane that crosses a face runs a second visit that must skip its entry face.
+Lanes with a NaN or an infinity: the CPU and the GPU agree on the cell and on which coordinates are NaN (the CPU's default NaN and
+the GPU's differ in the sign bit); against the "flat_z" 0 run they too are compared bit for bit."""
+import functools
+import types
+
+import numpy as np
+import pytest
+
+import browniancycle as B
+from cudaparticlesfoam_amd import _lib as L
+
+pytestmark = pytest.mark.gpu
+
+LAUNCHES = (1, 3, 20)
+CHECKPOINTS = (1, 4, 24)
+FLAT = "cpf::step_kernel_stream_flat<true, false, false, %d>"
+STREAM = "cpf::step_kernel_stream<false, true, false, false, %d>"
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def _case(name, mesh, U, dt):
+    U = np.ascontiguousarray(U)
+    assert not U[:, 2].any()
+    U.setflags(write=False)
+    c = types.SimpleNamespace(name=name, mesh=mesh, U=U, U2=U, dt=float(dt), sigma=0.0)
+    c.tables = B.cellwalk().build(mesh)
+    c.lo, c.hi = mesh.bounds()
+    return c
+
+
+def _random_field(mesh, seed):
+    _, vols = mesh.cell_centres_volumes()
+    U = np.random.default_rng(seed).normal(size=(mesh.n_cells, 3))
+    U[:, 2] = 0.0
+    return U, 0.4 * float(np.cbrt(vols.min())) / float(np.abs(U).max())
+
+
+def _dyadic_field(mesh):
+    """per cell, by its (i, j): (+-2, +-1) in general, and the cells the engineered lanes live in; dt = 1 / 8"""
+    centres, _ = mesh.cell_centres_volumes()
+    ij = np.floor(centres[:, :2]).astype(int)
+    U = np.zeros((mesh.n_cells, 3))
+    U[:, 0] = 2.0 * (1 - 2 * (ij[:, 0] % 2))
+    U[:, 1] = 1.0 * (1 - 2 * (ij[:, 1] % 2))
+    special = {(3, 1): (4.0, 4.0), (1, 3): (2.0, 0.0), (2, 3): (-0.0, -2.0), (3, 3): (-2.0 ** -7, 0.0), (5, 4): (240.0, 200.0),
+               (0, 0): (-144.0, 1.0), (2, 2): (0.25, 0.125)}
+    for c in range(mesh.n_cells):
+        if tuple(ij[c]) in special:
+            U[c, :2] = special[tuple(ij[c])]
+    return U
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    from cudaparticlesfoam_amd.cases import box_mesh
+    from cudaparticlesfoam_amd.cases.blockmesh import block_mesh
+    if name == "unit box":
+        mesh = box_mesh(6, 5, 1)
+        return _case(name, mesh, _dyadic_field(mesh), 0.125)
+    if name == "four cells":
+        mesh = box_mesh(2, 2, 1)
+        U = np.array([[2.0, 1.0, 0.0], [-3.0, 0.5, 0.0], [0.5, -2.0, 0.0], [-1.0, -1.0, 0.0]])
+        return _case(name, mesh, U[:mesh.n_cells], 0.125)
+    if name == "sheared":
+        base = [(0.0, 0.0), (6.0, 1.0), (7.5, 6.0), (1.5, 5.0)]
+        v = np.array([(x, y, 0.0) for x, y in base] + [(x, y, 1.0) for x, y in base])
+        mesh = block_mesh(v, [dict(hex=range(8), n=(6, 5, 1), simple=(1, 1, 1))])
+        U, dt = _random_field(mesh, 311)
+        return _case(name, mesh, U, dt)
+    assert name == "pitzDaily"
+    from cudaparticlesfoam_amd.cases import pitzdaily as pz
+    mesh = pz.pitzdaily_mesh()
+    U = np.array(pz.analytic_step_u(mesh))
+    U[:, 2] = 0.0
+    return _case(name, mesh, U, 1e-4)
+
+
+def _locate(c, p):
+    cw = B.cellwalk()
+    return cw.locate_initial(p[:, 0].copy(), p[:, 1].copy(), p[:, 2].copy(), c.tables, nthreads=cw.max_threads).astype(np.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def cloud(name, n, sort):
+    """uniform points inside the mesh at z = 1/2 with the CPU statement's cells; sort: ordered by cell; lanes 5, 64 and 130 begin
+    lost / frozen"""
+    c = case(name)
+    rng = np.random.default_rng(17 + n)
+    xyz = np.empty((0, 3)); cell = np.empty(0, np.int32)
+    while xyz.shape[0] < n:
+        p = rng.uniform(c.lo, c.hi, size=(2 * n + 64, 3))
+        p[:, 2] = 0.5 * (c.lo[2] + c.hi[2])
+        k = _locate(c, p)
+        xyz = np.concatenate([xyz, p[k >= 0]]); cell = np.concatenate([cell, k[k >= 0]])
+    xyz, cell = xyz[:n], cell[:n].copy()
+    if sort:
+        o = np.argsort(cell, kind="stable")
+        xyz, cell = xyz[o], cell[o]
+    for i, state in B.START_DEAD.items():
+        if i < n:
+            cell[i] = state
+    xyz, cell = np.ascontiguousarray(xyz), np.ascontiguousarray(cell)
+    xyz.setflags(write=False); cell.setflags(write=False)
+    return xyz, cell
+
+
+@functools.lru_cache(maxsize=None)
+def engineered_cloud():
+    """(xyz, cell0, special [n] bool): five hand-built tiles on the unit box, then random particles ordered by cell up to 4 096 + 13"""
+    c = case("unit box")
+    e = 2.0 ** -50
+    lanes = []                                           # (cell's (i, j), x, y, cell state or None)
+
+    def add(ij, x, y, state=None):
+        lanes.append((ij, x, y, state))
+    # tile 0: cell (2, 2), U = (1/4, 1/8): displacement (1/32, 1/64), starts well inside -- nobody is a candidate for any face
+    for k in range(64):
+        add((2, 2), 2.25 + (k % 8) / 16.0, 2.25 + (k // 8) / 16.0)
+    # tile 1: the same, and lane 37 leaves through the x face
+    for k in range(64):
+        add((2, 2), 2.25 + (k % 8) / 16.0, 2.25 + (k // 8) / 16.0)
+    lanes[64 + 37] = ((2, 2), 3.0 - 1.0 / 64, 2.5, None)
+    # tile 2
+    t2 = []
+    for y in (1.25, 1.5, 1.625):                         # cell (1, 1), U = (-2, -1): displacement (-1/4, -1/8)
+        t2 += [((1, 1), 1.25, y), ((1, 1), 1.5, 1.0 + 0.125 + (y - 1.25)),      # ends on x = 1 / on y = 1: dT == 1
+               ((1, 1), 1.0 + e, y), ((1, 1), 1.0 - e, y),                      # 2^-50 inside / outside the exit face x = 1
+               ((1, 1), 1.5, 1.0 + e), ((1, 1), 1.5, 1.0 - e)]
+    for x in (3.25, 3.5, 3.75):                          # cell (3, 3), U = (-2^-7, 0): displacement -2^-10 in x; outside across x = 4 and x = 3
+        t2 += [((3, 3), 4.0 + e, x), ((3, 3), 4.0 + 2 * e, x - 0.125), ((3, 3), 3.0 - e, x), ((3, 3), 3.0 + 2.0 ** -11, x)]
+    for d in (0.25, 0.125, 0.375):                       # cell (3, 1), U = (4, 4): through the corner (4, 2), dT == d / (1/2) on both faces
+        t2 += [((3, 1), 4.0 - d, 2.0 - d), ((3, 1), 4.0 - d, 2.0 - d - 2.0 ** -30), ((3, 1), 4.0 - d - 2.0 ** -30, 2.0 - d)]
+    for y in (3.0 + e, 3.5, 4.0 - e, 3.0, 4.0):          # cell (1, 3), U = (2, +0): parallel to its y faces, den == +-0
+        t2 += [((1, 3), 1.5, y), ((1, 3), 1.875, y)]
+    for x in (2.0 + e, 2.5, 3.0 - e, 2.0, 3.0):          # cell (2, 3), U = (-0, -2): parallel to its x faces
+        t2 += [((2, 3), x, 3.5), ((2, 3), x, 3.125)]
+    assert len(t2) <= 64
+    while len(t2) < 64:
+        t2.append(((1, 1), 1.5, 1.5))
+    for ij, x, y in t2:
+        add(ij, x, y)
+    # tile 3: NaN and infinities in x or y, frozen and lost lanes, among live ones in cell (4, 2), U = (2, 1)
+    bad = [(np.nan, 2.5), (4.5, np.nan), (np.inf, 2.5), (4.5, np.inf), (-np.inf, 2.5), (4.5, -np.inf), (np.nan, np.nan), (np.inf, -np.inf)]
+    for k in range(64):
+        if k % 4 == 1:
+            x, y = bad[(k // 4) % 8]
+            add((4, 2), x, y)
+        elif k % 8 == 2:
+            add((4, 2), 4.5, 2.5, B.CELL_FROZEN if k % 16 == 2 else B.CELL_LOST)
+        else:
+            add((4, 2), 4.0625 + (k % 8) / 8.0, 2.0625 + (k // 8) / 8.0)
+    # tile 4: cell (5, 4), U = (240, 200): displacement (30, 25), five domain widths -- five bounces, lost; cell (0, 0), U = (-144, 1):
+    # displacement (-18, 1/8), three widths -- three bounces
+    for k in range(64):
+        if k % 2:
+            add((5, 4), 5.125 + (k // 2) / 64.0, 4.25 + (k // 2) / 128.0)
+        else:
+            add((0, 0), 0.125 + (k // 2) / 64.0, 0.25 + (k // 2) / 128.0)
+    assert len(lanes) == 320
+    centres = np.array([(ij[0] + 0.5, ij[1] + 0.5, 0.5) for ij, _, _, _ in lanes])
+    cell = _locate(c, centres)
+    assert (cell >= 0).all()
+    for k, (_, _, _, state) in enumerate(lanes):
+        if state is not None:
+            cell[k] = state
+    xyz = np.array([(x, y, 0.5) for _, x, y, _ in lanes])
+    rx, rc = cloud("unit box", 4096 + 13 - 320, True)
+    xyz = np.ascontiguousarray(np.concatenate([xyz, rx])); cell = np.ascontiguousarray(np.concatenate([cell, rc]))
+    special = np.arange(xyz.shape[0]) < 320
+    for a in (xyz, cell, special):
+        a.setflags(write=False)
+    return xyz, cell, special
+
+
+# one context per mesh, closed behind the file's last test
+_state = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _module_state():
+    yield
+    for ctx in _state.values():
+        ctx.close()
+    _state.clear()
+
+
+def _ctx(name, make):
+    if name not in _state:
+        c, ctx = case(name), make()
+        ctx.set_mesh(c.mesh); ctx.set_velocity(c.U); ctx.synchronize()
+        _state[name] = ctx
+    return _state[name]
+
+
+def gpu_run(ctx, c, xyz, cell0, lookup, flat_z):
+    """{cycles: (xyz, cell)} behind launches of 1, 3 and 20 cycles on a cloud whose z one cycle of dt = 0 has settled"""
+    out = {}
+    for k, v in (("stats", 0), ("sort_interval", 0), ("flat_z", flat_z)):
+        ctx.set_option(k, v)
+    try:
+        ctx.set_particles(xyz, cell0)
+        ctx.step(0.0, 0.0, 1, L.STEP_FUSE_CYCLES)
+        assert ctx.step_kernel_name(0.0, L.STEP_FUSE_CYCLES) == (FLAT if flat_z else STREAM) % lookup
+        done = 0
+        for k in LAUNCHES:
+            ctx.step(c.dt, 0.0, k, L.STEP_FUSE_CYCLES)
+            name = ctx.step_kernel_name(0.0, L.STEP_FUSE_CYCLES)
+            assert name == (FLAT if flat_z else STREAM) % lookup, name
+            done += k
+            xyzw, cell = ctx.get_particles()
+            out[done] = (xyzw[:, :3].copy(), cell.copy())
+        ctx.step(c.dt, 0.0, 0, L.STEP_FUSE_CYCLES)                   # the zero-cycle launch
+        xyzw, cell = ctx.get_particles()
+        assert np.array_equal(_bits(xyzw[:, :3]), _bits(out[done][0])) and np.array_equal(cell, out[done][1]), "a launch of zero cycles moved somebody"
+    finally:
+        for k, v in (("stats", 1), ("sort_interval", 50), ("flat_z", 1)):
+            ctx.set_option(k, v)
+    return out
+
+
+def check(name, xyz, cell0, lookup, make, what):
+    c, ctx = case(name), _ctx(name, make)
+    ref, diag = B.run_cpu(c, xyz, cell0, None, reflect=1, checkpoints=CHECKPOINTS, U=c.U)
+    got = gpu_run(ctx, c, xyz, cell0, lookup, 1)
+    three = gpu_run(ctx, c, xyz, cell0, lookup, 0)
+    finite = np.isfinite(xyz[:, :2]).all(1)
+    for k in CHECKPOINTS:
+        p, cell = got[k]
+        p3, cell3 = three[k]
+        bad = np.nonzero(cell != cell3)[0]
+        assert bad.size == 0, (what, k, "cells differ from the three-coordinate body", bad[:5], cell[bad[:5]], cell3[bad[:5]])
+        bad = np.nonzero((_bits(p[:, :2]) != _bits(p3[:, :2])).any(1))[0]
+        assert bad.size == 0, (what, k, "x, y differ from the three-coordinate body", bad[:5], p[bad[:5]], p3[bad[:5]])
+        s = ref[k]
+        bad = np.nonzero(cell != s.cell)[0]
+        assert bad.size == 0, (what, k, "cells differ from the CPU", bad.size, bad[:5], cell[bad[:5]], s.cell[bad[:5]])
+        bad = np.nonzero((_bits(p[finite, :2]) != _bits(s.xyz[finite, :2])).any(1))[0]
+        assert bad.size == 0, (what, k, "x, y differ from the CPU", bad.size, bad[:5], p[finite][bad[:5]], s.xyz[finite][bad[:5]])
+        assert np.array_equal(np.isnan(p[~finite, :2]), np.isnan(s.xyz[~finite, :2])), (what, k, "NaN lanes")
+    return ref, diag, got
+
+
+RANDOM = [("four cells", 37, 9), ("four cells", 64, 9), ("unit box", 2000, 9), ("unit box", 20000, 8), ("sheared", 2000, 9),
+          ("sheared", 4096 + 13, 8), ("sheared", 20000, 8), ("pitzDaily", 100000, 9)]
+
+
+@pytest.mark.parametrize("sort", [True, False], ids=["by-cell", "as-drawn"])
+@pytest.mark.parametrize("name,n,lookup", RANDOM, ids=["%s-n%d-lookup%d" % r for r in RANDOM])
+def test_random_clouds(name, n, lookup, sort, gpu_ctx_factory, oracle_libs):
+    xyz, cell0 = cloud(name, n, sort)
+    _, diag, _ = check(name, xyz, cell0, lookup, gpu_ctx_factory, "%s n=%d %s" % (name, n, "by cell" if sort else "as drawn"))
+    hp = B.hard_paths(diag)
+    print("MEASURED %s n=%d: %s" % (name, n, hp))
+    assert hp["crossing"] >= 0.05, hp
+    if name != "pitzDaily" and n >= 2000:
+        assert hp["reflecting"] >= 0.005, hp
+
+
+def test_engineered_lanes(gpu_ctx_factory, oracle_libs):
+    xyz, cell0, special = engineered_cloud()
+    ref, diag, got = check("unit box", xyz, cell0, 8, gpu_ctx_factory, "engineered")
+    visits, walls = diag[0, :, 0], diag[0, :, 1]                # the first cycle, per lane
+    first = ref[1]
+    # tile 0: one visit each, nobody crossed; tile 1: lane 37 alone crossed
+    assert (visits[:64] == 1).all() and (walls[:64] == 0).all()
+    assert visits[64 + 37] == 2 and (np.delete(visits[64:128], 37) == 1).all()
+    # tile 2: the lanes that end exactly on a face are in the neighbour's cell, on the face
+    assert first.xyz[128, 0] == 1.0 and first.cell[128] != cell0[128]
+    assert first.xyz[129, 1] == 1.0 and first.cell[129] != cell0[129]
+    # tile 3: frozen and lost lanes kept their state and their position, non-finite lanes their cell
+    t3 = slice(192, 256)
+    dead = cell0[t3] < 0
+    assert dead.sum() == 8 and (got[24][1][t3][dead] < 0).all()
+    assert np.array_equal(_bits(got[24][0][t3][dead]), _bits(xyz[t3][dead]))
+    nonfinite = ~np.isfinite(xyz[t3, :2]).all(1)
+    assert nonfinite.sum() == 16 and np.array_equal(got[24][1][t3][nonfinite], cell0[t3][nonfinite])
+    # tile 4: the odd lanes used all five bounces and are lost, the even ones bounced three times and live
+    t4 = np.arange(256, 320)
+    assert (walls[t4[1::2]] == 5).all() and (first.cell[t4[1::2]] == B.CELL_LOST).all(), (walls[t4], first.cell[t4])
+    assert (walls[t4[0::2]] == 3).all() and (first.cell[t4[0::2]] >= 0).all(), (walls[t4], first.cell[t4])
