@@ -8,6 +8,7 @@
 // sit above nStay, so only O(leavers) particles move.  Compaction uses wave64 ballots and
 // popcount prefixes; cross-wave offsets go through LDS.
 #include "cpf_device.h"
+#include "cpf_slice.h"      // count_runs
 
 namespace cpf {
 
@@ -219,21 +220,7 @@ __global__ __launch_bounds__(kHistBlock) void cell_histogram_lds_kernel(const in
             cs[u] = (i < hi) ? cell[i] : -1;
         }
 #pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            const int c = cs[u];
-            bool todo = c >= 0;
-#pragma unroll 1
-            for (int round = 0; round < 2; ++round) {
-                const unsigned long long m = __ballot(todo);
-                if (m == 0ull) break;
-                const int leader = __ffsll((long long)m) - 1;
-                const int cl = __builtin_amdgcn_readlane(c, leader);
-                const unsigned long long same = __ballot(todo && c == cl);
-                if (lane == leader) atomicAdd(&sHist[cl], (unsigned int)__popcll(same));
-                if (c == cl) todo = false;
-            }
-            if (todo) atomicAdd(&sHist[c], 1u);
-        }
+        for (int u = 0; u < kUnroll; ++u) count_runs<2>(cs[u], 1u, lane, [&](int c, unsigned w) { atomicAdd(&sHist[c], w); });
     }
     __syncthreads();
     unsigned int* row = partial + (int64_t)blockIdx.x * nCells;
