@@ -189,6 +189,22 @@ constexpr int kKernArgStep0 = (int)offsetof(StreamKernArgs, step0), kKernArgSeed
 #ifndef CPF_FLAT_FACE_ASM
 #define CPF_FLAT_FACE_ASM 1
 #endif
+// the round's bookkeeping around the face blocks, body without z only, each item an A/B knob, 0 = the code as the compiler made it
+// (docs/experiments.md, round 13):
+// LOOKUP_ASM: the loop lookup's trip -- one per distinct cell of the busy lanes -- as a hand-written block (cpf_stream_ops.h,
+// lookup_loop_asm): 7 scalar-issue (one of them a pad) and 5 vector instructions for a record on chip, where hipcc needs 14 and 7;
+// VOTE_MASK: the visit's outcome is applied behind the busy lanes' region, so that "still busy" is built from the compares' own masks
+// -- no trip of the vote through a vector register (v_cndmask 0/1 + v_cmp) -- and ANDed with the round's busy mask;
+// WALL_J: "still on a wall after five bounces" is tested in the wall branch, where j changes, not by every lane in every round.
+#ifndef CPF_FLAT_LOOKUP_ASM
+#define CPF_FLAT_LOOKUP_ASM 1
+#endif
+#ifndef CPF_FLAT_VOTE_MASK
+#define CPF_FLAT_VOTE_MASK 1
+#endif
+#ifndef CPF_FLAT_WALL_J
+#define CPF_FLAT_WALL_J 1
+#endif
 // (with the kick the landing zone and the hit pool are larger: 7 slots keep the sixth wave, 6600 of 6826 bytes)
 #ifndef CPF_STREAM_SLOTS_BROWN
 #define CPF_STREAM_SLOTS_BROWN 10
@@ -305,6 +321,8 @@ __device__ __forceinline__ void stream_body(
     constexpr bool kFlatGather = ZSET && CPF_FLAT_ROUND_GATHER != 0, kHints = ZSET && CPF_FLAT_ROUND_HINTS != 0;
     constexpr bool kOneHook = ZSET && CPF_FLAT_ROUND_ONE_HOOK != 0;
     constexpr bool kFaceAsm = ZSET && CPF_FLAT_FACE_ASM != 0 && CPF_STREAM_FLAT_ZERO_SKIP == 0;
+    constexpr bool kLookupAsm = ZSET && CPF_FLAT_LOOKUP_ASM != 0, kVoteMask = kMaskBusy && CPF_FLAT_VOTE_MASK != 0;
+    constexpr bool kWallJ = ZSET && CPF_FLAT_WALL_J != 0;
     // (FLAT) z of every live particle is a fixed point of the flat cycle: the launch leaves z in memory alone.  Wave-uniform;
     // the landing zone is then x[64] | y[64] | cell[64], and no z is loaded or stored (the z the walk carries in registers is dead)
     // (ZSET: at compile time, and no test of it is left in the code)
@@ -680,6 +698,9 @@ __device__ __forceinline__ void stream_body(
                         }
 #endif
                     }
+                } else if (kLookupAsm) {
+                    missLanes = 0ull;
+                    lookup_loop_asm(busyMask, lk, tagv, myslot, used, missLanes);
                 } else {
                     unsigned long long todo = busyMask;
                     missLanes = 0ull;
@@ -796,6 +817,62 @@ __device__ __forceinline__ void stream_body(
                     }
                     park(E);
                     return E;
+                };
+                // ---- (the body without z, kVoteMask / kWallJ) what the visit led to, as the statement at the end of the busy lanes' region says it,
+                // in a form of its own:
+                //   * kVoteMask: it is applied BEHIND that region, by every lane of the wave, to what the visit left in nextOut, wallOut, EOut
+                //     -- a lane that is not busy made no visit, next = kSitOut, which is no outcome at all.  "Still busy" is then built from
+                //     the compares' own masks and ANDed with the round's busy mask; inside the region the vote went through a vector
+                //     register (the region's join merges a bool);
+                //   * kWallJ: j changes in the wall branch alone, so "lost" -- five bounces, or a wall that does not reflect -- is decided
+                //     there: such a lane's hop count is set to the cap, and the cap ends it like any other.  (h is dead by then: the lane
+                //     is done with the cycle and cycle_begin resets it; cell, token and j are the same.)
+                //   * "at the hop cap" needs no AND with "crossed": h grows by crossing alone and a lane at the cap is done, so a busy lane
+                //     enters the round below the cap (lanes that are not busy are masked by the round's busy mask).
+                int nextOut = kSitOut;
+                double4 wallOut;
+                D3 EOut;
+                auto outcome_flat = [&](const int next, const double4& wallPlane, D3& E) __attribute__((always_inline)) {
+                    // (in a discarded statement for every other kernel: their closure captures nothing, their code is the parent's to the instruction)
+                    if constexpr (kVoteMask || kWallJ) {
+                    const bool wall = next < 0 && next != kSitOut;
+                    const bool inside = next >= 0;
+                    if (wall) {
+                        if (!REFLECT) j = kMaxReflect;
+                        else {
+                            park_hit(S_);
+                            if (STATS) ++st.refl;
+                            const D3 nn = {wallPlane.x, wallPlane.y, wallPlane.z};
+                            const double sd = fma(wallPlane.y, E.y, wallPlane.x * E.x) - wallPlane.w;
+                            E = {fma(-2.0 * sd, nn.x, E.x), fma(-2.0 * sd, nn.y, E.y), 0.0};
+                            park(E);
+                            v = axpy(-2.0 * dot3(wallPlane, v), nn, v);
+                            h = 0;
+                            ++j;
+                        }
+                        if (kWallJ && (!REFLECT || j >= kMaxReflect)) h = kMaxHops;
+                    }
+                    if constexpr (kVoteMask) {
+                        // (every term a compare's own mask: a vote on a bool that is not itself a compare -- an OR of them -- goes
+                        // through a vector register again.  EXEC is whole here, and the round's busy mask closes the expression)
+                        const unsigned long long endsM = __builtin_amdgcn_uicmp((unsigned)next, (unsigned)cur, 32 /* eq */);
+                        const unsigned long long crossM = ballot64(inside) & ~endsM;
+                        const bool cross = __builtin_amdgcn_inverse_ballot_w64(crossM);
+                        token = cross ? cur : (wall ? next : token);
+                        cur = cross ? next : cur;
+                        add_lanes(h, crossM);
+                        unsigned long long doneM = endsM | __builtin_amdgcn_uicmp((unsigned)h, (unsigned)kMaxHops, 32 /* eq */);
+                        if (!kWallJ) doneM |= ballot64(wall) & ballot64(j >= kMaxReflect);
+                        busyM = busyMask & ~doneM;
+                    } else {
+                        const bool ends = next == cur;
+                        const bool cross = inside & !ends;
+                        token = cross ? cur : (wall ? next : token);
+                        cur = cross ? next : cur;
+                        h += cross ? 1 : 0;
+                        busy = !(ends | (h == kMaxHops) | (!kWallJ & wall & (j >= kMaxReflect)));
+                    }
+                    }
                 };
                 if (busy) {
                     int next, outSlot = 0;
@@ -933,12 +1010,15 @@ __device__ __forceinline__ void stream_body(
                     // (mixed meshes) left through a face group -- the coplanar pieces of a split face: the piece is chosen
                     // at the exit point S_ (cpf_walk.h; rare: per-lane reads of the CSR tables)
                     if (mixed && next != kSitOut && is_group(next)) next = resolve_group(next, S_, m.cellOff, m.planes, m.groupOff, m.groupNbr);
-                    // ---- what the visit led to.  The common outcomes -- the segment ends here, or it crosses into a neighbour --
-                    // are applied with selects, not branches: nested branches made the compiler shuttle cell, token and the two
-                    // counters between registers at every join (a dozen v_mov per round).  Only the wall is a branch (rare).
 #ifdef CPF_STREAM_TIMELINE
                     if (next == kSitOut) tlSat = true; else ++tlVis;
 #endif
+                    if constexpr (kVoteMask) { nextOut = next; wallOut = wallPlane; EOut = E; }
+                    else if constexpr (kWallJ) outcome_flat(next, wallPlane, E);
+                    else {
+                    // ---- what the visit led to.  The common outcomes -- the segment ends here, or it crosses into a neighbour --
+                    // are applied with selects, not branches: nested branches made the compiler shuttle cell, token and the two
+                    // counters between registers at every join (a dozen v_mov per round).  Only the wall is a branch (rare).
                     const bool ends = next == cur;                                 // segment ends in this cell
                     const bool wall = next < 0 && next != kSitOut;                 // a boundary face (kSitOut: no visit this round)
                     const bool cross = next >= 0 && !ends;
@@ -966,8 +1046,10 @@ __device__ __forceinline__ void stream_body(
                     if (kPlainOutcome) busy = !(ends | (cross & (h == kMaxHops)) | (wall & (j >= kMaxReflect)));
                     else
                     busy = !(ends || (cross && h == kMaxHops) || (wall && j >= kMaxReflect));   // hop cap: keep the last cell
+                    }
                 }
-                if (kMaskBusy) busyM = ballot64(busy);
+                if constexpr (kVoteMask) outcome_flat(nextOut, wallOut, EOut);
+                else if (kMaskBusy) busyM = ballot64(busy);
 #ifdef CPF_STREAM_TIMELINE
                 {
                     const unsigned nb = (unsigned)__popcll(busyMask), ns = (unsigned)__popcll(ballot64(tlSat));

@@ -87,6 +87,62 @@ __device__ __forceinline__ double kernarg_f64() {
     asm volatile("s_load_dwordx2 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "n"(BYTE_OFFSET) : "memory");
     return __longlong_as_double((long long)(((unsigned long long)r[1] << 32) | r[0]));
 }
+// THE LOOP LOOKUP IN HAND-WRITTEN ISA (the body without z, CPF_FLAT_LOOKUP_ASM in cpf_stream.hip).  The record cache's loop lookup:
+// one trip per distinct cell of the busy lanes `todo`.  The leader is the first set bit of `todo`, ck its cell; `same` are the
+// lanes in ck (every lane of the wave votes -- EXEC is whole here --, so a finished lane still standing in ck gets a slot number
+// nobody reads, as in the C++ loop); the slot is the first set bit of the compare of ck against the tag vector (lane k = the cell in slot k).
+// Hit: the slot is marked in `used` and moved into `myslot` of the `same` lanes.  Miss: the busy lanes among `same` -- `same & todo`:
+// a busy lane leaves `todo` only with its cell -- go to `missLanes`.  What hipcc makes of the C++ loop costs 14 scalar-issue and 7
+// vector instructions per hit; this is 7 and 5, one of the seven a pad (no leader re-read, no AND with the busy mask, `used` by
+// s_bitset1 instead of shift and OR, the select in place, one exit test -- s_andn2 sets SCC).  `used` stays in the trip: one
+// instruction per trip, where rebuilding it from `myslot` behind the loop is estimated at three per slot in every round with a
+// miss, four rounds of ten (an estimate from the listing: the lazy form was not built or measured).
+// Wait states, by hand (the compiler's hazard recogniser does not look inside the string):
+//   * the lane select of v_readlane is written by the SCALAR unit (s_ff1): no hazard (four states are wanted behind a VALU write);
+//   * a VALU write of an SGPR read by a VALU as an operand wants TWO states on gfx950 (hipcc puts `s_nop 1` between a v_readlane
+//     and a v_cmp on its result; gfx90a wants none).  v_readlane writes ck and both v_cmp read it, and nothing in the trip is
+//     independent of ck: `s_nop 1` behind the v_readlane.  v_cmp writes `same` and v_cndmask reads it as its mask five instructions
+//     later (v_cmp, branch, s_ff1, s_bitset1, v_mov): covered;
+//   * v_cmp writes VCC -> s_cbranch_vccz and the scalar unit's read of VCC: none.
+// No EXEC write, no memory operation; M0 is not touched.
+__device__ __forceinline__ void lookup_loop_asm(unsigned long long todo, int lk, int tagv, int& myslot, unsigned& used, unsigned long long& missLanes) {
+    unsigned long long same;
+    int ck, bit, slotv;
+    asm volatile(
+        "s_cmp_eq_u64 %[todo], 0\n\t"
+        "s_cbranch_scc1 .Lcpf_lk_done_%=\n"
+        ".Lcpf_lk_trip_%=:\n\t"
+        "s_ff1_i32_b64 %[bit], %[todo]\n\t"
+        "v_readlane_b32 %[ck], %[lk], %[bit]\n\t"
+        "s_nop 1\n\t"
+        "v_cmp_eq_u32_e64 %[same], %[ck], %[lk]\n\t"
+        "v_cmp_eq_u32_e32 vcc, %[ck], %[tagv]\n\t"
+        "s_cbranch_vccz .Lcpf_lk_miss_%=\n\t"
+        "s_ff1_i32_b64 %[bit], vcc\n\t"
+        "s_bitset1_b32 %[used], %[bit]\n\t"
+        "v_mov_b32_e32 %[slotv], %[bit]\n\t"
+        "v_cndmask_b32_e64 %[myslot], %[myslot], %[slotv], %[same]\n\t"
+        "s_andn2_b64 %[todo], %[todo], %[same]\n\t"
+        "s_cbranch_scc1 .Lcpf_lk_trip_%=\n\t"
+        "s_branch .Lcpf_lk_done_%=\n"
+        ".Lcpf_lk_miss_%=:\n\t"
+        "s_and_b64 %[same], %[same], %[todo]\n\t"
+        "s_or_b64 %[miss], %[miss], %[same]\n\t"
+        "s_andn2_b64 %[todo], %[todo], %[same]\n\t"
+        "s_cbranch_scc1 .Lcpf_lk_trip_%=\n"
+        ".Lcpf_lk_done_%=:"
+        : [todo] "+s"(todo), [myslot] "+v"(myslot), [used] "+s"(used), [miss] "+s"(missLanes), [same] "=&s"(same), [ck] "=&s"(ck),
+          [bit] "=&s"(bit), [slotv] "=&v"(slotv)
+        : [lk] "v"(lk), [tagv] "v"(tagv)
+        : "vcc", "scc");
+}
+// h += 1 in the lanes of a wave mask: the mask is the carry-in of one add.  (What hipcc makes of `h += cond ? 1 : 0` while cond is a
+// compare; a mask that comes from scalar operations it first turns into 0 / 1 in a vector register.)  The carry-out goes to VCC.
+// PRECONDITION: `lanes` is written by the scalar unit (here: s_andn2 of two masks).  A mask straight from a v_cmp is a VALU write of an
+// SGPR, which wants two wait states in front of this VALU read on gfx950, and hipcc pads nothing inside or in front of the string.
+__device__ __forceinline__ void add_lanes(int& h, unsigned long long lanes) {
+    asm("v_addc_co_u32_e64 %0, vcc, 0, %0, %1" : "+v"(h) : "s"(lanes) : "vcc");
+}
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory"); }
 

@@ -17,7 +17,11 @@ cp $LIB /tmp/lib_orig.so
 for rep in $(seq 1 "$REPS"); do
   for name in $NAMES; do
     if [ "$name" = product ]; then cp /tmp/lib_orig.so $LIB; else cp "build_ab/lib_$name.so" $LIB || continue; fi
-    timeout -s KILL ${AB_TIMEOUT:-300} "$@" 2>/tmp/ab_err.log | grep '^{' | sed "s/^/$name: /" || tail -3 /tmp/ab_err.log
+    timeout -s KILL ${AB_TIMEOUT:-300} "$@" 2>/tmp/ab_err.log | grep '^{' | sed "s/^/$name: /"
+    rc=${PIPESTATUS[0]}
+    # a run that did not end well -- killed, aborted, crashed, or a HIP error reported and exit 1 -- ends the call: nothing more is
+    # started on that GPU
+    if [ "$rc" -ne 0 ]; then tail -3 /tmp/ab_err.log; echo "$name: exit $rc, stopped"; cp /tmp/lib_orig.so $LIB; exit "$rc"; fi
   done
 done
 cp /tmp/lib_orig.so $LIB
