@@ -184,7 +184,7 @@ struct StepPlan {
 // vf: the "VertexVelocity" cycle's tables (null: the cell-constant cycle); stats: statistics counters are on
 StepPlan plan_step(const MeshView& m, const StreamState& ss, int variant, const VertexField* vf, int64_t n, int nCyc, double D,
                    unsigned flags, bool stats);
-// zSettled: the cloud's z is settled (CPF_STEP_Z_SETTLED; the flat instantiations then leave z in memory alone, StreamArgs::zSettled);
+// zSettled: the cloud's z is settled (CPF_STEP_Z_SETTLED; a flat launch then runs the body without z, StepPlan::flat_body);
 // evStart / evStop: the time stamps of a plan.stamped() launch (null: untimed)
 hipError_t launch_step(const StepPlan& p, hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid,
                        double* vel, int64_t n, double dt, double D, uint32_t step0, int nCyc, uint32_t seed, const MeshView& m,

@@ -89,7 +89,9 @@ static_assert(offsetof(StreamKernArgs, x) == 0 && offsetof(StreamKernArgs, cell)
 constexpr int kKernArgHitSpill = (int)(offsetof(StreamKernArgs, sa) + offsetof(StreamArgs, hitSpill));
 constexpr int kKernArgZBad = (int)(offsetof(StreamKernArgs, sa) + offsetof(StreamArgs, zBad));
 // the Brownian kick's own arguments are read from the kernarg segment where they are needed -- the particle ids once per tile,
-// step0 / seed / sigma once per cycle -- instead of holding seven scalar registers for the whole kernel (CPF_STREAM_BROWN_KERNARG)
+// step0 / seed / sigma once per cycle -- instead of holding seven scalar registers for the whole kernel (CPF_STREAM_BROWN_KERNARG).
+// (The switch stays although nothing builds its 0: written without it, the generated code of 101 of the 192 kernels moves -- the
+// same instruction counts to within two, another digest; docs/experiments.md, round 14.)
 constexpr int kKernArgGid = (int)offsetof(StreamKernArgs, gid), kKernArgSigma = (int)offsetof(StreamKernArgs, sigma);
 constexpr int kKernArgStep0 = (int)offsetof(StreamKernArgs, step0), kKernArgSeed = (int)offsetof(StreamKernArgs, seed);
 #ifndef CPF_STREAM_BROWN_KERNARG
@@ -101,27 +103,19 @@ constexpr int kKernArgStep0 = (int)offsetof(StreamKernArgs, step0), kKernArgSeed
 #ifndef CPF_STREAM_L1_ZERO_SKIP
 #define CPF_STREAM_L1_ZERO_SKIP 1
 #endif
-#ifndef CPF_STREAM_LAZY_USED
-#define CPF_STREAM_LAZY_USED 1
-#endif
 #ifndef CPF_STREAM_BOX_SPARSE
 #define CPF_STREAM_BOX_SPARSE 1
 #endif
-// the zero-denominator vote per face in the flat walk: off -- a 2-D mesh whose side faces are exactly parallel to everybody's
-// displacement is a mesh of boxes in axis-aligned flow; pitzDaily's trapezoids never are, and the vote costs the headline 2.3 %
-// (0.1048-0.1063 -> 0.1032-0.1033 ms, analytic field 0.0986-0.0999 -> 0.0985-0.0986).  Same results either way.
 // the flat walk under the Brownian kick (cpf_walk.h, trace_lds4_flat<.., KEEP_Z>): 0 = off (A/B builds)
 #ifndef CPF_STREAM_FLAT_KICK
 #define CPF_STREAM_FLAT_KICK 0
 #endif
+// the zero-denominator vote per face in the flat walk: off -- a 2-D mesh whose side faces are exactly parallel to everybody's
+// displacement is a mesh of boxes in axis-aligned flow; pitzDaily's trapezoids never are, and the vote costs the headline 2.3 %
+// (0.1048-0.1063 -> 0.1032-0.1033 ms, analytic field 0.0986-0.0999 -> 0.0985-0.0986).  Same results either way.  (On: the body
+// without z takes the C++ face test, stream_body's kFaceAsm)
 #ifndef CPF_STREAM_FLAT_ZERO_SKIP
 #define CPF_STREAM_FLAT_ZERO_SKIP 0
-#endif
-// the flat walk on a cloud whose z is settled (StreamArgs::zSettled, cpf_walk.h "flat walk"): z is neither loaded nor stored --
-// 40 of the 56 bytes per particle-step.  0 = always stream z (A/B builds).  (Skipping the z parts of the LDS traffic as well --
-// sE[2], a wave-uniform branch per write -- measured no faster: docs/experiments.md, round 7)
-#ifndef CPF_STREAM_FLAT_Z
-#define CPF_STREAM_FLAT_Z 1
 #endif
 #ifndef CPF_STREAM_SLOTS_BOX
 #define CPF_STREAM_SLOTS_BOX 9
@@ -159,51 +153,6 @@ constexpr int kKernArgStep0 = (int)offsetof(StreamKernArgs, step0), kKernArgSeed
 // 98 512-99 584 with eight (the parent 92 607-92 620).  (The three-coordinate body lost 17 % when squeezed into an eighth wave's 64.)
 #ifndef CPF_STREAM_WAVES_FLAT_BODY
 #define CPF_STREAM_WAVES_FLAT_BODY 0
-#endif
-// the round of the body without z (step_kernel_stream_flat), each item an A/B knob (docs/experiments.md, round 9):
-// MASK: which lanes are busy is carried from round to round as a wave mask in scalar registers -- the round's vote on it and the
-// loop's were two trips through a vector register (v_cndmask 0/1 + v_cmp) per round, now one;
-// OUTCOME: "still busy" from plain mask operations instead of three nested exec regions;
-// GATHER: the per-lane gather walk (a round with 32 or more lanes without a record slot: a cloud that is not kept sorted) is the
-// flat walk on the global record -- four side faces, two coordinates -- instead of the six-face walk in three;
-// HINTS: ... and lies behind the round's hot path (branch weights);  ONE_HOOK: the zero-cycle launch runs the round's hook.
-// MASK and OUTCOME are where the time is (+2.5 % each); the other three take a sixth of the code out and nothing off the clock.
-// (Measured and dropped: a one-cell short cut in front of the loop lookup, -1.2 %.)
-#ifndef CPF_FLAT_ROUND_GATHER
-#define CPF_FLAT_ROUND_GATHER 1
-#endif
-#ifndef CPF_FLAT_ROUND_HINTS
-#define CPF_FLAT_ROUND_HINTS 1
-#endif
-#ifndef CPF_FLAT_ROUND_ONE_HOOK
-#define CPF_FLAT_ROUND_ONE_HOOK 1
-#endif
-#ifndef CPF_FLAT_ROUND_MASK
-#define CPF_FLAT_ROUND_MASK 1
-#endif
-#ifndef CPF_FLAT_ROUND_OUTCOME
-#define CPF_FLAT_ROUND_OUTCOME 1
-#endif
-// FACE_ASM: the face tests of the body without z -- its LDS visit and its gather visit -- as a hand-written block each: the
-// predicates chained in EXEC (v_cmpx) instead of combined on the scalar ALU (cpf_walk.h, face_accept_flat_asm).  0 = the C++ face test.
-#ifndef CPF_FLAT_FACE_ASM
-#define CPF_FLAT_FACE_ASM 1
-#endif
-// the round's bookkeeping around the face blocks, body without z only, each item an A/B knob, 0 = the code as the compiler made it
-// (docs/experiments.md, round 13):
-// LOOKUP_ASM: the loop lookup's trip -- one per distinct cell of the busy lanes -- as a hand-written block (cpf_stream_ops.h,
-// lookup_loop_asm): 7 scalar-issue (one of them a pad) and 5 vector instructions for a record on chip, where hipcc needs 14 and 7;
-// VOTE_MASK: the visit's outcome is applied behind the busy lanes' region, so that "still busy" is built from the compares' own masks
-// -- no trip of the vote through a vector register (v_cndmask 0/1 + v_cmp) -- and ANDed with the round's busy mask;
-// WALL_J: "still on a wall after five bounces" is tested in the wall branch, where j changes, not by every lane in every round.
-#ifndef CPF_FLAT_LOOKUP_ASM
-#define CPF_FLAT_LOOKUP_ASM 1
-#endif
-#ifndef CPF_FLAT_VOTE_MASK
-#define CPF_FLAT_VOTE_MASK 1
-#endif
-#ifndef CPF_FLAT_WALL_J
-#define CPF_FLAT_WALL_J 1
 #endif
 // (with the kick the landing zone and the hit pool are larger: 7 slots keep the sixth wave, 6600 of 6826 bytes)
 #ifndef CPF_STREAM_SLOTS_BROWN
@@ -270,10 +219,12 @@ static_assert(shape_is<0>(6, 7, 1, 6, 7, 18) && shape_is<1>(9, 7, 1, 10, 5, 40) 
 // instead of the record's cell-constant one; everything else -- the record cache, the walk, the prefetch -- is the same code.
 // Two kernels wrap it (below): step_kernel_stream, whose name and parameter list every profile and test of rounds 2-5 knows,
 // and step_kernel_stream_vertex, which appends the VertexField to the same parameter list (the kernarg offsets stay valid).
-// ZSET: the flat walk of a launch whose z is settled (StreamArgs::zSettled) as a body of its own, in which z does not exist --
-// the landing zone is x | y | cell, positions, end points, the hit point and the parked result are pairs, no z term is computed
-// (cpf_walk.h "settled z": the same bits in x, y and the cell as the three-coordinate body run with z = 0, which is what the
-// run-time flag made of such a launch).  A third kernel wraps it: step_kernel_stream_flat, step_kernel_stream's parameter list.
+// ZSET: the flat walk of a launch whose z is settled (CPF_STEP_Z_SETTLED) as a body of its own, in which z does not exist --
+// the landing zone is x | y | cell, positions, end points, the hit point and the parked result are pairs, no z term is computed,
+// z in memory is left alone (cpf_walk.h "settled z": the same bits in x, y and the cell as the three-coordinate body run with
+// z = 0).  "No z" is this parameter and nothing else: every other instantiation, the three-coordinate flat walk included, loads
+// and stores z.  The body has no build-time variants -- what each piece of its round was measured at stands where the piece is.
+// A third kernel wraps it: step_kernel_stream_flat, step_kernel_stream's parameter list.
 template <bool BROWNIAN, bool REFLECT, bool STORE_VEL, bool STATS, int LOOKUP, bool VERTEX, bool ZSET = false>
 __device__ __forceinline__ void stream_body(
     const int64_t* __restrict__ gid, double* __restrict__ vel, int64_t n, double dt, double sigma, uint32_t step0,
@@ -317,16 +268,10 @@ __device__ __forceinline__ void stream_body(
     const unsigned preBase = uniform32(lds_addr(sPre));
     const unsigned slotBase = uniform32(lds_addr(slots));
     const int tpc = sa.tilesPerChunk;
-    constexpr bool kMaskBusy = ZSET && CPF_FLAT_ROUND_MASK != 0, kPlainOutcome = ZSET && CPF_FLAT_ROUND_OUTCOME != 0;
-    constexpr bool kFlatGather = ZSET && CPF_FLAT_ROUND_GATHER != 0, kHints = ZSET && CPF_FLAT_ROUND_HINTS != 0;
-    constexpr bool kOneHook = ZSET && CPF_FLAT_ROUND_ONE_HOOK != 0;
-    constexpr bool kFaceAsm = ZSET && CPF_FLAT_FACE_ASM != 0 && CPF_STREAM_FLAT_ZERO_SKIP == 0;
-    constexpr bool kLookupAsm = ZSET && CPF_FLAT_LOOKUP_ASM != 0, kVoteMask = kMaskBusy && CPF_FLAT_VOTE_MASK != 0;
-    constexpr bool kWallJ = ZSET && CPF_FLAT_WALL_J != 0;
-    // (FLAT) z of every live particle is a fixed point of the flat cycle: the launch leaves z in memory alone.  Wave-uniform;
-    // the landing zone is then x[64] | y[64] | cell[64], and no z is loaded or stored (the z the walk carries in registers is dead)
-    // (ZSET: at compile time, and no test of it is left in the code)
-    const bool zKeep = ZSET || (FLAT && CPF_STREAM_FLAT_Z != 0 && sa.zSettled != 0);
+    // (ZSET) the face tests of the LDS visit and of the gather visit as a hand-written block each: the predicates chained in EXEC
+    // (v_cmpx) instead of combined on the scalar ALU (cpf_walk.h, face_accept_flat_asm; the block has no zero-denominator vote).
+    // Round 12: +4.4 % / +5.3 % on the headline against the C++ face test
+    constexpr bool kFaceAsm = ZSET && CPF_STREAM_FLAT_ZERO_SKIP == 0;
     // the lane's parked end point / parked result (sE): a pair without z
     auto park = [&](const D3& e) __attribute__((always_inline)) {
         sE[0][lane] = e.x; sE[1][lane] = e.y;
@@ -400,7 +345,7 @@ __device__ __forceinline__ void stream_body(
         if (t < nFull) {
             const char* s1 = (ul < 32u ? reinterpret_cast<const char*>(x + b) : reinterpret_cast<const char*>(y + b)) + (ul & 31u) * 16u;
             glds16(s1, preBase);                                               // x -> [0, 512), y -> [512, 1024)
-            if (zKeep) {
+            if (ZSET) {                // (no z: 40 of the 56 bytes per particle-step; round 7: +3-6 % on the headline)
                 if (ul < 16u) glds16(reinterpret_cast<const char*>(cell + b) + ul * 16u, preBase + 1024u);      // cell -> [1024, 1280)
             } else if (ul < 48u) {
                 const char* s2 = ul < 32u ? reinterpret_cast<const char*>(z + b) + ul * 16u
@@ -418,7 +363,7 @@ __device__ __forceinline__ void stream_body(
         }
         const unsigned lim = nTail - 1u;
         const unsigned l = ul < lim ? ul : lim;
-        if (zKeep) {
+        if (ZSET) {
             const double vx = (x + b)[l], vy = (y + b)[l];
             const int vc = (cell + b)[l];
             sPre[ul] = vx; sPre[64 + ul] = vy;
@@ -465,7 +410,7 @@ __device__ __forceinline__ void stream_body(
             const unsigned plim = tile < nFull ? 63u : nTail - 1u;      // last lane with a particle slot
             double px = sPre[ul], py = sPre[64 + ul], pz = 0.0;
             int pc;
-            if (zKeep) pc = reinterpret_cast<const int*>(sPre + 128)[ul];
+            if (ZSET) pc = reinterpret_cast<const int*>(sPre + 128)[ul];
             else { pz = sPre[128 + ul]; pc = reinterpret_cast<const int*>(sPre + 192)[ul]; }
             uint64_t pid = 0;
             if (BROWNIAN) {
@@ -480,7 +425,7 @@ __device__ __forceinline__ void stream_body(
             // (flat walk that streams z) a live particle whose z is not finite: the launch says so, and the cloud's owner does not
             // call it settled -- a wall would mirror such a particle to NaN in x and y, which a launch without z cannot do
             // (cpf_walk.h "settled z").  Rare: the pointer is read from the kernarg segment where it is needed
-            if (FLAT && !ZSET && !zKeep && ballot64(pc >= 0 && !(fabs(pz) <= 1.7976931348623157e308)) != 0ull) {
+            if (FLAT && !ZSET && ballot64(pc >= 0 && !(fabs(pz) <= 1.7976931348623157e308)) != 0ull) {
                 unsigned* const bad = static_cast<unsigned*>(kernarg_pointer<kKernArgZBad>());
                 if (bad != nullptr && lane == 0) *bad = 1u;
             }
@@ -531,10 +476,10 @@ __device__ __forceinline__ void stream_body(
                     }
                     if (ul <= rlim) {
                         async_store(x + b, ul * 8u, prev.x); async_store(y + b, ul * 8u, prev.y);
-                        if (!zKeep) async_store(z + b, ul * 8u, prev.z);
+                        if (!ZSET) async_store(z + b, ul * 8u, prev.z);
                         async_store(cell + b, ul * 4u, rc);
                     }
-                    younger += zKeep ? 3 : 4;
+                    younger += ZSET ? 3 : 4;
                 }
                 if (ntilesLeft > 0 && !(sa.debug & 2)) younger += prefetch(ntile, cp);
                 __builtin_amdgcn_sched_barrier(0);
@@ -546,7 +491,9 @@ __device__ __forceinline__ void stream_body(
             // crossed or hit in this cycle), it has been reflected iff j != 0, and it is lost in this cycle iff
             // j >= kMaxReflect (still on a wall after 5 bounces; a wall without reflection sets j = kMaxReflect too).
             bool busy = false;
-            unsigned long long busyM = 0ull;         // (kMaskBusy) the busy lanes as a wave mask, from one round to the next
+            // (ZSET) the busy lanes as a wave mask in scalar registers, from one round to the next: the round's vote on `busy` and the
+            // loop's were two trips through a vector register (v_cndmask 0/1 + v_cmp) per round (round 9: +2.5 % on the headline)
+            unsigned long long busyM = 0ull;
             bool zUnclear = false;                   // (kick on a one-cell-thick mesh) some lane's mirrored end point is not clear of the z planes
             int token = INT32_MIN, h = 0, j = 0;
             int hitAt = -1;                          // pool: where this lane's hit point is parked (< kPool: pool entry)
@@ -565,7 +512,7 @@ __device__ __forceinline__ void stream_body(
             auto cycle_begin = [&](int c) __attribute__((always_inline)) {
                 if (cur < 0) cur = CPF_CELL_FROZEN;                                  // lost in the previous cycle: w = 0
                 busy = cur >= 0;
-                if (kMaskBusy) busyM = ballot64(cur >= 0);
+                if (ZSET) busyM = ballot64(cur >= 0);
                 token = INT32_MIN; h = 0; j = 0;
                 if (bigCells) key2 = 0;
                 if (!HIT_IN_REGS && REFLECT) { hitAt = -1; if (lane == 0) sPoolUsed = 0u; }
@@ -647,8 +594,8 @@ __device__ __forceinline__ void stream_body(
                 // are what that case is short of (measured: the fixed sequence costs pitzDaily 1.5-3 %, and saves the
                 // large meshes 4-7 %; both in ONE kernel behind a run-time flag: the worse of the two everywhere, hence
                 // the template parameter).  A round that finds every cell on chip (the common case) issues no memory request.
-                const unsigned long long busyMask = kMaskBusy ? busyM : ballot64(busy);
-                if (kMaskBusy) busy = __builtin_amdgcn_inverse_ballot_w64(busyM);
+                const unsigned long long busyMask = ZSET ? busyM : ballot64(busy);
+                if (ZSET) busy = __builtin_amdgcn_inverse_ballot_w64(busyM);
                 // the lane's parked end point, requested before the lookup: its LDS round trip hides behind it (1 %)
                 const D3 Epre = parked();
                 // what the lane looks up: its cell -- or, between the two halves of a visit of a two-record cell, the second record
@@ -669,9 +616,9 @@ __device__ __forceinline__ void stream_body(
                             missLanes = 0ull;
                         }
                     } else {
-#if CPF_STREAM_LAZY_USED
                         // the sweep itself is vector work only; which slots are in use (`used`) is scalar work -- four
-                        // operations per tag -- that only a round with a miss needs (the victims of its jobs)
+                        // operations per tag -- that only a round with a miss needs (the victims of its jobs): 36 scalar
+                        // instructions less in every other round, 1-2 % on the 3-D meshes
                         unsigned long long eqs[NS];
 #pragma unroll
                         for (int k = 0; k < NS; ++k) {
@@ -684,21 +631,11 @@ __device__ __forceinline__ void stream_body(
 #pragma unroll
                             for (int k = 0; k < NS; ++k) used |= ((eqs[k] & busyMask) != 0ull ? 1u : 0u) << k;
                         }
-#else
-#pragma unroll
-                        for (int k = 0; k < NS; ++k) {
-                            const int tk = __builtin_amdgcn_readlane(tagv, k);
-                            const unsigned long long eqK = __builtin_amdgcn_uicmp((unsigned)lk, (unsigned)tk, 32 /* eq */);
-                            const unsigned long long inK = eqK & busyMask;
-                            // (one select per tag on the compare's own mask; left alone, hipcc issues a second, inverted
-                            // compare per tag to get the constant into the operand slot it prefers)
-                            asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(myslot) : "v"(myslot), "n"(k), "s"(eqK));
-                            used |= (inK != 0ull ? 1u : 0u) << k;
-                            missLanes &= ~inK;
-                        }
-#endif
                     }
-                } else if (kLookupAsm) {
+                } else if (ZSET) {
+                    // the loop lookup's trip as a hand-written block (cpf_stream_ops.h, lookup_loop_asm): 7 scalar-issue and 5 vector
+                    // instructions for a record on chip, where hipcc makes 14 and 7 of the loop below (round 13: +2.7 % on the headline).
+                    // (Measured and dropped in round 9: a one-cell short cut in front of the lookup, -1.2 %.)
                     missLanes = 0ull;
                     lookup_loop_asm(busyMask, lk, tagv, myslot, used, missLanes);
                 } else {
@@ -770,7 +707,7 @@ __device__ __forceinline__ void stream_body(
                     } else
                     if (younger >= 7) wait_vmcnt<7>();
                     else if (younger == 6) wait_vmcnt<6>();
-                    else if (younger == 5) wait_vmcnt<5>();                 // (settled z: three stores + the prefetch)
+                    else if (younger == 5) wait_vmcnt<5>();                 // (no launch gets here since round 14: three stores + the prefetch is the body without z, above)
                     else if (younger >= 4) wait_vmcnt<4>();
                     else if (younger == 3) wait_vmcnt<3>();
                     else if (younger >= 2) wait_vmcnt<2>();
@@ -818,13 +755,14 @@ __device__ __forceinline__ void stream_body(
                     park(E);
                     return E;
                 };
-                // ---- (the body without z, kVoteMask / kWallJ) what the visit led to, as the statement at the end of the busy lanes' region says it,
-                // in a form of its own:
-                //   * kVoteMask: it is applied BEHIND that region, by every lane of the wave, to what the visit left in nextOut, wallOut, EOut
+                // ---- (the body without z) what the visit led to, as the statement at the end of the busy lanes' region says it for the other
+                // kernels, in a form of its own (round 9: the busy mask and plain mask operations in place of three nested exec regions,
+                // +2.5 % each on the headline; round 13: the two items below, 1.6 % and 1.3-1.8 % of the product):
+                //   * it is applied BEHIND that region, by every lane of the wave, to what the visit left in nextOut, wallOut, EOut
                 //     -- a lane that is not busy made no visit, next = kSitOut, which is no outcome at all.  "Still busy" is then built from
                 //     the compares' own masks and ANDed with the round's busy mask; inside the region the vote went through a vector
                 //     register (the region's join merges a bool);
-                //   * kWallJ: j changes in the wall branch alone, so "lost" -- five bounces, or a wall that does not reflect -- is decided
+                //   * j changes in the wall branch alone, so "lost" -- five bounces, or a wall that does not reflect -- is decided
                 //     there: such a lane's hop count is set to the cap, and the cap ends it like any other.  (h is dead by then: the lane
                 //     is done with the cycle and cycle_begin resets it; cell, token and j are the same.)
                 //   * "at the hop cap" needs no AND with "crossed": h grows by crossing alone and a lane at the cap is done, so a busy lane
@@ -833,8 +771,8 @@ __device__ __forceinline__ void stream_body(
                 double4 wallOut;
                 D3 EOut;
                 auto outcome_flat = [&](const int next, const double4& wallPlane, D3& E) __attribute__((always_inline)) {
-                    // (in a discarded statement for every other kernel: their closure captures nothing, their code is the parent's to the instruction)
-                    if constexpr (kVoteMask || kWallJ) {
+                    // (in a discarded statement for every other kernel: their closure captures nothing)
+                    if constexpr (ZSET) {
                     const bool wall = next < 0 && next != kSitOut;
                     const bool inside = next >= 0;
                     if (wall) {
@@ -843,35 +781,26 @@ __device__ __forceinline__ void stream_body(
                             park_hit(S_);
                             if (STATS) ++st.refl;
                             const D3 nn = {wallPlane.x, wallPlane.y, wallPlane.z};
+                            // (cpf_walk.h "settled z": the z terms of sd and of the mirrored end point are +-0 * 0)
                             const double sd = fma(wallPlane.y, E.y, wallPlane.x * E.x) - wallPlane.w;
                             E = {fma(-2.0 * sd, nn.x, E.x), fma(-2.0 * sd, nn.y, E.y), 0.0};
                             park(E);
-                            v = axpy(-2.0 * dot3(wallPlane, v), nn, v);
+                            v = axpy(-2.0 * dot3(wallPlane, v), nn, v);       // (only a launch that stores velocities reads v, all three components)
                             h = 0;
                             ++j;
                         }
-                        if (kWallJ && (!REFLECT || j >= kMaxReflect)) h = kMaxHops;
+                        if (!REFLECT || j >= kMaxReflect) h = kMaxHops;
                     }
-                    if constexpr (kVoteMask) {
-                        // (every term a compare's own mask: a vote on a bool that is not itself a compare -- an OR of them -- goes
-                        // through a vector register again.  EXEC is whole here, and the round's busy mask closes the expression)
-                        const unsigned long long endsM = __builtin_amdgcn_uicmp((unsigned)next, (unsigned)cur, 32 /* eq */);
-                        const unsigned long long crossM = ballot64(inside) & ~endsM;
-                        const bool cross = __builtin_amdgcn_inverse_ballot_w64(crossM);
-                        token = cross ? cur : (wall ? next : token);
-                        cur = cross ? next : cur;
-                        add_lanes(h, crossM);
-                        unsigned long long doneM = endsM | __builtin_amdgcn_uicmp((unsigned)h, (unsigned)kMaxHops, 32 /* eq */);
-                        if (!kWallJ) doneM |= ballot64(wall) & ballot64(j >= kMaxReflect);
-                        busyM = busyMask & ~doneM;
-                    } else {
-                        const bool ends = next == cur;
-                        const bool cross = inside & !ends;
-                        token = cross ? cur : (wall ? next : token);
-                        cur = cross ? next : cur;
-                        h += cross ? 1 : 0;
-                        busy = !(ends | (h == kMaxHops) | (!kWallJ & wall & (j >= kMaxReflect)));
-                    }
+                    // (every term a compare's own mask: a vote on a bool that is not itself a compare -- an OR of them -- goes
+                    // through a vector register again.  EXEC is whole here, and the round's busy mask closes the expression)
+                    const unsigned long long endsM = __builtin_amdgcn_uicmp((unsigned)next, (unsigned)cur, 32 /* eq */);
+                    const unsigned long long crossM = ballot64(inside) & ~endsM;
+                    const bool cross = __builtin_amdgcn_inverse_ballot_w64(crossM);
+                    token = cross ? cur : (wall ? next : token);
+                    cur = cross ? next : cur;
+                    add_lanes(h, crossM);
+                    const unsigned long long doneM = endsM | __builtin_amdgcn_uicmp((unsigned)h, (unsigned)kMaxHops, 32 /* eq */);
+                    busyM = busyMask & ~doneM;
                     }
                 };
                 if (busy) {
@@ -885,7 +814,7 @@ __device__ __forceinline__ void stream_body(
                     bool hdrCell = false;
                     if (bigCells && myslot >= 0) hdrCell = *reinterpret_cast<const int*>(&slots[0][0] + myslot * kSlotStride + 7) == kBigCellMark;
                     // (the body without z: the lane has its record on chip -- the per-lane gather walk lies behind the round's hot path)
-                    if ((kHints && __builtin_expect(myslot >= 0, 1)) || (!kHints && myslot >= 0 && !(bigCells && hdrCell))) {
+                    if ((ZSET && __builtin_expect(myslot >= 0, 1)) || (!ZSET && myslot >= 0 && !(bigCells && hdrCell))) {
                         const double4* rec = &slots[0][0] + myslot * kStride;
                         if (needAdvect) E = advect(rec);
                         // ---- the visit, and -- in the same round -- the visits after a wall.  A wall hit never changes the
@@ -974,7 +903,7 @@ __device__ __forceinline__ void stream_body(
                         // no slot: more distinct new cells in the wave than the round can place (a cloud that is not
                         // kept sorted).  Per-lane gathers keep such a wave moving.
                         next = kSitOut;
-                        if ((kHints && __builtin_expect(gatherRound, 0)) || (!kHints && (gatherRound || (bigCells && hdrCell)))) {
+                        if ((ZSET && __builtin_expect(gatherRound, 0)) || (!ZSET && (gatherRound || (bigCells && hdrCell)))) {
                             const double4* rec = BOX ? m.boxRec + 4 * (int64_t)cur : m.cellRec + 8 * (int64_t)cur;
                             if (needAdvect) E = advect(rec);
                             int gS0 = 0;
@@ -994,8 +923,10 @@ __device__ __forceinline__ void stream_body(
                             }
                             if (BOX) next = trace_box<false, mixed>(S_, E, cur, rec, token, outSlot);
                             // (the body without z) the flat walk on the global record: four side faces, two coordinates, the face
-                            // test of the LDS visit.  Same bits as the six-face walk with z = 0 (cpf_walk.h "the body without z")
-                            else if (kFlatGather) next = trace_lds4_flat<false, false, kFaceAsm>(S_, E, cur, rec, token, outSlot);
+                            // test of the LDS visit.  Same bits as the six-face walk with z = 0 (cpf_walk.h "the body without z").
+                            // (Round 9: this, the branch weights above and the zero-cycle launch through the round's hook take a sixth of
+                            // the code out and nothing off the clock)
+                            else if (ZSET) next = trace_lds4_flat<false, false, kFaceAsm>(S_, E, cur, rec, token, outSlot);
                             else if (!gBig)
                             next = trace_fixed<6, false, mixed, kGatherAhead>(S_, E, cur, rec, reinterpret_cast<const int32_t*>(rec + 7), token, outSlot, 0);
                             if (STATS) ++st.hops;
@@ -1013,8 +944,7 @@ __device__ __forceinline__ void stream_body(
 #ifdef CPF_STREAM_TIMELINE
                     if (next == kSitOut) tlSat = true; else ++tlVis;
 #endif
-                    if constexpr (kVoteMask) { nextOut = next; wallOut = wallPlane; EOut = E; }
-                    else if constexpr (kWallJ) outcome_flat(next, wallPlane, E);
+                    if constexpr (ZSET) { nextOut = next; wallOut = wallPlane; EOut = E; }        // (applied behind the region: outcome_flat)
                     else {
                     // ---- what the visit led to.  The common outcomes -- the segment ends here, or it crosses into a neighbour --
                     // are applied with selects, not branches: nested branches made the compiler shuttle cell, token and the two
@@ -1029,12 +959,9 @@ __device__ __forceinline__ void stream_body(
                             park_hit(S_);
                             if (STATS) ++st.refl;
                             const D3 nn = {wallPlane.x, wallPlane.y, wallPlane.z};
-                            // (ZSET, cpf_walk.h "settled z": the z terms of sd and of the mirrored end point are +-0 * 0)
-                            const double sd = (ZSET ? fma(wallPlane.y, E.y, wallPlane.x * E.x) : dot3(wallPlane, E)) - wallPlane.w;
-                            if (ZSET) E = {fma(-2.0 * sd, nn.x, E.x), fma(-2.0 * sd, nn.y, E.y), 0.0};
-                            else E = axpy(-2.0 * sd, nn, E);
+                            const double sd = dot3(wallPlane, E) - wallPlane.w;
+                            E = axpy(-2.0 * sd, nn, E);
                             park(E);
-                            // (ZSET: only a launch that stores velocities reads v, all three components, as ever)
                             v = axpy(-2.0 * dot3(wallPlane, v), nn, v);
                             h = 0;
                             ++j;                                                   // j == 5: still on a wall after 5 bounces, lost
@@ -1043,13 +970,10 @@ __device__ __forceinline__ void stream_body(
                     token = cross ? cur : (wall ? next : token);                   // (a wall's code as token: the advect is done)
                     cur = cross ? next : cur;
                     h += cross ? 1 : 0;
-                    if (kPlainOutcome) busy = !(ends | (cross & (h == kMaxHops)) | (wall & (j >= kMaxReflect)));
-                    else
                     busy = !(ends || (cross && h == kMaxHops) || (wall && j >= kMaxReflect));   // hop cap: keep the last cell
                     }
                 }
-                if constexpr (kVoteMask) outcome_flat(nextOut, wallOut, EOut);
-                else if (kMaskBusy) busyM = ballot64(busy);
+                if constexpr (ZSET) outcome_flat(nextOut, wallOut, EOut);
 #ifdef CPF_STREAM_TIMELINE
                 {
                     const unsigned nb = (unsigned)__popcll(busyMask), ns = (unsigned)__popcll(ballot64(tlSat));
@@ -1081,8 +1005,8 @@ __device__ __forceinline__ void stream_body(
 
             // (the body without z: a zero-cycle launch runs ONE round with no busy lane and neither a cycle's begin nor its move --
             // the round's own hook stores what was loaded -- so that the kernel holds one instance of the hook)
-            const int nRun = (kOneHook && nCyc <= 0) ? 1 : nCyc;
-            if (kOneHook || nCyc > 0) {
+            const int nRun = (ZSET && nCyc <= 0) ? 1 : nCyc;
+            if (ZSET || nCyc > 0) {
                 // ONE instance of the round in the kernel's code: the tile's first round carries the hook behind a
                 // wave-uniform flag (three inlined copies -- hook round, other rounds of the first cycle, rounds of the later
                 // cycles of a fused launch -- were 3 x 1400 instructions and a dozen register shuffles at every loop edge).
@@ -1091,7 +1015,7 @@ __device__ __forceinline__ void stream_body(
                     // (read per cycle through an opaque copy: a test of nCyc itself is invariant in this loop, and hipcc then
                     // makes two copies of the loop, round and all, one per outcome)
                     int live = nCyc;
-                    if (kOneHook) asm volatile("" : "+s"(live));
+                    if (ZSET) asm volatile("" : "+s"(live));
                     if (live > 0) cycle_begin(c);
 #ifdef CPF_STREAM_TIMELINE
                     tlVis = 0; tlRoundIdx = 0;
@@ -1111,7 +1035,7 @@ __device__ __forceinline__ void stream_body(
                     // a second copy of the round, which the comment above is about)
                     if constexpr (ZSET) {
                         _Pragma("clang loop unroll(disable)")
-                        do { round(hookDue, cycleStart, c); hookDue = false; cycleStart = false; } while (kMaskBusy ? busyM != 0ull : ballot64(busy) != 0ull);
+                        do { round(hookDue, cycleStart, c); hookDue = false; cycleStart = false; } while (busyM != 0ull);
                     } else
                     do { round(hookDue, cycleStart, c); hookDue = false; cycleStart = false; } while (ballot64(busy) != 0ull);
 #endif
@@ -1161,7 +1085,7 @@ __device__ __forceinline__ void stream_body(
             const D3 res = parked();
             if (ul <= rlim) {
                 (x + b)[ul] = res.x; (y + b)[ul] = res.y;
-                if (!zKeep) (z + b)[ul] = res.z;
+                if (!ZSET) (z + b)[ul] = res.z;
                 (cell + b)[ul] = rc;
             }
             if (STORE_VEL && ralive) {
@@ -1206,7 +1130,6 @@ __global__ __launch_bounds__(64, (StreamShape<false, STORE_VEL, STATS, LOOKUP>::
     int nCyc, uint32_t seed, MeshView m, unsigned long long* __restrict__ counters, StreamArgs sa) {
     stream_body<false, REFLECT, STORE_VEL, STATS, LOOKUP, false, true>(gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa, VertexField{});
 }
-#if CPF_FLAT_FACE_ASM
 // The headline's entry with the face blocks: the same body under a budget of 80 scalar registers in all, what the entry had with
 // the C++ face test.  Left alone the allocator takes 82 -- the miss mask, which is not live across a visit, gets a pair of its own
 // above the visit's instead of sharing one below -- and the budget costs no spill and no instruction.  (The attribute takes no
@@ -1219,7 +1142,6 @@ void step_kernel_stream_flat<true, false, false, kLookupFlatLoop>(
     int nCyc, uint32_t seed, MeshView m, unsigned long long* __restrict__ counters, StreamArgs sa) {
     stream_body<false, true, false, false, kLookupFlatLoop, false, true>(gid, vel, n, dt, sigma, step0, nCyc, seed, m, counters, sa, VertexField{});
 }
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // launcher: persistent grid sized by the occupancy of the instantiation
@@ -1266,11 +1188,10 @@ static hipError_t launch_stream_inst(hipStream_t st, double* x, double* y, doubl
     unsigned* nxt = ss.d_grab + (size_t)((ss.parity & 1) ^ 1) * kStreamGroups * kStreamCounterStride;
     if (R * kStreamGroups > ss.hitSpillWaves) R = ss.hitSpillWaves / kStreamGroups;      // (never: the area is sized for the chip)
     if (R < 1 || ss.d_hitSpill == nullptr) return hipErrorInvalidValue;
-    // (the flat instantiations only: every other one streams z whatever the caller says; "flat_z" 0: they stream it too)
-    // (ZS: the caller has decided just that, StepPlan::flat_body)
-    const bool zSettled = mode.flat && !VX && settled && ss.flatZ != 0;
-    if (ZS != zSettled && mode.flat && !VX) return hipErrorInvalidValue;
-    StreamArgs sa = {cur, nxt, (int)R, tpc, (unsigned)bigChunks, ss.debug, ss.d_hitSpill, zSettled ? 1 : 0, ss.zBad};
+    // a flat launch is the body without z exactly when the cloud's z is settled and "flat_z" is on (the caller's StepPlan::flat_body);
+    // every other kernel streams z whatever the caller says
+    if (mode.flat && !VX && ZS != (settled && ss.flatZ != 0)) return hipErrorInvalidValue;
+    StreamArgs sa = {cur, nxt, (int)R, tpc, (unsigned)bigChunks, ss.debug, ss.d_hitSpill, 0, ss.zBad};
     auto launch = [&](const auto&... tail) {       // StreamKernArgs' order; tail: what the kernel appends to it (the vertex kernel's VertexField)
         const dim3 grid((unsigned)(R * kStreamGroups));
         if (evStart != nullptr && evStop != nullptr)

@@ -87,7 +87,7 @@ __device__ __forceinline__ double kernarg_f64() {
     asm volatile("s_load_dwordx2 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "n"(BYTE_OFFSET) : "memory");
     return __longlong_as_double((long long)(((unsigned long long)r[1] << 32) | r[0]));
 }
-// THE LOOP LOOKUP IN HAND-WRITTEN ISA (the body without z, CPF_FLAT_LOOKUP_ASM in cpf_stream.hip).  The record cache's loop lookup:
+// THE LOOP LOOKUP IN HAND-WRITTEN ISA (the body without z: stream_body's loop lookup under ZSET, cpf_stream.hip).  The record cache's loop lookup:
 // one trip per distinct cell of the busy lanes `todo`.  The leader is the first set bit of `todo`, ck its cell; `same` are the
 // lanes in ck (every lane of the wave votes -- EXEC is whole here --, so a finished lane still standing in ck gets a slot number
 // nobody reads, as in the C++ loop); the slot is the first set bit of the compare of ck against the tag vector (lane k = the cell in slot k).
@@ -172,8 +172,9 @@ struct StreamArgs {
                            // each other (measured with 4-tile chunks throughout: the last wave 20 us after the median)
     int debug;             // diagnostics only (results are wrong): 1 = no stores, 2 = no loads after a wave's first tile
     double* hitSpill;      // kStreamHitSpillDoubles per workgroup: wall hit points beyond the wave's LDS pool
-    int zSettled;          // (flat walk only) z of every live particle is already a fixed point of the flat cycle: z is neither
-                           // loaded nor stored (cpf_walk.h "flat walk"; CPF_STEP_Z_SETTLED)
+    int kernargPad;        // unread, always 0: where the run-time "z is settled" flag stood until round 14.  Without it the kernarg
+                           // segment is 8 bytes shorter, the offsets of everything behind `sa` (the vertex kernel's VertexField, the
+                           // hidden arguments) move, and no kernel of cpf_stream.hip keeps its instructions (docs/experiments.md, round 14)
     unsigned* zBad;        // (flat walk that streams z) set to 1 by a wave that loads a live particle whose z is not finite: such
                            // a cloud is not called settled (cpf_walk.h "settled z"; StreamState::zBad, host memory the device writes)
 };

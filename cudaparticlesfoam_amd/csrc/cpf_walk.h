@@ -254,7 +254,7 @@ __device__ __forceinline__ void trace_lds6_record(const D3& P0, const D3& Pd, co
 // sees -- two FMAs per face that need not be issued, a vote and a branch per round that need not be taken, and no z in the walk.
 // (face_test<.., FLAT>; S.z is left alone: fma(dT, +-0, P0.z) is P0.z)
 //
-// SETTLED Z (CPF_STEP_Z_SETTLED, StreamArgs::zSettled).  What one flat cycle does to a live particle's z is a function f of z
+// SETTLED Z (CPF_STEP_Z_SETTLED: what admits a flat launch to the body without z, below).  What one flat cycle does to a live particle's z is a function f of z
 // alone: the advect gives Pn.z = z + dt * u.z with u.z == +-0 and dt finite (cpf_step_dev refuses any other), disp.z = Pn.z - z,
 // E.z = z + disp.z; the walk never moves S.z; a mirror about a side wall adds -2 sd * nz with nz == +-0 (a wall is only ever a
 // side face here, and sd is finite for finite z -- see "not settled" below for the others: a lane with a non-finite x or y never
@@ -283,8 +283,9 @@ __device__ __forceinline__ void trace_lds6_record(const D3& P0, const D3& Pd, co
 // pinned word the cloud's owner reads behind that launch, once, before the first launch that would leave z alone -- no pass
 // over the cloud), and flat launches keep streaming z for as long as one is reported.
 //
-// THE BODY WITHOUT Z (stream_body's ZSET, step_kernel_stream_flat: what a flat launch on a settled cloud runs).  The run-time flag
-// above ran the three-coordinate body with z = 0.0 in place of the z it did not load.  Every z term is then a product or a
+// THE BODY WITHOUT Z (stream_body's ZSET, step_kernel_stream_flat: what a flat launch on a settled cloud runs).  Round 7 ran
+// such a launch on the three-coordinate body behind a run-time flag, with z = 0.0 in place of the z it did not load (the flag went
+// in round 14: "no z" is the template parameter alone).  Every z term is then a product or a
 // sum of zeros, and dropping it gives the same bits in x, y and the cell, for every input:
 //   * advect, displacement, end point, move: z components only; x and y never read them;
 //   * the mirror: sd = dot3(plane, E) - w = fma(nz, E.z, t) - w with t = fma(ny, E.y, nx * E.x), nz == +-0, E.z == +-0.  The
@@ -306,7 +307,7 @@ __device__ __forceinline__ void trace_lds6_record(const D3& P0, const D3& Pd, co
 // = u up to the sign of a zero, which no comparison sees (E.z and P0.z are finite: a lane with a NaN or infinite end point is
 // never `clear`).  The exit point keeps its z: S = P0 + dT * Pd with the real Pd.z.  Same bits as trace_lds6(..., zNever = true).
 //
-// THE FACE BLOCK IN HAND-WRITTEN ISA (FACE_ASM; the body without z only: step_kernel_stream_flat, CPF_FLAT_FACE_ASM).  The C++ face
+// THE FACE BLOCK IN HAND-WRITTEN ISA (FACE_ASM; the body without z only: step_kernel_stream_flat, stream_body's kFaceAsm).  The C++ face
 // test computes every predicate into a scalar register pair and combines them on the scalar ALU -- a vote of three compares, a
 // scalar compare and a branch, then the exact predicate's four compares, four scalar operations, a saveexec and a branch, then
 // two more compares, an AND and a saveexec: 14 scalar-issue instructions per face with a candidate lane, in a kernel whose

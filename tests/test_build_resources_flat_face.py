@@ -1,5 +1,5 @@
-"""CPU: the hand-written face block of the flat walk's body without z (csrc/cpf_walk.h, ``face_accept_flat_asm``; the knob is
-``CPF_FLAT_FACE_ASM`` in csrc/cpf_stream.hip) as it stands in the code object's listing -- one cross-compile of cpf_stream.hip to
+"""CPU: the hand-written face block of the flat walk's body without z (csrc/cpf_walk.h, ``face_accept_flat_asm``; called from
+``stream_body`` under ``ZSET`` in csrc/cpf_stream.hip) as it stands in the code object's listing -- one cross-compile of cpf_stream.hip to
 gfx950 assembly with the product's flags (tools/resource_usage.py).
 
 The headline's entry, ``step_kernel_stream_flat<true, false, false, 8>``:

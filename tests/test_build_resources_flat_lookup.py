@@ -1,5 +1,5 @@
-"""CPU: the round's bookkeeping around the face blocks of the flat walk's body without z (csrc/cpf_stream.hip: CPF_FLAT_LOOKUP_ASM,
-CPF_FLAT_VOTE_MASK, CPF_FLAT_WALL_J) as it stands in the code object's listing -- one cross-compile of
+"""CPU: the round's bookkeeping around the face blocks of the flat walk's body without z (csrc/cpf_stream.hip, stream_body under ZSET:
+the lookup trip in hand-written ISA, the vote from masks, the j test in the wall branch) as it stands in the code object's listing -- one cross-compile of
 cpf_stream.hip to gfx950 assembly with the product's flags (tools/resource_usage.py), counted with ``classes()`` of
 tests/test_build_resources_flat_face.py.
 

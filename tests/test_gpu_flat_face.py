@@ -1,4 +1,4 @@
-"""GPU: the hand-written face block of the flat walk's body without z (csrc/cpf_walk.h, face_accept_flat_asm; CPF_FLAT_FACE_ASM),
+"""GPU: the hand-written face block of the flat walk's body without z (csrc/cpf_walk.h, face_accept_flat_asm),
 BIT FOR BIT in x, y and the cell against two statements of the same cycle:
 
   1. the CPU statement, oracle/cellwalk.c (CellWalk.step_given(xi = None) through tests/browniancycle.py, run_cpu);

@@ -1,10 +1,10 @@
-"""GPU: the round's bookkeeping around the face blocks of the flat walk's body without z (csrc/cpf_stream.hip: CPF_FLAT_LOOKUP_ASM,
-the loop lookup's trip as a hand-written block, csrc/cpf_stream_ops.h lookup_loop_asm; CPF_FLAT_VOTE_MASK and CPF_FLAT_WALL_J, the
+"""GPU: the round's bookkeeping around the face blocks of the flat walk's body without z (csrc/cpf_stream.hip, stream_body under ZSET:
+the loop lookup's trip as a hand-written block, csrc/cpf_stream_ops.h lookup_loop_asm; outcome_flat, the
 visit's outcome applied behind the busy lanes' region and the j test in the wall branch), BIT FOR BIT in x, y, the
 cell and the stored velocity against two statements of the same cycle, the way tests/test_gpu_flat_face.py does it:
 
   1. the CPU statement, oracle/cellwalk.c (CellWalk.step_given(xi = None) through tests/browniancycle.py, run_cpu);
-  2. the same library with option "flat_z" 0: the three-coordinate body, which none of the three knobs touches.
+  2. the same library with option "flat_z" 0: the three-coordinate body, which none of the three touches.
 
 What runs: cpf_step on the context's own cloud, never re-sorted.  One cycle of dt = 0 settles z; the launches behind it -- one
 cycle, three cycles, and launches of zero cycles between and behind them, all with CPF_STEP_FUSE_CYCLES -- report
@@ -15,7 +15,7 @@ count is the cloud's size, frozen slots included, and "stream_lookup" cannot nam
 tests/test_gpu_flat_face.py, from 512.  A cloud of 1, 63, 64, 65 or 200 particles is therefore that many particles -- ordered by
 cell, in the cloud's first tiles -- followed by 512 frozen slots: a first tile with one busy lane, tiles one lane short of full,
 full, one lane over, partial last tiles of 1, 63, 0, 1 and 8 lanes, and always far fewer tiles than the chip has waves.  One
-case runs the fixed compare (9) on 200 particles without the filler: the knobs other than the lookup's are in that entry too.
+case runs the fixed compare (9) on 200 particles without the filler: what is not the lookup's is in that entry too.
 
 The other shapes, all through the loop lookup:
   * every tile in one cell (four tiles per cell): one trip per round, a hit from the second tile on;
