@@ -117,6 +117,15 @@ constexpr int kKernArgStep0 = (int)offsetof(StreamKernArgs, step0), kKernArgSeed
 #ifndef CPF_STREAM_FLAT_ZERO_SKIP
 #define CPF_STREAM_FLAT_ZERO_SKIP 0
 #endif
+// (the body without z) the exit point of a visit without its select: S = P0 + dTmin * Pd for every visiting lane, nobody reads it
+// of a lane that accepted no face (cpf_walk.h, trace_lds4_flat's EXIT_ALWAYS has the argument).  0: the select, for A/B builds
+#ifndef CPF_STREAM_FLAT_EXIT_ALWAYS
+#define CPF_STREAM_FLAT_EXIT_ALWAYS 1
+#endif
+// (the body without z) the counted wait behind a round's record requests as one hand-written block.  0: the C++ chain, for A/B builds
+#ifndef CPF_STREAM_FLAT_WAIT_ASM
+#define CPF_STREAM_FLAT_WAIT_ASM 1
+#endif
 #ifndef CPF_STREAM_SLOTS_BOX
 #define CPF_STREAM_SLOTS_BOX 9
 #endif
@@ -272,6 +281,10 @@ __device__ __forceinline__ void stream_body(
     // (v_cmpx) instead of combined on the scalar ALU (cpf_walk.h, face_accept_flat_asm; the block has no zero-denominator vote).
     // Round 12: +4.4 % / +5.3 % on the headline against the C++ face test
     constexpr bool kFaceAsm = ZSET && CPF_STREAM_FLAT_ZERO_SKIP == 0;
+    // (ZSET, round 15) ... and the exit point behind them computed for every visiting lane, not selected: a compare, four selects
+    // and the initialisation of `best` per visit.  (ZSET, round 15) the counted wait as one block: cpf_stream_ops.h, wait_vmcnt_flat
+    constexpr bool kExitAlways = kFaceAsm && CPF_STREAM_FLAT_EXIT_ALWAYS != 0;
+    constexpr bool kWaitAsm = ZSET && CPF_STREAM_FLAT_WAIT_ASM != 0;
     // the lane's parked end point / parked result (sE): a pair without z
     auto park = [&](const D3& e) __attribute__((always_inline)) {
         sE[0][lane] = e.x; sE[1][lane] = e.y;
@@ -699,7 +712,8 @@ __device__ __forceinline__ void stream_body(
 #endif
                 if (nJobs != 0) {
                     // the requested records are older than everything the hook issued: wait for exactly them
-                    if (ZSET) {                          // three stores or none, the prefetch's two loads or none
+                    if (kWaitAsm) wait_vmcnt_flat(younger);          // (the chain below as one hand-written block, cpf_stream_ops.h)
+                    else if (ZSET) {                     // three stores or none, the prefetch's two loads or none
                         if (younger == 5) wait_vmcnt<5>();
                         else if (younger == 3) wait_vmcnt<3>();
                         else if (younger == 2) wait_vmcnt<2>();
@@ -858,7 +872,7 @@ __device__ __forceinline__ void stream_body(
                             // measured 1-2 % there, nothing with the Brownian kick, and a loss where faces drop out for
                             // zero denominators)
                             if (BOX) next = trace_box<!BROWNIAN, mixed>(S_, E, cur, rec, token, outSlot);
-                            else if (FLAT) next = trace_lds4_flat<(CPF_STREAM_FLAT_ZERO_SKIP != 0), false, kFaceAsm>(S_, E, cur, rec, token, outSlot);
+                            else if (FLAT) next = trace_lds4_flat<(CPF_STREAM_FLAT_ZERO_SKIP != 0), false, kFaceAsm, kExitAlways>(S_, E, cur, rec, token, outSlot);
                             else if (CPF_STREAM_FLAT_KICK && BROWNIAN && !mixed && flatKick && !zUnclear)
                             next = trace_lds4_flat<false, true>(S_, E, cur, rec, token, outSlot);     // (cpf_walk.h: flat walk under the kick)
                             else
@@ -926,7 +940,7 @@ __device__ __forceinline__ void stream_body(
                             // test of the LDS visit.  Same bits as the six-face walk with z = 0 (cpf_walk.h "the body without z").
                             // (Round 9: this, the branch weights above and the zero-cycle launch through the round's hook take a sixth of
                             // the code out and nothing off the clock)
-                            else if (ZSET) next = trace_lds4_flat<false, false, kFaceAsm>(S_, E, cur, rec, token, outSlot);
+                            else if (ZSET) next = trace_lds4_flat<false, false, kFaceAsm, kExitAlways>(S_, E, cur, rec, token, outSlot);
                             else if (!gBig)
                             next = trace_fixed<6, false, mixed, kGatherAhead>(S_, E, cur, rec, reinterpret_cast<const int32_t*>(rec + 7), token, outSlot, 0);
                             if (STATS) ++st.hops;

@@ -145,6 +145,32 @@ __device__ __forceinline__ void add_lanes(int& h, unsigned long long lanes) {
 }
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory"); }
+// The body without z's counted wait as one block: wait until all but the `younger` latest vector-memory operations are done, for the
+// counts its hook can leave behind a round's record requests -- 5 (three stores and the prefetch's two loads), 3, 2 -- and for
+// everything otherwise.  s_waitcnt takes its count as an immediate, so this is a chain of tests; hipcc builds the if / else chain of
+// wait_vmcnt<N>() as flags in scalar register pairs that it tests through VCC, 15 to 22 scalar-issue instructions on the way to one
+// wait (round 15).  Here: two for 5, four for 3, six for 2 and for the rest, each plus its wait and at most one branch out.
+__device__ __forceinline__ void wait_vmcnt_flat(int younger) {
+    asm volatile(
+        "s_cmp_lg_u32 %[y], 5\n\t"
+        "s_cbranch_scc1 .Lcpf_wait_a_%=\n\t"
+        "s_waitcnt vmcnt(5)\n\t"
+        "s_branch .Lcpf_wait_done_%=\n"
+        ".Lcpf_wait_a_%=:\n\t"
+        "s_cmp_lg_u32 %[y], 3\n\t"
+        "s_cbranch_scc1 .Lcpf_wait_b_%=\n\t"
+        "s_waitcnt vmcnt(3)\n\t"
+        "s_branch .Lcpf_wait_done_%=\n"
+        ".Lcpf_wait_b_%=:\n\t"
+        "s_cmp_lg_u32 %[y], 2\n\t"
+        "s_cbranch_scc1 .Lcpf_wait_c_%=\n\t"
+        "s_waitcnt vmcnt(2)\n\t"
+        "s_branch .Lcpf_wait_done_%=\n"
+        ".Lcpf_wait_c_%=:\n\t"
+        "s_waitcnt vmcnt(0)\n"
+        ".Lcpf_wait_done_%=:"
+        : : [y] "s"(younger) : "scc", "memory");
+}
 
 // Work distribution.  ONE global chunk counter does not work: returning atomics on one address are served at about
 // one per 12 ns chip-wide (measured: 78 125 grabs = 0.97 ms for a zero-cycle launch), and every wave's next grab

@@ -367,12 +367,37 @@ __device__ __forceinline__ void record_pair_flat_asm(double4& pa, double4& pb, c
     face_accept_flat_asm<SLOT>(denA, fdA, b.x, token, dTmin, next, best);
     face_accept_flat_asm<SLOT + 1>(denB, fdB, b.y, token, dTmin, next, best);
 }
-template <bool ZERO_SKIP, bool KEEP_Z = false, bool FACE_ASM = false>
+//
+// THE EXIT POINT WITHOUT ITS SELECT (EXIT_ALWAYS, round 15; the body without z only).  `if (best >= 0) { S = P0 + dTmin * Pd; outSlot =
+// best; }` is a compare and four selects per visit, and `best = -1` a move, for the sake of the lanes that accepted no face: theirs
+// keep S and outSlot.  In stream_body's ZSET round nobody reads either of such a lane, so the body computes S = fma(dTmin, Pd, P0)
+// with dTmin still 2.0 for them, leaves `best` unset until a face is accepted, and hands it out as it is.  The argument:
+//   * next and best are written together, by an accepted face only (face_accept_flat_asm: three moves under one EXEC), so a lane
+//     that accepted none returns next == cur.  outcome_flat ends it (endsM): its busy bit is cleared, it makes no further visit in this
+//     cycle, and cycle_end -- which every lane with cur >= 0 runs, and a visiting lane was busy, so cur >= 0, and ending leaves cur as it
+//     was -- writes S_ = E, or hit + (E - hit) with the PARKED hit point, before anything reads S_: park_hit(S_) and the mirror read
+//     it in the wall branch (an accepted wall face), the next visit's P0 belongs to a lane that is still busy (it crossed or was
+//     mirrored: an accepted face).  outSlot is read for the wall's plane alone, under next < 0: an accepted face (next == cur >= 0
+//     otherwise).  No load is issued from an unset outSlot: the read stands inside the region of the lanes with next < 0.
+//   * hop cap: a lane reaches it by crossing -- an accepted face, a proper S_; it is done and cycle_end overwrites S_ all the same.
+//   * five bounces: every bounce is an accepted wall face; park_hit and the mirror read a proper S_, the sixth visit never happens.
+//   * a wall without reflection: accepted; S_ is not read (no park_hit), j = kMaxReflect, and cycle_end (REFLECT false) writes S_ = E.
+//   * fused cycles: cycle_end closes every cycle of the launch, and the next cycle's first visit starts from the S_ it wrote; the
+//     tile's result is that S_ too.  A launch of zero cycles has no busy lane and makes no visit.
+//   * non-finite Pd (x, y or the record's velocity not finite): every comparison of the face block that reads den, fd or dT is an
+//     ordered one and fails, no face is accepted, next == cur: the first case.  S_ holds a NaN until cycle_end writes E over it -- the
+//     bits it wrote before, for E and the parked hit point do not come from S_ of this visit.
+//   * lanes that are not visiting -- not busy, or left without a slot in a round that is no gather round -- are outside the EXEC
+//     mask of the region the visit stands in: their S_ is not written at all.
+// (Round 13 measured the select under a narrowed EXEC instead: 9 vector instructions fewer, 4 scalar more, no gain.)
+template <bool ZERO_SKIP, bool KEEP_Z = false, bool FACE_ASM = false, bool EXIT_ALWAYS = false>
 __device__ __forceinline__ int trace_lds4_flat(D3& S, const D3& E, int cur, const double4* rec, int token, int& outSlot) {
     static_assert(!(FACE_ASM && (KEEP_Z || ZERO_SKIP)), "the hand-written face block is the body without z's, without the zero-denominator vote");
+    static_assert(!EXIT_ALWAYS || FACE_ASM, "the exit point without its select: argued for the body without z and its face block");
     const D3 P0 = S;
     const D3 Pd = {E.x - P0.x, E.y - P0.y, KEEP_Z ? E.z - P0.z : 0.0};
     int next = cur, best = -1;
+    if constexpr (EXIT_ALWAYS) asm volatile("" : "=v"(best));          // (unset: no move; read only where a face block has written it)
     double dTmin = 2.0;
     const int2* nb = reinterpret_cast<const int2*>(rec + 7);
     if constexpr (FACE_ASM) {
@@ -382,7 +407,7 @@ __device__ __forceinline__ int trace_lds4_flat(D3& S, const D3& E, int cur, cons
     { double4 p0 = rec[0], p1 = rec[1]; record_pair<ZERO_SKIP, false, true>(p0, p1, nb[0], 0, P0, Pd, token, dTmin, next, best); }
     { double4 p2 = rec[2], p3 = rec[3]; record_pair<ZERO_SKIP, false, true>(p2, p3, nb[1], 2, P0, Pd, token, dTmin, next, best); }
     }
-    if (best >= 0) {
+    if (EXIT_ALWAYS || best >= 0) {
         if (KEEP_Z) S = axpy(dTmin, Pd, P0);
         else { S.x = fma(dTmin, Pd.x, P0.x); S.y = fma(dTmin, Pd.y, P0.y); }
         outSlot = best;
