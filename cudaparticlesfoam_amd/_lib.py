@@ -154,6 +154,12 @@ SIGNATURES = {
     "cpf_get_recycle_counts": (_int, [_ctx, _vp]),
     "cpf_recycle_reset_counts": (_int, [_ctx]),
     "cpf_respawn_positions_host": (_int, [_u32, _vp, _i64, _u32, _vp, _vp, _vp]),
+    "cpf_source_table_host": (_int, [_vp, _vp, _vp, _dbl, _dbl, _i64, _vp, _vp, C.POINTER(_i64)]),
+    "cpf_source_positions_host": (_int, [_u32, _vp, _i64, _u32, _vp, _vp, _i64, _vp]),
+    "cpf_set_source_triangles": (_int, [_ctx, _vp, _vp, _vp, _dbl, _dbl, _i64]),
+    "cpf_get_source_table": (_int, [_ctx, _vp, _vp, C.POINTER(_i64)]),
+    "cpf_respawn_source": (_int, [_ctx, _i64]),
+    "cpf_respawn_source_dev": (_int, [_ctx, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _u32]),
     "cpf_age_enable": (_int, [_ctx, _i32, _i32]),
     "cpf_age_disable": (_int, [_ctx]),
     "cpf_age_sample": (_int, [_ctx]),

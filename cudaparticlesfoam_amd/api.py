@@ -292,6 +292,30 @@ class Context:
     def recycle_reset_counts(self):
         self._ck(self.lib.cpf_recycle_reset_counts(self.h))
 
+    # -- patch source: dead slots respawn on weighted triangles (include/cpf.h "patch source")
+    def set_source_triangles(self, tri, weights=None, depth=(0.0, 0.0)):
+        """The source: triangles [m][3][3] (``PolyMesh.face_triangles`` gives a patch's), weights [m] (None: the areas;
+        ``inflow_weights`` gives the flux-weighted ones) and the depth range, (d0, d1) for all or [m][2]; no triangle clears it."""
+        t, w, dep, d0, d1 = _source_args(tri, weights, depth)
+        self._ck(self.lib.cpf_set_source_triangles(self.h, _ptr(t) if t.size else None, _ptr(w), _ptr(dep), d0, d1, t.shape[0]))
+
+    def source_table(self):
+        """(rec [k][16], hi [k] uint32) of the source as built (cpf_source_table_host's layout); k == 0 without a source."""
+        k = C.c_int64(0)
+        self._ck(self.lib.cpf_get_source_table(self.h, None, None, C.byref(k)))
+        rec, hi = np.empty((k.value, 16), np.float64), np.empty(k.value, np.uint32)
+        if k.value:
+            self._ck(self.lib.cpf_get_source_table(self.h, _ptr(rec), _ptr(hi), C.byref(k)))
+        return rec, hi
+
+    def respawn_source(self, max_count: int = -1):
+        """Up to ``max_count`` (< 0: all) dead slots of the context-owned cloud, in array order, get a fresh position on the source
+        and are located; the cloud's epoch counter -- ``respawn_box``'s -- goes up by one."""
+        self._ck(self.lib.cpf_respawn_source(self.h, int(max_count)))
+
+    def respawn_source_dev(self, x, y, z, cell, gid, n, max_count: int = -1, epoch: int = 0):
+        self._ck(self.lib.cpf_respawn_source_dev(self.h, x, y, z, cell, gid, n, int(max_count), int(epoch)))
+
     # -- tracer age: residence times at the sink, the mean-age field (include/cpf.h "tracer age")
     def age_enable(self, bin_cycles: int, n_bins: int):
         """Turns age tracking of the context-owned cloud on (or starts it anew): everybody is born now; ``n_bins`` residence-time
@@ -415,6 +439,58 @@ def respawn_positions_host(seed: int, gid, epoch: int, lower, upper, n: Optional
     if st != L.CPF_OK:
         raise L.CpfError(st, "cpf_respawn_positions_host")
     return xyz
+
+
+def _source_args(tri, weights, depth):
+    t = np.ascontiguousarray(tri, dtype=np.float64).reshape(-1, 3, 3)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if w is not None and w.size != t.shape[0]:
+        raise ValueError("source: %d weights for %d triangles" % (w.size, t.shape[0]))
+    d = np.ascontiguousarray(depth, dtype=np.float64)
+    if d.shape == (2,):
+        return t, w, None, float(d[0]), float(d[1])
+    if d.shape != (t.shape[0], 2):
+        raise ValueError("source: depth is (d0, d1) or [m][2]")
+    return t, w, d, 0.0, 0.0
+
+
+def source_table_host(tri, weights=None, depth=(0.0, 0.0)):
+    """The table ``Context.set_source_triangles`` would build and upload, on the host alone (cpf_source_table_host): (rec [k][16],
+    hi [k] uint32) of the k triangles kept; rec[:, 14] is their index in ``tri``."""
+    lib = L.load()
+    t, w, dep, d0, d1 = _source_args(tri, weights, depth)
+    m = t.shape[0]
+    rec, hi, k = np.empty((m, 16), np.float64), np.empty(m, np.uint32), C.c_int64(0)
+    st = lib.cpf_source_table_host(_ptr(t) if m else None, _ptr(w), _ptr(dep), d0, d1, m, _ptr(rec), _ptr(hi), C.byref(k))
+    if st != L.CPF_OK:
+        raise L.CpfError(st, "cpf_source_table_host")
+    return rec[:k.value].copy(), hi[:k.value].copy()
+
+
+def source_positions_host(seed: int, gid, epoch: int, rec, hi, n: Optional[int] = None) -> np.ndarray:
+    """Where ``respawn_source`` puts the particles ``gid`` (None: 0 .. n-1) at ``epoch`` under ``seed`` on the table (rec, hi):
+    [n][3], computed on the host alone from the kernel's own text (cpf_source_positions_host)."""
+    lib = L.load()
+    g = None if gid is None else np.ascontiguousarray(gid, dtype=np.int64).reshape(-1)
+    n = int(n) if g is None else g.size
+    r = np.ascontiguousarray(rec, dtype=np.float64).reshape(-1, 16)
+    h = np.ascontiguousarray(hi, dtype=np.uint32).reshape(-1)
+    xyz = np.empty((n, 3), np.float64)
+    st = lib.cpf_source_positions_host(seed & 0xFFFFFFFF, _ptr(g), n, int(epoch) & 0xFFFFFFFF, _ptr(r), _ptr(h), h.size, _ptr(xyz))
+    if st != L.CPF_OK:
+        raise L.CpfError(st, "cpf_source_positions_host")
+    return xyz
+
+
+def inflow_weights(mesh, U, tri, face_of_tri) -> np.ndarray:
+    """Flux weights of the triangles of ``mesh.face_triangles``: area * max(0, -U_owner . n_out), n_out the triangle's right-hand
+    unit normal (outward on a boundary face) and U_owner the velocity of the face's owner cell."""
+    t = np.asarray(tri, dtype=np.float64).reshape(-1, 3, 3)
+    c = np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0])
+    length = np.sqrt((c * c).sum(1))
+    n_out = c / np.where(length > 0, length, 1.0)[:, None]
+    u = np.asarray(U, dtype=np.float64)[np.asarray(mesh.owner)[np.asarray(face_of_tri, dtype=np.int64)]]
+    return 0.5 * length * np.maximum(0.0, -(u * n_out).sum(1))
 
 
 def build_mesh_tables_host(mesh):
@@ -605,6 +681,11 @@ class CudaParticles:
     sink cell are absorbed (``Context.sink_apply``) and every dead slot is respawned in the source box
     (``Context.respawn_box``), before the occupancy sample if one is due: an inlet and an outlet at constant particle count.
 
+    With ``sourceTriangles`` ([m][3][3]; ``mesh.face_triangles(mesh.patch_faces("inlet"))``) the dead slots are respawned on those
+    triangles instead (``Context.respawn_source``) and ``sourceBox`` is unused: ``sourceWeights`` ([m]; default: the areas,
+    ``inflow_weights`` gives the flux-weighted ones) chooses the triangle and ``sourceDepth`` ((d0, d1) or [m][2]; default 0)
+    is the range of depths behind it.  The weights do not follow ``advect(U=...)``.
+
     Two more, also this library's own: ``ageBins`` (default 0 = off) and ``ageBinCycles`` (default: ``recycleInterval``, else 1).
     When ``ageBins`` is positive, age tracking (``Context.age_enable``) starts once the cloud is located: every absorption adds a
     residence time to ``rtd()``, and wherever an occupancy sample is taken the age field is sampled too, after recycling, for
@@ -626,6 +707,9 @@ class CudaParticles:
         self.recycleInterval = int(d.get("recycleInterval", 0))         # this library's own keys, like occupancyInterval
         self.sinkCells = d.get("sinkCells", None)
         self.sourceBox = d.get("sourceBox", self.seedingBox)
+        self.sourceTriangles = d.get("sourceTriangles", None)
+        self.sourceWeights = d.get("sourceWeights", None)
+        self.sourceDepth = d.get("sourceDepth", (0.0, 0.0))
         self.ageBins = int(d.get("ageBins", 0))
         self.ageBinCycles = int(d.get("ageBinCycles", self.recycleInterval if self.recycleInterval > 0 else 1))
         # hard-coded switches of the fragment (src/initCuda.H:64-72)
@@ -642,6 +726,8 @@ class CudaParticles:
         self.ctx.set_velocity(U)
         if self.recycleInterval > 0 and self.sinkCells is not None:
             self.ctx.set_sink_cells(self.sinkCells)
+        if self.recycleInterval > 0 and self.sourceTriangles is not None:
+            self.ctx.set_source_triangles(self.sourceTriangles, self.sourceWeights, self.sourceDepth)
         if positions is not None:            # parity runs inject positions
             self.ctx.set_particles(positions)
             self.numParticles = int(np.asarray(positions).shape[0])
@@ -694,7 +780,10 @@ class CudaParticles:
             done += chunk
             if self.recycleInterval > 0 and self.step % self.recycleInterval == 0:
                 self.ctx.sink_apply()
-                self.ctx.respawn_box(self.sourceBox[0], self.sourceBox[1], -1)
+                if self.sourceTriangles is not None:
+                    self.ctx.respawn_source(-1)
+                else:
+                    self.ctx.respawn_box(self.sourceBox[0], self.sourceBox[1], -1)
             if self.occupancyInterval > 0 and self.step % self.occupancyInterval == 0:
                 self.ctx.occupancy_sample()
                 if self.ageBins > 0:

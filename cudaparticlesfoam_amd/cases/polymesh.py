@@ -58,6 +58,31 @@ class PolyMesh:
             cells.append(np.asarray(self.owner[start:start + size], dtype=np.int64))
         return np.unique(np.concatenate(cells)).astype(np.int32)
 
+    def patch_faces(self, *names: str) -> np.ndarray:
+        """Face ids of the named boundary patches, in the order given (e.g. the faces of an inlet)."""
+        by_name = {name: (start, size) for (name, _, start, size) in self.patches}
+        faces = [np.empty(0, np.int64)]
+        for name in names:
+            if name not in by_name:
+                raise KeyError("patch_faces: no patch %r (the mesh has %s)" % (name, sorted(by_name)))
+            start, size = by_name[name]
+            faces.append(np.arange(start, start + size, dtype=np.int64))
+        return np.concatenate(faces).astype(np.int32)
+
+    def face_triangles(self, faces) -> Tuple[np.ndarray, np.ndarray]:
+        """The fan triangles (f[0], f[k], f[k+1]), k = 1 .. n-2, of the given faces, face by face: (tri [m][3][3],
+        face_of_tri [m] int32).  It is the triangulation of ``tet_decomposition`` and of the walk's derived cells; a triangle's
+        right-hand normal is its face's (outward on the boundary)."""
+        fo = self.face_offsets.astype(np.int64)
+        fv = self.face_verts.astype(np.int64)
+        tri, of = [], []
+        for f in np.asarray(faces, dtype=np.int64).reshape(-1):
+            loop = fv[fo[f]:fo[f + 1]]
+            for k in range(1, loop.size - 1):
+                tri.append(self.points[[loop[0], loop[k], loop[k + 1]]])
+                of.append(f)
+        return (np.ascontiguousarray(tri, dtype=np.float64).reshape(-1, 3, 3), np.asarray(of, dtype=np.int32))
+
     # ------------------------------------------------------- derived topology
     def cell_faces(self) -> Tuple[np.ndarray, np.ndarray]:
         """CSR (offsets, faces) of ``mesh.cells()`` in ``primitiveMesh::calcCells`` order."""

@@ -59,6 +59,12 @@ struct Mesh {
     int64_t occupancySamples = 0;           // samples added since the last reset
     // recycling (cpf_set_sink_cells; cpf_recycle.hip): the sink set belongs to the mesh and goes with it
     DevBuf<uint32_t> sinkMask;              // one bit per DERIVED cell, ceil(host.nCells / 32) words; null: no sink set
+    // patch source (cpf_set_source_triangles; cpf_inlet.hip): it belongs to the mesh too
+    DevBuf<double> sourceRec;               // [sourceKept][16] triangle records; null: no source
+    DevBuf<uint32_t> sourceHi;              // [sourceKept] bounds, padded with 0xFFFFFFFF to a multiple of 4 entries
+    int64_t sourceKept = 0;
+    std::vector<double> sourceRecHost;      // the table as built (cpf_get_source_table)
+    std::vector<uint32_t> sourceHiHost;
 };
 
 // "VertexVelocity" advect only: the tet decomposition and one velocity per tet-mesh vertex.  It belongs to the mesh it was made
@@ -1528,6 +1534,169 @@ int cpf_respawn_positions_host(uint32_t seed, const int64_t* gid, int64_t n, uin
                                const double upper[3], double* xyz) {
     if (n < 0 || !lower || !upper || (n > 0 && !xyz)) return CPF_ERR_ARG;
     for (int64_t i = 0; i < n; ++i) cpf::respawn_position(seed, (uint64_t)(gid ? gid[i] : i), epoch, lower, upper, xyz + 3 * i);
+    return CPF_OK;
+}
+
+// ---- patch source: dead slots respawn on weighted triangles (cpf_inlet.hip; the position: cpf_philox.h) ---------------------
+int cpf_source_table_host(const double* tri, const double* weight, const double* depth, double d0, double d1, int64_t n,
+                          double* rec, uint32_t* hi, int64_t* nKept) {
+    if (!nKept || n < 0 || (n > 0 && !tri)) return CPF_ERR_ARG;
+    *nKept = 0;
+    if (!depth && !(std::isfinite(d0) && std::isfinite(d1) && d0 <= d1)) return CPF_ERR_ARG;
+    // per triangle, every operation rounded on its own: e1 = B - A, e2 = C - A, c = e1 x e2, len = sqrt(c.c)
+    struct Geo { double e1[3], e2[3], c[3], len; };
+    const auto geometry = [tri](int64_t t) {
+        const double *A = tri + 9 * t, *B = A + 3, *C = A + 6;
+        Geo g;
+        for (int a = 0; a < 3; ++a) { g.e1[a] = B[a] - A[a]; g.e2[a] = C[a] - A[a]; }
+        for (int a = 0; a < 3; ++a) {
+            const int b = (a + 1) % 3, d = (a + 2) % 3;
+            const double p = g.e1[b] * g.e2[d], q = g.e1[d] * g.e2[b];
+            g.c[a] = p - q;
+        }
+        const double xx = g.c[0] * g.c[0], yy = g.c[1] * g.c[1], zz = g.c[2] * g.c[2];
+        const double xy = xx + yy;
+        g.len = std::sqrt(xy + zz);
+        return g;
+    };
+    struct Kept { int64_t t; double sum; };                // a kept triangle and the running sum C_t of the kept weights
+    std::vector<Kept> kept;
+    double sum = 0.0;
+    for (int64_t t = 0; t < n; ++t) {
+        if (depth && !(std::isfinite(depth[2 * t]) && std::isfinite(depth[2 * t + 1]) && depth[2 * t] <= depth[2 * t + 1]))
+            return CPF_ERR_ARG;
+        const double len = geometry(t).len;
+        const double area = len / 2.0;
+        const double w = weight ? weight[t] : area;
+        if (!(std::isfinite(w) && w >= 0.0)) return CPF_ERR_ARG;
+        if (len == 0.0 || w == 0.0) continue;
+        if (!std::isfinite(len)) return CPF_ERR_ARG;
+        sum = sum + w;
+        kept.push_back({t, sum});
+    }
+    if (kept.empty() || !std::isfinite(sum)) return CPF_ERR_ARG;
+    // b_t = floor(C_t / C_last * 2^32), the last one 2^32; a triangle whose bound is its predecessor's has a share below 2^-32
+    int64_t m = 0;
+    uint64_t before = 0;
+    const uint64_t full = (uint64_t)1 << 32;
+    for (size_t i = 0; i < kept.size(); ++i) {
+        const Kept& k = kept[i];
+        const double share = k.sum / sum;
+        uint64_t b = i + 1 == kept.size() ? full : (uint64_t)std::floor(share * 4294967296.0);
+        if (b > full) b = full;
+        if (b == before) continue;
+        before = b;
+        if (m >= ((int64_t)1 << 24)) return CPF_ERR_ARG;
+        if (hi) hi[m] = (uint32_t)(b - 1);
+        if (rec) {
+            double* r = rec + cpf::kSourceDoubles * m;
+            const double* A = tri + 9 * k.t;
+            const Geo g = geometry(k.t);
+            for (int a = 0; a < 3; ++a) { r[a] = A[a]; r[3 + a] = g.e1[a]; r[6 + a] = g.e2[a]; r[9 + a] = -g.c[a] / g.len; }
+            const double lo = depth ? depth[2 * k.t] : d0, up = depth ? depth[2 * k.t + 1] : d1;
+            r[12] = lo; r[13] = up - lo; r[14] = (double)k.t; r[15] = 0.0;
+        }
+        ++m;
+    }
+    *nKept = m;
+    return CPF_OK;
+}
+
+int cpf_source_positions_host(uint32_t seed, const int64_t* gid, int64_t n, uint32_t epoch, const double* rec, const uint32_t* hi,
+                              int64_t nKept, double* xyz) {
+    if (n < 0 || !rec || !hi || nKept <= 0 || nKept > ((int64_t)1 << 24) || hi[nKept - 1] != 0xFFFFFFFFu || (n > 0 && !xyz))
+        return CPF_ERR_ARG;
+    for (int64_t i = 0; i < n; ++i) {
+        uint32_t c[4];
+        cpf::source_words(seed, (uint64_t)(gid ? gid[i] : i), epoch, c);
+        const int t = cpf::source_pick(hi, (int)nKept, c[0]);
+        cpf::source_point(c, rec + cpf::kSourceDoubles * (int64_t)t, xyz + 3 * i);
+    }
+    return CPF_OK;
+}
+
+int cpf_set_source_triangles(cpf_context* ctx, const double* tri, const double* weight, const double* depth, double d0, double d1,
+                             int64_t n) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_set_source_triangles: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, n >= 0 && (tri || n == 0), CPF_ERR_ARG, "cpf_set_source_triangles: bad arguments");
+    std::vector<double> rec((size_t)n * cpf::kSourceDoubles);
+    std::vector<uint32_t> hi((size_t)n + 4);
+    int64_t kept = 0;
+    if (n > 0)
+        CPF_REQUIRE(ctx, cpf_source_table_host(tri, weight, depth, d0, d1, n, rec.data(), hi.data(), &kept) == CPF_OK, CPF_ERR_ARG,
+                    "cpf_set_source_triangles: weights must be finite and >= 0, depths finite with d0 <= d1, and between 1 and 2^24 "
+                    "triangles must keep a share of at least 2^-32");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass over the old table may still be running)
+    ctx->mesh.sourceRec = DevBuf<double>{};
+    ctx->mesh.sourceHi = DevBuf<uint32_t>{};
+    ctx->mesh.sourceKept = 0;
+    ctx->mesh.sourceRecHost.clear();
+    ctx->mesh.sourceHiHost.clear();
+    if (n == 0) return CPF_OK;
+    rec.resize((size_t)kept * cpf::kSourceDoubles);
+    const size_t padded = ((size_t)kept + 3) / 4 * 4;
+    hi.resize(padded);
+    for (size_t i = (size_t)kept; i < padded; ++i) hi[i] = 0xFFFFFFFFu;
+    DevBuf<double> dRec;
+    DevBuf<uint32_t> dHi;
+    CPF_HIP(ctx, dRec.alloc(rec.size()));
+    CPF_HIP(ctx, dHi.alloc(hi.size()));
+    CPF_HIP(ctx, hipMemcpy(dRec, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
+    CPF_HIP(ctx, hipMemcpy(dHi, hi.data(), hi.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    hi.resize((size_t)kept);
+    ctx->mesh.sourceRec = std::move(dRec);
+    ctx->mesh.sourceHi = std::move(dHi);
+    ctx->mesh.sourceKept = kept;
+    ctx->mesh.sourceRecHost = std::move(rec);
+    ctx->mesh.sourceHiHost = std::move(hi);
+    return CPF_OK;
+}
+
+int cpf_get_source_table(cpf_context* ctx, double* rec, uint32_t* hi, int64_t* nKept) {
+    CPF_REQUIRE(ctx, ctx && nKept, CPF_ERR_ARG, "null argument");
+    *nKept = ctx->mesh.sourceKept;
+    if (rec) std::copy(ctx->mesh.sourceRecHost.begin(), ctx->mesh.sourceRecHost.end(), rec);
+    if (hi) std::copy(ctx->mesh.sourceHiHost.begin(), ctx->mesh.sourceHiHost.end(), hi);
+    return CPF_OK;
+}
+
+int cpf_respawn_source_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cell, const int64_t* gid, int64_t n,
+                           int64_t maxCount, uint32_t epoch) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_respawn_source: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->mesh.sourceKept > 0, CPF_ERR_STATE, "cpf_respawn_source: call cpf_set_source_triangles first");
+    CPF_REQUIRE(ctx, n >= 0 && n < ((int64_t)1 << 31) && (n == 0 || (x && y && z && cell)), CPF_ERR_ARG,
+                "cpf_respawn_source: bad arguments");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    int r = ensureRecycleCounts(ctx);
+    if (r) return r;
+    if (maxCount > 0 && maxCount < n) {
+        r = ensureScratch(ctx, cpf::respawn_scratch_bytes(n));
+        if (r) return r;
+    }
+    const cpf::SourceView src{ctx->mesh.sourceRec, ctx->mesh.sourceHi, (int32_t)ctx->mesh.sourceKept};
+    CPF_HIP(ctx, cpf::respawn_source(ctx->stream, x, y, z, cell, gid, n, src, maxCount, ctx->seed, epoch, meshView(ctx), gridView(ctx),
+                                     ctx->scratch, ctx->scratchBytes, ctx->recycleCounts));
+    return CPF_OK;
+}
+
+int cpf_respawn_source(cpf_context* ctx, int64_t maxCount) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_respawn_source: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->mesh.sourceKept > 0, CPF_ERR_STATE, "cpf_respawn_source: call cpf_set_source_triangles first");
+    CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_respawn_source: no located particles");
+    if (ctx->age.on && maxCount != 0) {
+        // age tracking: every candidate is born now, as in cpf_respawn_box
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        CPF_HIP(ctx, cpf::age_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->age.birth, ctx->cloud.n, ctx->stepCounter));
+    }
+    int r = cpf_respawn_source_dev(ctx, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell, ctx->cloud.cur.gid,
+                                   ctx->cloud.n, maxCount, ctx->cloud.respawnEpoch);
+    if (r) return r;
+    ctx->cloud.zSettled = false;                    // (as behind cpf_respawn_box)
+    ++ctx->cloud.respawnEpoch;
     return CPF_OK;
 }
 

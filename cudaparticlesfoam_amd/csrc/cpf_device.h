@@ -290,6 +290,17 @@ size_t respawn_scratch_bytes(int64_t n);
 hipError_t respawn_box(hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid, int64_t n,
                        const double lower[3], const double upper[3], int64_t maxCount, uint32_t seed, uint32_t epoch,
                        const MeshView& m, const GridView& g, void* scratch, size_t scratchBytes, unsigned long long* counters);
+// passes (a) and (b) of a limited respawn, for the place kernels of cpf_recycle.hip and cpf_inlet.hip: *offsets = the exclusive
+// offsets of the slices' dead slots (in `scratch`), or null where maxCount cannot bind (< 0, or >= n)
+hipError_t respawn_offsets(hipStream_t st, const int32_t* cell, int64_t n, int64_t maxCount, void* scratch, size_t scratchBytes,
+                           const unsigned** offsets);
+// patch source (cpf_inlet.hip).  The same candidates, order and counters as respawn_box; the position is source_point's
+// (cpf_philox.h) on the table of cpf_source_table_host: rec[nKept][16] doubles, hi[nKept] bounds padded with 0xFFFFFFFF to a
+// multiple of 4 entries (the kernel stages them with 16-byte loads)
+struct SourceView { const double* rec; const uint32_t* hi; int32_t nKept; };
+hipError_t respawn_source(hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid, int64_t n,
+                          const SourceView& src, int64_t maxCount, uint32_t seed, uint32_t epoch, const MeshView& m,
+                          const GridView& g, void* scratch, size_t scratchBytes, unsigned long long* counters);
 // tracer age (cpf_age.hip).  birth[id] (n entries, id = gid[slot]; gid null: the slot) is the cycle count at which particle id last
 // became live, an age is (uint32_t)(now - birth).  age_absorb: sink_apply, and hist[min(age / binCycles, nBins - 1)] += 1 for every
 // particle it absorbs.  age_stamp: birth[id] = now for every slot with cell < 0.  age_field: for every i with 0 <= cell[i] <

@@ -24,10 +24,7 @@
 namespace cpf {
 namespace {
 
-// one round of loads per workgroup: dead slots come in runs (a sink's cells are neighbours in a sorted cloud, a sort sends the dead to
-// the tail), and a workgroup takes its dead 64 at a time per wave -- measured, four rounds a workgroup made a run three times as slow
-constexpr int kSpawnLoads = 1;                              // 16-byte loads per lane
-constexpr int kSpawnSlice = slice_ids(kSpawnLoads);         // ids per workgroup
+// (kSpawnLoads, kSpawnSlice: cpf_slice.h -- cpf_inlet.hip's pass walks the same slices)
 constexpr int kScanBlock = 1024;                            // the single workgroup of pass (b)
 
 }  // namespace
@@ -207,6 +204,19 @@ size_t respawn_scratch_bytes(int64_t n) {
     return (size_t)(blocks > 0 ? blocks : 1) * 2 * sizeof(unsigned);
 }
 
+hipError_t respawn_offsets(hipStream_t st, const int32_t* cell, int64_t n, int64_t maxCount, void* scratch, size_t scratchBytes,
+                           const unsigned** offsets) {
+    *offsets = nullptr;
+    if (!(maxCount > 0 && maxCount < n)) return hipSuccess;     // (maxCount >= n cannot bind: the unlimited pass alone)
+    if (scratchBytes < respawn_scratch_bytes(n)) return hipErrorInvalidValue;
+    const SliceLaunch l = slice_launch(cell, n, kSpawnLoads);
+    unsigned* counts = static_cast<unsigned*>(scratch);
+    hipLaunchKernelGGL(respawn_count_kernel, dim3((unsigned)l.blocks), dim3(kSliceBlock), 0, st, cell, n, l.vec ? 1 : 0, counts);
+    hipLaunchKernelGGL(respawn_scan_kernel, dim3(1), dim3(kScanBlock), 0, st, counts, counts + l.blocks, (int)l.blocks);
+    *offsets = counts + l.blocks;
+    return hipGetLastError();
+}
+
 hipError_t respawn_box(hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid, int64_t n,
                        const double lower[3], const double upper[3], int64_t maxCount, uint32_t seed, uint32_t epoch,
                        const MeshView& m, const GridView& g, void* scratch, size_t scratchBytes, unsigned long long* counters) {
@@ -216,14 +226,9 @@ hipError_t respawn_box(hipStream_t st, double* x, double* y, double* z, int32_t*
     const int vec = l.vec ? 1 : 0;
     SpawnBox box;
     for (int k = 0; k < 3; ++k) { box.lower[k] = lower[k]; box.upper[k] = upper[k]; }
-    unsigned* offsets = nullptr;
-    if (maxCount > 0 && maxCount < n) {                     // (maxCount >= n cannot bind: the unlimited pass alone)
-        if (scratchBytes < respawn_scratch_bytes(n)) return hipErrorInvalidValue;
-        unsigned* counts = static_cast<unsigned*>(scratch);
-        offsets = counts + l.blocks;
-        hipLaunchKernelGGL(respawn_count_kernel, dim3((unsigned)l.blocks), dim3(kSliceBlock), 0, st, cell, n, vec, counts);
-        hipLaunchKernelGGL(respawn_scan_kernel, dim3(1), dim3(kScanBlock), 0, st, counts, offsets, (int)l.blocks);
-    }
+    const unsigned* offsets = nullptr;
+    const hipError_t e = respawn_offsets(st, cell, n, maxCount, scratch, scratchBytes, &offsets);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(respawn_place_kernel, dim3((unsigned)l.blocks), dim3(kSliceBlock), 0, st, x, y, z, cell, gid, n, vec, box, offsets,
                        maxCount, seed, epoch, m.cellOff, m.planes, g, counters);
     return hipGetLastError();

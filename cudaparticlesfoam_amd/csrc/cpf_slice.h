@@ -21,6 +21,11 @@ constexpr int kSliceBlock = 256;                            // 4 waves
 constexpr int kSliceLoads = 4;                              // 16-byte loads in flight per lane (the respawn kernels: one, see there)
 constexpr int kSliceTrip = kSliceBlock * 4;                 // ids one round of loads covers
 constexpr int slice_ids(int loads) { return kSliceTrip * loads; }   // ids per workgroup
+// the respawn passes (cpf_recycle.hip, cpf_inlet.hip): one round of loads per workgroup: dead slots come in runs (a sink's cells are
+// neighbours in a sorted cloud, a sort sends the dead to the tail), and a workgroup takes its dead 64 at a time per wave --
+// measured, four rounds a workgroup made a run three times as slow
+constexpr int kSpawnLoads = 1;                              // 16-byte loads per lane
+constexpr int kSpawnSlice = slice_ids(kSpawnLoads);         // ids per workgroup
 constexpr int kSinkLdsWords = 2048;                         // mask words staged in LDS: 8 KB, 65 536 cells -- half a slice's id bytes at most
 
 // The launch of a slice pass over n > 0 ids: its grid, and whether `cell` is 16-byte aligned (a slice starts at a multiple of

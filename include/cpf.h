@@ -449,6 +449,52 @@ int cpf_respawn_positions_host(uint32_t seed, const int64_t* gid, int64_t n, uin
                                const double upper[3], double* xyz);
 
 /* ---------------------------------------------------------------------------------------------
+ * patch source: dead slots are respawned on a triangulated surface, weighted by flux -- the inlet of the recycling cloud
+ * NO REFERENCE COUNTERPART for any entry of this group.  Where cpf_respawn_box puts a dead slot uniformly into a box, these put it
+ * on one of the caller's triangles (normally the fan triangles (f[0], f[k], f[k+1]) of an inlet patch's faces), chosen with
+ * probability proportional to a weight (default: the area; the flux-weighted choice is area * max(0, -U_owner . n_out)), uniformly
+ * within the triangle, pushed AGAINST the triangle's right-hand normal (B - A) x (C - A) -- into the mesh, for a boundary face in
+ * OpenFOAM's orientation -- by a depth drawn uniformly from [d0, d1].  With d1 = |U.n| * dt * (cycles between respawns) the slab
+ * holds what entered since the last respawn.  Candidates, array order, maxCount, the three counters, the cell of a point and the
+ * fate of a point outside the mesh are cpf_respawn_box's; so is the cloud's epoch counter, which the two share.
+ * The table (cpf_source_table_host), per input triangle with every operation rounded on its own: e1 = B - A, e2 = C - A,
+ * c = e1 x e2, len = sqrt(c.c), nIn = -c / len, area = len / 2, w = weight ? weight[t] : area.  A triangle with len == 0 or
+ * w == 0 is dropped.  With C_t the running sum of the kept weights in input order, b_t = floor(C_t / C_last * 2^32), b_last = 2^32;
+ * a triangle with b_t == b_(t-1) (a share below 2^-32) is dropped too; hi[t] = b_t - 1, strictly increasing, ending in 0xFFFFFFFF.
+ * A record is 16 doubles: A[3] | e1[3] | e2[3] | nIn[3] | d0 | d1 - d0 | index of the triangle in the caller's array | 0.
+ * The position, a pure function of (seed, particle id, epoch): Philox4x32-7, counter (id low 32, id high 32, epoch, 0), key (seed,
+ * 0x43504633); word 0 picks the first t with w0 <= hi[t]; words 1 and 2, as 64-bit integers, are each replaced by 2^32 - w if
+ * w1 + w2 > 2^32, and u = w * 2^-32; d = d0 + (w3 * 2^-32) * (d1 - d0); pos_k = ((A_k + u1 * e1_k) + u2 * e2_k) + d * nIn_k, each
+ * product and sum rounded on its own, in that order.
+ * The weights are the caller's: a source does not follow cpf_set_velocity -- set it again when U changes.  cpf_shard_* and the
+ * compat fragments do not know of it.
+ * ------------------------------------------------------------------------------------------- */
+/* NO REFERENCE COUNTERPART.  The table builder -- no context, no GPU.  tri[n][3][3]; weight[n] nullable (the areas); depth[n][2]
+ * nullable (then d0, d1 hold for every triangle; otherwise they are ignored).  rec (16 * n doubles) and hi (n words) are nullable
+ * and have room for n triangles; *nKept = the number written.  CPF_ERR_ARG: a weight negative or not finite (a triangle with a
+ * coordinate that is not finite has such an area), d0 > d1, a depth not finite, no triangle kept, more than 2^24 kept. */
+int cpf_source_table_host(const double* tri, const double* weight, const double* depth, double d0, double d1, int64_t n,
+                          double* rec, uint32_t* hi, int64_t* nKept);
+/* NO REFERENCE COUNTERPART.  The position on the host alone -- no context, no GPU; compiled from the text the kernel is compiled
+ * from: xyz[n][3] for the ids gid[n] (null: 0 .. n-1) on the table rec[nKept][16], hi[nKept]. */
+int cpf_source_positions_host(uint32_t seed, const int64_t* gid, int64_t n, uint32_t epoch, const double* rec, const uint32_t* hi,
+                              int64_t nKept, double* xyz);
+/* NO REFERENCE COUNTERPART.  Builds the table of the n triangles (host memory, as for cpf_source_table_host) and uploads it.
+ * n == 0 clears the source.  CPF_ERR_STATE without a mesh.  The source belongs to the mesh: cpf_set_mesh* drops it. */
+int cpf_set_source_triangles(cpf_context* ctx, const double* tri, const double* weight, const double* depth, double d0, double d1,
+                             int64_t n);
+/* NO REFERENCE COUNTERPART.  The context's table: rec[nKept][16] and hi[nKept] (each nullable), *nKept (0 without a source). */
+int cpf_get_source_table(cpf_context* ctx, double* rec, uint32_t* hi, int64_t* nKept);
+/* NO REFERENCE COUNTERPART.  Respawns up to maxCount (< 0: all) dead slots of the context-owned cloud on the source, with the
+ * cloud's own epoch counter -- the one cpf_respawn_box uses and increments: a run may mix the two, and no (id, epoch) is drawn
+ * twice from one stream.  Asynchronous on the context's stream.  The cloud's z no longer counts as settled.  With age tracking
+ * on, every candidate is stamped first, as by cpf_respawn_box.  CPF_ERR_STATE without a mesh, a source or located particles. */
+int cpf_respawn_source(cpf_context* ctx, int64_t maxCount);
+/* NO REFERENCE COUNTERPART.  The same on caller-owned device arrays (gid nullable: id = index; n < 2^31) with the caller's epoch. */
+int cpf_respawn_source_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cell, const int64_t* gid, int64_t n,
+                           int64_t maxCount, uint32_t epoch);
+
+/* ---------------------------------------------------------------------------------------------
  * tracer age: the residence-time distribution at the sink and the local mean age, for a recycled cloud
  * NO REFERENCE COUNTERPART for any entry of this group.  The state is one 32-bit stamp per PARTICLE ID (the order of
  * cpf_get_particles), birth[id] = the context's cycle counter when that particle last became live.  The cycle counter is the one

@@ -61,6 +61,12 @@ def collect_age():
     return parse(r.stderr, ("age_",))
 
 
+def collect_inlet():
+    """The same rows for the patch-source kernel (cpf_inlet.hip: inlet_place_kernel); collect() does not list it."""
+    r = subprocess.run(hipcc_cmd("cpf_inlet.hip") + ["-c", "-o", "/dev/null"], capture_output=True, text=True)
+    return parse(r.stderr, ("inlet_",))
+
+
 def kernel_bodies(asm):
     """mangled kernel name -> its instructions (labels, directives and comments dropped).  Only what the listing types as a
     function: a library's constant table (rocprim has one) is a _Z label too, and the text behind the last one is the metadata."""
