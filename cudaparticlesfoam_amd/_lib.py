@@ -169,6 +169,18 @@ SIGNATURES = {
     "cpf_get_ages": (_int, [_ctx, _vp]),
     "cpf_age_get_births": (_int, [_ctx, _vp]),
     "cpf_age_set_births": (_int, [_ctx, _vp]),
+    "cpf_tag_enable": (_int, [_ctx, _i32, _i32]),
+    "cpf_tag_disable": (_int, [_ctx]),
+    "cpf_set_sink_groups": (_int, [_ctx, _vp, _vp, _i64]),
+    "cpf_set_source_origins": (_int, [_ctx, _vp, _i64]),
+    "cpf_set_box_origin": (_int, [_ctx, _i32]),
+    "cpf_tag_sample": (_int, [_ctx]),
+    "cpf_tag_reset": (_int, [_ctx]),
+    "cpf_get_transfer": (_int, [_ctx, _vp]),
+    "cpf_get_tag_field": (_int, [_ctx, _vp, C.POINTER(_i64)]),
+    "cpf_tag_get_origins": (_int, [_ctx, _vp]),
+    "cpf_tag_set_origins": (_int, [_ctx, _vp]),
+    "cpf_source_picks_host": (_int, [_u32, _vp, _i64, _u32, _vp, _i64, _vp]),
     "cpf_set_velocity": (_int, [_ctx, _vp, _i64]),
     "cpf_set_velocity_dev": (_int, [_ctx, _vp, _i64]),
     "cpf_alloc_particles": (_int, [_ctx, _i64]),

@@ -383,6 +383,82 @@ class Context:
         np.divide(s.astype(np.float64), c.astype(np.float64), out=out, where=c > 0)
         return out * float(dt)
 
+    # -- tracer tags: origin per particle, grouped sinks, the transfer matrix (include/cpf.h "tracer tags")
+    def tag_enable(self, n_origins: int = 1, n_sinks: int = 1):
+        """Turns tagging of the context-owned cloud on (or starts it anew): everybody has origin 0, every sink cell is in group 0,
+        the source and the box give origin 0; ``n_origins`` and ``n_sinks`` are each in [1, 16]."""
+        self._ck(self.lib.cpf_tag_enable(self.h, int(n_origins), int(n_sinks)))
+        self._tag_shape = (int(n_origins), int(n_sinks))
+
+    def tag_disable(self):
+        self._ck(self.lib.cpf_tag_disable(self.h))
+
+    def set_sink_groups(self, cells, groups):
+        """``set_sink_cells(cells)``, with cell ``cells[k]`` in sink group ``groups[k]``."""
+        c = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1)
+        g = np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+        if c.size != g.size:
+            raise ValueError("set_sink_groups: %d groups for %d cells" % (g.size, c.size))
+        self._ck(self.lib.cpf_set_sink_groups(self.h, _ptr(c) if c.size else None, _ptr(g) if g.size else None, c.size))
+
+    def set_source_origins(self, origin_of_triangle):
+        """One origin per triangle of ``set_source_triangles``, in the caller's order (dropped triangles included)."""
+        o = np.ascontiguousarray(origin_of_triangle, dtype=np.int32).reshape(-1)
+        self._ck(self.lib.cpf_set_source_origins(self.h, _ptr(o) if o.size else None, o.size))
+
+    def set_box_origin(self, origin: int):
+        self._ck(self.lib.cpf_set_box_origin(self.h, int(origin)))
+
+    def tag_sample(self):
+        """One sample of the per-origin occupancy: every live particle adds 1 to (its cell, its origin); asynchronous."""
+        self._ck(self.lib.cpf_tag_sample(self.h))
+
+    def tag_reset(self):
+        """Zeroes the transfer matrix, the field and the sample count; the origins stay."""
+        self._ck(self.lib.cpf_tag_reset(self.h))
+
+    def tag_origins(self) -> np.ndarray:
+        """uint8 [n] in particle-id order: the origin of the respawn that last made each particle live (0: the initial cloud)."""
+        o = np.empty(self.n, np.uint8)
+        self._ck(self.lib.cpf_tag_get_origins(self.h, _ptr(o)))
+        return o
+
+    def tag_set_origins(self, origins):
+        o = np.ascontiguousarray(origins, dtype=np.uint8).reshape(-1)
+        if o.size != self.n:
+            raise ValueError("tag_set_origins: %d origins for %d particles" % (o.size, self.n))
+        self._ck(self.lib.cpf_tag_set_origins(self.h, _ptr(o)))
+
+    def transfer(self) -> np.ndarray:
+        """uint64 [n_origins][n_sinks]: absorptions since the last reset by (origin, sink group); synchronises."""
+        t = np.zeros(getattr(self, "_tag_shape", (1, 1)), np.uint64)
+        self._ck(self.lib.cpf_get_transfer(self.h, _ptr(t)))
+        return t
+
+    def tag_field(self):
+        """(counts uint64 [n_origins][n_cells], n_samples) per parent cell since the last reset; synchronises."""
+        n_origins = getattr(self, "_tag_shape", (1, 1))[0]
+        c = np.zeros((self.n_cells, n_origins), np.uint64)
+        ns = C.c_int64(0)
+        self._ck(self.lib.cpf_get_tag_field(self.h, _ptr(c), C.byref(ns)))
+        return np.ascontiguousarray(c.T), ns.value
+
+    def origin_concentration(self) -> np.ndarray:
+        """[n_origins][n_cells]: time-averaged particles of each origin per unit volume, counts / (n_samples * V)."""
+        counts, ns = self.tag_field()
+        if ns == 0:
+            raise ValueError("origin_concentration: no tag sample yet (tag_sample)")
+        return counts.astype(np.float64) / (float(ns) * self.cell_volumes()[None, :])
+
+    def origin_fraction(self) -> np.ndarray:
+        """[n_origins][n_cells]: each origin's share of the particles found in a cell over the samples taken; NaN where none was."""
+        counts, _ = self.tag_field()
+        c = counts.astype(np.float64)
+        total = c.sum(axis=0)
+        out = np.full(c.shape, np.nan)
+        np.divide(c, total[None, :], out=out, where=(total > 0)[None, :])
+        return out
+
     def cell_ranges_dev(self, weights, n_ranks, cell_lo):
         self._ck(self.lib.cpf_cell_ranges_dev(self.h, weights, n_ranks, cell_lo))
 
@@ -480,6 +556,20 @@ def source_positions_host(seed: int, gid, epoch: int, rec, hi, n: Optional[int] 
     if st != L.CPF_OK:
         raise L.CpfError(st, "cpf_source_positions_host")
     return xyz
+
+
+def source_picks_host(seed: int, gid, epoch: int, hi, n: Optional[int] = None) -> np.ndarray:
+    """Which kept record of the table's bounds ``hi`` ``respawn_source`` picks for the particles ``gid`` (None: 0 .. n-1) at
+    ``epoch`` under ``seed``: int32 [n], computed on the host alone from the kernels' own text (cpf_source_picks_host)."""
+    lib = L.load()
+    g = None if gid is None else np.ascontiguousarray(gid, dtype=np.int64).reshape(-1)
+    n = int(n) if g is None else g.size
+    h = np.ascontiguousarray(hi, dtype=np.uint32).reshape(-1)
+    pick = np.empty(n, np.int32)
+    st = lib.cpf_source_picks_host(seed & 0xFFFFFFFF, _ptr(g), n, int(epoch) & 0xFFFFFFFF, _ptr(h), h.size, _ptr(pick))
+    if st != L.CPF_OK:
+        raise L.CpfError(st, "cpf_source_picks_host")
+    return pick
 
 
 def inflow_weights(mesh, U, tri, face_of_tri) -> np.ndarray:
@@ -690,6 +780,12 @@ class CudaParticles:
     When ``ageBins`` is positive, age tracking (``Context.age_enable``) starts once the cloud is located: every absorption adds a
     residence time to ``rtd()``, and wherever an occupancy sample is taken the age field is sampled too, after recycling, for
     ``mean_age()``.
+
+    Two more: ``sinkGroups`` (one int per entry of ``sinkCells``) and ``sourceOrigins`` (one int per triangle of
+    ``sourceTriangles``).  Tagging (``Context.tag_enable``) is on if and only if one of them is given, with max + 1 sink groups and
+    origins (1 where the key is absent), once the cloud is located: every absorption adds to ``transfer()[origin, group]``, and
+    wherever an occupancy sample is taken the per-origin field is sampled too, for ``origin_fraction()``.  The initial cloud has
+    origin 0, so number real sources from 1 to tell it apart.
     """
 
     def __init__(self, mesh, U, particle_dict: Optional[dict] = None, device: int = 0,
@@ -712,6 +808,13 @@ class CudaParticles:
         self.sourceDepth = d.get("sourceDepth", (0.0, 0.0))
         self.ageBins = int(d.get("ageBins", 0))
         self.ageBinCycles = int(d.get("ageBinCycles", self.recycleInterval if self.recycleInterval > 0 else 1))
+        self.sinkGroups = d.get("sinkGroups", None)
+        self.sourceOrigins = d.get("sourceOrigins", None)
+        self.tags = self.sinkGroups is not None or self.sourceOrigins is not None
+        if self.sinkGroups is not None and (self.recycleInterval <= 0 or self.sinkCells is None):
+            raise ValueError("sinkGroups needs recycleInterval > 0 and sinkCells")
+        if self.sourceOrigins is not None and (self.recycleInterval <= 0 or self.sourceTriangles is None):
+            raise ValueError("sourceOrigins needs recycleInterval > 0 and sourceTriangles")
         # hard-coded switches of the fragment (src/initCuda.H:64-72)
         self.usingAdvection = True
         self.usingBrownianMotion = True
@@ -738,6 +841,14 @@ class CudaParticles:
         self.ctx.sort_by_cell()
         if self.ageBins > 0:
             self.ctx.age_enable(self.ageBinCycles, self.ageBins)
+        if self.tags:
+            n_sinks = 1 if self.sinkGroups is None else int(np.max(self.sinkGroups)) + 1
+            n_origins = 1 if self.sourceOrigins is None else int(np.max(self.sourceOrigins)) + 1
+            self.ctx.tag_enable(n_origins, n_sinks)
+            if self.sinkGroups is not None:
+                self.ctx.set_sink_groups(self.sinkCells, self.sinkGroups)
+            if self.sourceOrigins is not None:
+                self.ctx.set_source_origins(self.sourceOrigins)
         if self.writer is not None:
             # frame 0 carries the velocities of one advect and out-of-domain particles as inactive, like the reference
             # (src/initCuda.H:184-201): a cycle of zero length (moves nothing, does not count as a step)
@@ -788,6 +899,8 @@ class CudaParticles:
                 self.ctx.occupancy_sample()
                 if self.ageBins > 0:
                     self.ctx.age_sample()
+                if self.tags:
+                    self.ctx.tag_sample()
         return n_cycles
 
     def particles(self):
@@ -808,6 +921,15 @@ class CudaParticles:
     def mean_age(self):
         """Mean age in seconds per cell over the samples ``occupancyInterval`` took, with ``ageBins`` set (``Context.mean_age``)."""
         return self.ctx.mean_age(self.dt)
+
+    def transfer(self):
+        """Absorptions by (origin, sink group), with ``sinkGroups`` or ``sourceOrigins`` set (``Context.transfer``)."""
+        return self.ctx.transfer()
+
+    def origin_fraction(self):
+        """Each origin's share per cell over the samples ``occupancyInterval`` took, NaN where no particle was found
+        (``Context.origin_fraction``)."""
+        return self.ctx.origin_fraction()
 
     def close(self):
         self.ctx.close()

@@ -114,6 +114,20 @@ struct Age {
     int64_t samples = 0;
 };
 
+// Tracer tags of the context's own cloud (cpf_tag_*; cpf_tags.hip).  The origins belong to a cloud, the groups and the field to a
+// mesh: a new cloud and a new mesh each replace the group with an empty one.
+struct Tags {
+    bool on = false;
+    int32_t nOrigins = 1, nSinks = 1, boxOrigin = 0;
+    DevBuf<uint8_t> origin;                 // [cloud.n] by particle id: the origin of the respawn that last made the particle live
+    DevBuf<uint8_t> sinkGroup;              // [host.nCells] the group of every DERIVED cell (read for cells of the sink mask only)
+    DevBuf<uint8_t> originOfKept;           // [sourceKept] the origin of every kept record of the source table; null: no source
+    DevBuf<unsigned long long> transfer;    // [nOrigins][nSinks] absorptions (room for kTagMax x kTagMax)
+    DevBuf<unsigned long long> field;       // [nParent][nOrigins] counts of the samples since the last reset
+    int64_t samples = 0;
+};
+constexpr int32_t kTagMax = 16;
+
 // asynchronous output (cpf_write_vtu_async): one frame in flight.  Lives as long as the context.
 struct FrameWriter {
     std::thread thread;
@@ -186,7 +200,7 @@ struct cpf_context {
     bool vertexFast = true;                     // cpf_set_option("vertex_fast")
     uint32_t seed = 1591593751u;                // cuda/particles.cu:544
     // ---- the groups
-    Mesh mesh; TetField tet; Cloud cloud; Age age; FrameWriter frame; Timing timing;
+    Mesh mesh; TetField tet; Cloud cloud; Age age; Tags tags; FrameWriter frame; Timing timing;
     // ---- what lives as long as the context
     DevBuf<char> scratch;
     size_t scratchBytes = 0;
@@ -292,6 +306,15 @@ int dropAge(cpf_context* ctx) {
     return CPF_OK;
 }
 
+// tagging off (cpf_tag_disable, a new cloud): a pass over the origins may still be running
+int dropTags(cpf_context* ctx) {
+    if (!ctx->tags.on) return CPF_OK;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->tags = Tags{};
+    return CPF_OK;
+}
+
 int sortEndBit(const cpf_context* ctx) {
     int bits = 1;
     while (((int64_t)1 << bits) < ctx->mesh.host.nCells + 2) ++bits;   // the all-ones key of lost/frozen sorts last
@@ -345,6 +368,7 @@ int setMeshImpl(cpf_context* ctx, const double* points, int64_t nPoints, const L
     ctx->mesh = Mesh{};
     ctx->tet = TetField{};
     ctx->age = Age{};
+    ctx->tags = Tags{};
     ctx->streamState.flatField = false;
     ctx->mesh.host = std::move(t);
     ctx->mesh.nParent = nCells;
@@ -892,6 +916,7 @@ int cpf_alloc_particles(cpf_context* ctx, int64_t capacity) {
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->cloud = Cloud{};
     ctx->age = Age{};
+    ctx->tags = Tags{};
     const size_t c = (size_t)capacity;
     CPF_HIP(ctx, ctx->cloud.cur.alloc(c));
     CPF_HIP(ctx, ctx->cloud.vel.alloc(c * 3));
@@ -906,6 +931,7 @@ int cpf_seed_box(cpf_context* ctx, int64_t n, const double lower[3], const doubl
     CPF_REQUIRE(ctx, lower && upper && n > 0, CPF_ERR_ARG, "cpf_seed_box: bad arguments");
     if (ctx->cloud.cap < n) { int r = cpf_alloc_particles(ctx, n); if (r) return r; }
     if (int r = dropAge(ctx)) return r;                     // (a new cloud: the stamps were the old one's)
+    if (int r = dropTags(ctx)) return r;                    // (... and so were the origins)
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, cpf::launch_seed_box(ctx->stream, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, 0, n, lower, upper, order));
     CPF_HIP(ctx, cpf::launch_iota64(ctx->stream, ctx->cloud.cur.gid, n, 0));
@@ -919,6 +945,8 @@ int cpf_set_particles(cpf_context* ctx, int64_t n, const double* xyz, const int3
     CPF_REQUIRE(ctx, xyz && n > 0, CPF_ERR_ARG, "cpf_set_particles: bad arguments");
     if (ctx->cloud.cap < n) { int r = cpf_alloc_particles(ctx, n); if (r) return r; }
     int r = dropAge(ctx);                                   // (a new cloud: the stamps were the old one's)
+    if (r) return r;
+    r = dropTags(ctx);                                      // (... and so were the origins)
     if (r) return r;
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     ctx->cloud.zSettled = false;
@@ -1423,6 +1451,8 @@ int cpf_set_sink_cells(cpf_context* ctx, const int32_t* parentCells, int64_t n) 
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass over the old mask may still be running)
     ctx->mesh.sinkMask = DevBuf<uint32_t>{};
+    // tagging: every cell of a plain sink set is in group 0 (cpf_set_sink_groups says otherwise)
+    if (ctx->tags.on) CPF_HIP(ctx, hipMemset(ctx->tags.sinkGroup, 0, (size_t)ctx->mesh.host.nCells));
     if (n == 0) return CPF_OK;
     // one bit per DERIVED cell: every derived cell of a sink parent is set
     const int64_t nDerived = ctx->mesh.host.nCells;
@@ -1456,6 +1486,13 @@ int cpf_sink_apply(cpf_context* ctx) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_sink_apply: call cpf_set_mesh first");
     CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_sink_apply: no located particles");
+    if (ctx->tags.on && ctx->mesh.sinkMask) {
+        // tagging: a read-only pass of its own counts (origin, sink group) of everybody the sink is about to absorb (cpf_tags.hip)
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        CPF_HIP(ctx, cpf::tag_transfer(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->tags.origin, ctx->cloud.n,
+                                       ctx->mesh.sinkMask, ctx->mesh.host.nCells, ctx->tags.sinkGroup, ctx->tags.nOrigins,
+                                       ctx->tags.nSinks, ctx->tags.transfer));
+    }
     if (!ctx->age.on) return cpf_sink_apply_dev(ctx, ctx->cloud.cur.cell, ctx->cloud.n);
     // age tracking: the same pass, which also bins the age of every particle it absorbs (cpf_age.hip)
     if (!ctx->mesh.sinkMask) return CPF_OK;
@@ -1501,6 +1538,12 @@ int cpf_respawn_box(cpf_context* ctx, const double lower[3], const double upper[
         // call that places them
         CPF_HIP(ctx, hipSetDevice(ctx->device));
         CPF_HIP(ctx, cpf::age_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->age.birth, ctx->cloud.n, ctx->stepCounter));
+    }
+    if (ctx->tags.on && boxOk && maxCount != 0) {
+        // tagging: every candidate gets the box's origin, under the conditions of age's stamp
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        CPF_HIP(ctx, cpf::tag_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->tags.origin, ctx->cloud.n, nullptr, 0,
+                                    nullptr, ctx->seed, ctx->cloud.respawnEpoch, ctx->tags.boxOrigin));
     }
     int r = cpf_respawn_box_dev(ctx, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell, ctx->cloud.cur.gid,
                                 ctx->cloud.n, lower, upper, maxCount, ctx->cloud.respawnEpoch);
@@ -1634,7 +1677,13 @@ int cpf_set_source_triangles(cpf_context* ctx, const double* tri, const double* 
     ctx->mesh.sourceKept = 0;
     ctx->mesh.sourceRecHost.clear();
     ctx->mesh.sourceHiHost.clear();
+    ctx->tags.originOfKept = DevBuf<uint8_t>{};
     if (n == 0) return CPF_OK;
+    DevBuf<uint8_t> dOrigin;                                // tagging: a new source starts with every triangle in origin 0
+    if (ctx->tags.on) {
+        CPF_HIP(ctx, dOrigin.alloc((size_t)kept));
+        CPF_HIP(ctx, hipMemset(dOrigin, 0, (size_t)kept));
+    }
     rec.resize((size_t)kept * cpf::kSourceDoubles);
     const size_t padded = ((size_t)kept + 3) / 4 * 4;
     hi.resize(padded);
@@ -1651,6 +1700,7 @@ int cpf_set_source_triangles(cpf_context* ctx, const double* tri, const double* 
     ctx->mesh.sourceKept = kept;
     ctx->mesh.sourceRecHost = std::move(rec);
     ctx->mesh.sourceHiHost = std::move(hi);
+    ctx->tags.originOfKept = std::move(dOrigin);
     return CPF_OK;
 }
 
@@ -1691,6 +1741,13 @@ int cpf_respawn_source(cpf_context* ctx, int64_t maxCount) {
         // age tracking: every candidate is born now, as in cpf_respawn_box
         CPF_HIP(ctx, hipSetDevice(ctx->device));
         CPF_HIP(ctx, cpf::age_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->age.birth, ctx->cloud.n, ctx->stepCounter));
+    }
+    if (ctx->tags.on && maxCount != 0) {
+        // tagging: every candidate gets the origin of the triangle this call's epoch picks for its id (cpf_tags.hip)
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        CPF_HIP(ctx, cpf::tag_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->tags.origin, ctx->cloud.n,
+                                    ctx->mesh.sourceHi, (int32_t)ctx->mesh.sourceKept, ctx->tags.originOfKept, ctx->seed,
+                                    ctx->cloud.respawnEpoch, 0));
     }
     int r = cpf_respawn_source_dev(ctx, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell, ctx->cloud.cur.gid,
                                    ctx->cloud.n, maxCount, ctx->cloud.respawnEpoch);
@@ -1812,6 +1869,173 @@ int cpf_get_ages(cpf_context* ctx, int64_t* age) {
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const uint32_t now = ctx->stepCounter;
     for (size_t i = 0; i < n; ++i) age[i] = cell[i] >= 0 ? (int64_t)(uint32_t)(now - birth[i]) : -1;
+    return CPF_OK;
+}
+
+// ---- tracer tags: an origin per particle id, grouped sinks, the transfer matrix, the per-origin field (cpf_tags.hip) -------
+int cpf_tag_enable(cpf_context* ctx, int32_t nOrigins, int32_t nSinks) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_tag_enable: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_tag_enable: no located particles");
+    CPF_REQUIRE(ctx, nOrigins >= 1 && nOrigins <= kTagMax && nSinks >= 1 && nSinks <= kTagMax, CPF_ERR_ARG,
+                "cpf_tag_enable: 1 <= nOrigins <= 16 and 1 <= nSinks <= 16");
+    CPF_REQUIRE(ctx, ctx->mesh.nParent * (int64_t)nOrigins < ((int64_t)1 << 31), CPF_ERR_ARG,
+                "cpf_tag_enable: nCells * nOrigins must stay below 2^31");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass over the old tables may still be running)
+    ctx->tags = Tags{};
+    Tags t;                                                 // moved in whole: a failure part-way leaves tagging off
+    const size_t n = (size_t)ctx->cloud.n, nDerived = (size_t)ctx->mesh.host.nCells, nField = (size_t)ctx->mesh.nParent * nOrigins;
+    CPF_HIP(ctx, t.origin.alloc(n));
+    CPF_HIP(ctx, t.sinkGroup.alloc(nDerived));
+    CPF_HIP(ctx, t.transfer.alloc((size_t)kTagMax * kTagMax));
+    CPF_HIP(ctx, t.field.alloc(nField));
+    CPF_HIP(ctx, hipMemsetAsync(t.origin, 0, n, ctx->stream));
+    CPF_HIP(ctx, hipMemsetAsync(t.sinkGroup, 0, nDerived, ctx->stream));
+    CPF_HIP(ctx, hipMemsetAsync(t.transfer, 0, (size_t)kTagMax * kTagMax * 8, ctx->stream));
+    CPF_HIP(ctx, hipMemsetAsync(t.field, 0, nField * 8, ctx->stream));
+    if (ctx->mesh.sourceKept > 0) {
+        CPF_HIP(ctx, t.originOfKept.alloc((size_t)ctx->mesh.sourceKept));
+        CPF_HIP(ctx, hipMemsetAsync(t.originOfKept, 0, (size_t)ctx->mesh.sourceKept, ctx->stream));
+    }
+    t.on = true; t.nOrigins = nOrigins; t.nSinks = nSinks;
+    ctx->tags = std::move(t);
+    return CPF_OK;
+}
+
+int cpf_tag_disable(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    return dropTags(ctx);
+}
+
+int cpf_set_sink_groups(cpf_context* ctx, const int32_t* parentCells, const int32_t* group, int64_t n) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_set_sink_groups: call cpf_tag_enable first");
+    CPF_REQUIRE(ctx, n >= 0 && ((parentCells && group) || n == 0), CPF_ERR_ARG, "cpf_set_sink_groups: bad arguments");
+    for (int64_t k = 0; k < n; ++k) {
+        CPF_REQUIRE(ctx, parentCells[k] >= 0 && parentCells[k] < ctx->mesh.nParent, CPF_ERR_ARG,
+                    "cpf_set_sink_groups: cell " + std::to_string(parentCells[k]) + " is not in [0, nCells)");
+        CPF_REQUIRE(ctx, group[k] >= 0 && group[k] < ctx->tags.nSinks, CPF_ERR_ARG,
+                    "cpf_set_sink_groups: group " + std::to_string(group[k]) + " is not in [0, nSinks)");
+    }
+    int r = cpf_set_sink_cells(ctx, parentCells, n);        // (the mask; it waits for the stream and puts everybody in group 0)
+    if (r || n == 0) return r;
+    std::vector<uint8_t> g((size_t)ctx->mesh.host.nCells, (uint8_t)0);
+    const bool derived = !ctx->mesh.first.empty();
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t c = parentCells[k];
+        const int64_t lo = derived ? ctx->mesh.first[(size_t)c] : c, hi = derived ? ctx->mesh.first[(size_t)c + 1] : c + 1;
+        for (int64_t d = lo; d < hi; ++d) g[(size_t)d] = (uint8_t)group[k];
+    }
+    CPF_HIP(ctx, hipMemcpy(ctx->tags.sinkGroup, g.data(), g.size(), hipMemcpyHostToDevice));
+    return CPF_OK;
+}
+
+int cpf_set_source_origins(cpf_context* ctx, const int32_t* originOfTriangle, int64_t nTriangles) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_set_source_origins: call cpf_tag_enable first");
+    CPF_REQUIRE(ctx, ctx->mesh.sourceKept > 0, CPF_ERR_STATE, "cpf_set_source_origins: call cpf_set_source_triangles first");
+    CPF_REQUIRE(ctx, originOfTriangle && nTriangles > 0, CPF_ERR_ARG, "cpf_set_source_origins: bad arguments");
+    for (int64_t t = 0; t < nTriangles; ++t)
+        CPF_REQUIRE(ctx, originOfTriangle[t] >= 0 && originOfTriangle[t] < ctx->tags.nOrigins, CPF_ERR_ARG,
+                    "cpf_set_source_origins: origin " + std::to_string(originOfTriangle[t]) + " is not in [0, nOrigins)");
+    // a kept record carries the index of the CALLER's triangle (dropped ones have no record)
+    std::vector<uint8_t> o((size_t)ctx->mesh.sourceKept);
+    for (size_t k = 0; k < o.size(); ++k) {
+        const int64_t t = (int64_t)ctx->mesh.sourceRecHost[k * cpf::kSourceDoubles + 14];
+        CPF_REQUIRE(ctx, t >= 0 && t < nTriangles, CPF_ERR_ARG,
+                    "cpf_set_source_origins: the source has a triangle " + std::to_string(t) + ", beyond nTriangles");
+        o[k] = (uint8_t)originOfTriangle[t];
+    }
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a stamp over the old origins may still be running)
+    CPF_HIP(ctx, hipMemcpy(ctx->tags.originOfKept, o.data(), o.size(), hipMemcpyHostToDevice));
+    return CPF_OK;
+}
+
+int cpf_set_box_origin(cpf_context* ctx, int32_t origin) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_set_box_origin: call cpf_tag_enable first");
+    CPF_REQUIRE(ctx, origin >= 0 && origin < ctx->tags.nOrigins, CPF_ERR_ARG,
+                "cpf_set_box_origin: origin " + std::to_string(origin) + " is not in [0, nOrigins)");
+    ctx->tags.boxOrigin = origin;
+    return CPF_OK;
+}
+
+int cpf_tag_sample(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_tag_sample: call cpf_tag_enable first");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, cpf::tag_field(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->tags.origin, ctx->cloud.n, ctx->mesh.parentOf,
+                                ctx->mesh.host.nCells, ctx->mesh.nParent, ctx->tags.nOrigins, ctx->tags.field));
+    ++ctx->tags.samples;
+    return CPF_OK;
+}
+
+int cpf_tag_reset(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_tag_reset: call cpf_tag_enable first");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemsetAsync(ctx->tags.transfer, 0, (size_t)kTagMax * kTagMax * 8, ctx->stream));
+    CPF_HIP(ctx, hipMemsetAsync(ctx->tags.field, 0, (size_t)ctx->mesh.nParent * ctx->tags.nOrigins * 8, ctx->stream));
+    ctx->tags.samples = 0;
+    return CPF_OK;
+}
+
+int cpf_get_transfer(cpf_context* ctx, uint64_t* T) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_get_transfer: call cpf_tag_enable first");
+    CPF_REQUIRE(ctx, T, CPF_ERR_ARG, "cpf_get_transfer: null array");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemcpyAsync(T, ctx->tags.transfer, (size_t)ctx->tags.nOrigins * ctx->tags.nSinks * 8, hipMemcpyDeviceToHost,
+                                ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPF_OK;
+}
+
+int cpf_get_tag_field(cpf_context* ctx, uint64_t* counts, int64_t* nSamples) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_get_tag_field: call cpf_tag_enable first");
+    if (nSamples) *nSamples = ctx->tags.samples;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    if (counts)
+        CPF_HIP(ctx, hipMemcpyAsync(counts, ctx->tags.field, (size_t)ctx->mesh.nParent * ctx->tags.nOrigins * 8, hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPF_OK;
+}
+
+int cpf_tag_get_origins(cpf_context* ctx, uint8_t* origin) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_tag_get_origins: call cpf_tag_enable first");
+    CPF_REQUIRE(ctx, origin, CPF_ERR_ARG, "cpf_tag_get_origins: null array");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemcpyAsync(origin, ctx->tags.origin, (size_t)ctx->cloud.n, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPF_OK;
+}
+
+int cpf_tag_set_origins(cpf_context* ctx, const uint8_t* origin) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_tag_set_origins: call cpf_tag_enable first");
+    CPF_REQUIRE(ctx, origin, CPF_ERR_ARG, "cpf_tag_set_origins: null array");
+    for (int64_t i = 0; i < ctx->cloud.n; ++i)
+        CPF_REQUIRE(ctx, (int32_t)origin[i] < ctx->tags.nOrigins, CPF_ERR_ARG,
+                    "cpf_tag_set_origins: origin " + std::to_string((int)origin[i]) + " is not in [0, nOrigins)");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemcpyAsync(ctx->tags.origin, origin, (size_t)ctx->cloud.n, hipMemcpyHostToDevice, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPF_OK;
+}
+
+int cpf_source_picks_host(uint32_t seed, const int64_t* gid, int64_t n, uint32_t epoch, const uint32_t* hi, int64_t nKept,
+                          int32_t* pick) {
+    if (n < 0 || !hi || nKept <= 0 || nKept > ((int64_t)1 << 24) || hi[nKept - 1] != 0xFFFFFFFFu || (n > 0 && !pick)) return CPF_ERR_ARG;
+    for (int64_t i = 0; i < n; ++i) {
+        uint32_t c[4];
+        cpf::source_words(seed, (uint64_t)(gid ? gid[i] : i), epoch, c);
+        pick[i] = cpf::source_pick(hi, (int)nKept, c[0]);
+    }
     return CPF_OK;
 }
 

@@ -311,6 +311,17 @@ hipError_t age_absorb(hipStream_t st, int32_t* cell, const int64_t* gid, const u
 hipError_t age_stamp(hipStream_t st, const int32_t* cell, const int64_t* gid, uint32_t* birth, int64_t n, uint32_t now);
 hipError_t age_field(hipStream_t st, const int32_t* cell, const int64_t* gid, const uint32_t* birth, int64_t n,
                      const int32_t* parentOf, int64_t nDerived, uint32_t now, unsigned long long* field);
+// tracer tags (cpf_tags.hip).  origin[id] (n bytes, id = gid[slot]; gid null: the slot) is the origin the respawn that last made
+// particle id live gave it, sinkGroup[d] the group of DERIVED cell d.  tag_transfer: reads only; transfer[origin * nSinks + group]
+// += 1 for every i that sink_apply would absorb (transfer: room for 16 x 16 words).  tag_stamp: for every slot with cell < 0,
+// origin[id] = boxOrigin (hi null), or originOfKept[source_pick(hi, nKept, source_words(seed, id, epoch)[0])].  tag_field: for
+// every i with 0 <= cell[i] < nDerived, field[parent * nOrigins + origin[id]] += 1 (parentOf null: the ids are parent ids already)
+hipError_t tag_transfer(hipStream_t st, const int32_t* cell, const int64_t* gid, const uint8_t* origin, int64_t n, const uint32_t* mask,
+                        int64_t nDerived, const uint8_t* sinkGroup, int32_t nOrigins, int32_t nSinks, unsigned long long* transfer);
+hipError_t tag_stamp(hipStream_t st, const int32_t* cell, const int64_t* gid, uint8_t* origin, int64_t n, const uint32_t* hi,
+                     int32_t nKept, const uint8_t* originOfKept, uint32_t seed, uint32_t epoch, int32_t boxOrigin);
+hipError_t tag_field(hipStream_t st, const int32_t* cell, const int64_t* gid, const uint8_t* origin, int64_t n, const int32_t* parentOf,
+                     int64_t nDerived, int64_t nParent, int32_t nOrigins, unsigned long long* field);
 hipError_t unpack_arrivals(hipStream_t st, double* x, double* y, double* z, int32_t* cell, int64_t* gid,
                            int64_t nStay, const double* recvbuf, int64_t nRecv);
 // output of a sharded cloud (cpf_shard_gather): records of kOutputDoubles doubles = x, y, z, cell, gid, vx, vy, vz

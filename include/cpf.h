@@ -541,6 +541,67 @@ int cpf_age_get_births(cpf_context* ctx, uint32_t* birth);
 int cpf_age_set_births(cpf_context* ctx, const uint32_t* birth);
 
 /* ---------------------------------------------------------------------------------------------
+ * tracer tags: where a particle of a recycled cloud came from and where it went
+ * NO REFERENCE COUNTERPART for any entry of this group.  The state is one byte per PARTICLE ID (the order of cpf_get_particles),
+ * origin[id] in [0, nOrigins): the origin that the respawn which last made the particle live gave it.  Sink cells are in groups,
+ * one byte per cell, in [0, nSinks).  nOrigins and nSinks are each in [1, 16], and nCells * nOrigins stays below 2^31.  Every sum
+ * is an integer, so the results are the same bits whatever the order of the cloud.  A table by id is moved by neither sort, and no
+ * step kernel knows of it.
+ * Tagging covers the CONTEXT-OWNED cloud only: cpf_shard_*, the _dev entries (cpf_sink_apply_dev, cpf_respawn_box_dev,
+ * cpf_respawn_source_dev) and the replacement fragments neither read nor write an origin.  While it is on,
+ *   cpf_sink_apply      first counts, in a read-only pass of its own, transfer[origin][group] += 1 for every particle it is about
+ *                       to absorb, then marks and counts exactly what it marks and counts without it -- with age tracking on or
+ *                       off: the residence-time histogram stays ONE histogram, not one per destination;
+ *   cpf_respawn_box     first gives every CANDIDATE (slot with cell < 0) the box's origin (cpf_set_box_origin; 0 by default), then
+ *                       places exactly the particles it places without it;
+ *   cpf_respawn_source  first gives every candidate the origin of the triangle that this call's epoch picks for its id
+ *                       (cpf_set_source_origins; 0 by default), then places exactly the particles it places without it.
+ * A candidate that a call leaves dead -- beyond maxCount, or drawn outside the mesh -- is stamped again by the call that places
+ * it.  The initial cloud has origin 0: number real sources from 1 to tell them from it.
+ * While it is off every call launches exactly what it launches without this group.
+ * The origins belong to a cloud, the groups and the field to a mesh: cpf_alloc_particles, cpf_seed_box, cpf_set_particles and
+ * cpf_set_mesh* turn tagging off.  Every entry but cpf_tag_enable, cpf_tag_disable and cpf_source_picks_host returns
+ * CPF_ERR_STATE while it is off.
+ * ------------------------------------------------------------------------------------------- */
+/* NO REFERENCE COUNTERPART.  Turns tagging on, or starts it anew: origin 0 for every particle, every sink cell in group 0, every
+ * source triangle and the box in origin 0, a zeroed transfer matrix, a zeroed field and a sample count of 0.  CPF_ERR_STATE without
+ * a mesh or without located particles; CPF_ERR_ARG unless 1 <= nOrigins <= 16, 1 <= nSinks <= 16 and nCells * nOrigins < 2^31. */
+int cpf_tag_enable(cpf_context* ctx, int32_t nOrigins, int32_t nSinks);
+/* NO REFERENCE COUNTERPART.  Turns tagging off and frees its tables (no error when it is off already). */
+int cpf_tag_disable(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  cpf_set_sink_cells(parentCells, n), and cell parentCells[k] is in group group[k] (a cell named twice:
+ * the last one holds).  CPF_ERR_ARG for a cell outside the mesh or a group outside [0, nSinks); the sink set is then unchanged.  A
+ * plain cpf_set_sink_cells while tagging is on puts all its cells in group 0. */
+int cpf_set_sink_groups(cpf_context* ctx, const int32_t* parentCells, const int32_t* group, int64_t n);
+/* NO REFERENCE COUNTERPART.  originOfTriangle[nTriangles] is indexed by the CALLER's triangle, the one cpf_set_source_triangles
+ * was given (triangles it dropped included).  CPF_ERR_STATE without a source; CPF_ERR_ARG for an origin outside [0, nOrigins) or
+ * fewer entries than the source has triangles.  cpf_set_source_triangles resets every triangle to origin 0. */
+int cpf_set_source_origins(cpf_context* ctx, const int32_t* originOfTriangle, int64_t nTriangles);
+/* NO REFERENCE COUNTERPART.  The origin cpf_respawn_box gives; CPF_ERR_ARG outside [0, nOrigins). */
+int cpf_set_box_origin(cpf_context* ctx, int32_t origin);
+/* NO REFERENCE COUNTERPART.  One sample of the per-origin occupancy: every live particle (cell >= 0) adds 1 to
+ * counts[its PARENT cell][its origin]; dead slots are skipped; the sample count goes up by one.  Summed over the origins it is what
+ * cpf_occupancy_sample would have added at the same point.  Asynchronous on the context's stream. */
+int cpf_tag_sample(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  Zeroes the transfer matrix, the field and the sample count (asynchronous); the origins stay. */
+int cpf_tag_reset(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  Waits for the context's stream; T[nOrigins][nSinks] = absorptions since the last reset of particles
+ * of that origin in cells of that group.  Their sum is what cpf_get_recycle_counts' `absorbed` went up by over the same calls. */
+int cpf_get_transfer(cpf_context* ctx, uint64_t* T);
+/* NO REFERENCE COUNTERPART.  Waits for the context's stream; counts[nCells][nOrigins] per PARENT cell (nullable) and *nSamples
+ * (nullable) since the last reset. */
+int cpf_get_tag_field(cpf_context* ctx, uint64_t* counts, int64_t* nSamples);
+/* NO REFERENCE COUNTERPART.  The origins, host arrays of n bytes in particle-id order, for checkpoint, restart and tests.  Both
+ * wait for the context's stream; cpf_tag_set_origins returns CPF_ERR_ARG for an origin outside [0, nOrigins). */
+int cpf_tag_get_origins(cpf_context* ctx, uint8_t* origin);
+int cpf_tag_set_origins(cpf_context* ctx, const uint8_t* origin);
+/* NO REFERENCE COUNTERPART.  pick[n]: the index of the kept record of the table (hi[nKept], cpf_source_table_host's) that
+ * cpf_respawn_source picks for the particles gid (NULL: 0 .. n-1) at `epoch` under `seed`: the kernels' own text, compiled for
+ * the host.  No context, no device. */
+int cpf_source_picks_host(uint32_t seed, const int64_t* gid, int64_t n, uint32_t epoch, const uint32_t* hi, int64_t nKept,
+                          int32_t* pick);
+
+/* ---------------------------------------------------------------------------------------------
  * device-array level (framework hosts that own the particle arrays, multi-GPU sharding)
  * SoA fp64 positions x,y,z [n]; cell [n] int32; gid [n] int64 global particle id (nullable:
  * gid = index); vel [n][3] (nullable unless CPF_STEP_STORE_VEL).

@@ -67,6 +67,13 @@ def collect_inlet():
     return parse(r.stderr, ("inlet_",))
 
 
+def collect_tags():
+    """The same rows for the tracer-tag kernels (cpf_tags.hip: tag_transfer_kernel, tag_stamp_kernel, tag_field_kernel); collect()
+    does not list them.  All their LDS is static."""
+    r = subprocess.run(hipcc_cmd("cpf_tags.hip") + ["-c", "-o", "/dev/null"], capture_output=True, text=True)
+    return parse(r.stderr, ("tag_",))
+
+
 def kernel_bodies(asm):
     """mangled kernel name -> its instructions (labels, directives and comments dropped).  Only what the listing types as a
     function: a library's constant table (rocprim has one) is a _Z label too, and the text behind the last one is the metadata."""
