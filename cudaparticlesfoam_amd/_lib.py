@@ -180,6 +180,12 @@ SIGNATURES = {
     "cpf_get_tag_field": (_int, [_ctx, _vp, C.POINTER(_i64)]),
     "cpf_tag_get_origins": (_int, [_ctx, _vp]),
     "cpf_tag_set_origins": (_int, [_ctx, _vp]),
+    "cpf_route_enable": (_int, [_ctx]),
+    "cpf_route_disable": (_int, [_ctx]),
+    "cpf_route_sample": (_int, [_ctx]),
+    "cpf_route_reset": (_int, [_ctx]),
+    "cpf_get_route_histogram": (_int, [_ctx, _vp]),
+    "cpf_get_route_field": (_int, [_ctx, _vp, _vp, C.POINTER(_i64)]),
     "cpf_source_picks_host": (_int, [_u32, _vp, _i64, _u32, _vp, _i64, _vp]),
     "cpf_set_velocity": (_int, [_ctx, _vp, _i64]),
     "cpf_set_velocity_dev": (_int, [_ctx, _vp, _i64]),

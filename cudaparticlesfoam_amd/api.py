@@ -459,6 +459,56 @@ class Context:
         np.divide(c, total[None, :], out=out, where=(total > 0)[None, :])
         return out
 
+    # -- routes: the residence time per origin and sink group (include/cpf.h "routes")
+    def route_enable(self):
+        """Turns routes on (or starts them anew); needs ``age_enable`` and ``tag_enable``.  ``sink_apply`` then runs one pass for
+        the transfer matrix, the age histogram and the histogram per route."""
+        self._ck(self.lib.cpf_route_enable(self.h))
+
+    def route_disable(self):
+        self._ck(self.lib.cpf_route_disable(self.h))
+
+    def route_sample(self):
+        """One sample of the age field per origin: every live particle adds its age and 1 to (its cell, its origin); asynchronous."""
+        self._ck(self.lib.cpf_route_sample(self.h))
+
+    def route_reset(self):
+        """Zeroes the route histogram, the route field and their sample count, and nothing of age or tags."""
+        self._ck(self.lib.cpf_route_reset(self.h))
+
+    def route_histogram(self) -> np.ndarray:
+        """uint64 [n_origins][n_sinks][n_bins]: absorptions since the last reset by route and age // bin_cycles; synchronises."""
+        n_bins = getattr(self, "_age_bins", (1, 1))[1]
+        h = np.zeros(getattr(self, "_tag_shape", (1, 1)) + (n_bins,), np.uint64)
+        self._ck(self.lib.cpf_get_route_histogram(self.h, _ptr(h)))
+        return h
+
+    def route_field(self):
+        """(age_sum uint64 [n_cells][n_origins], count uint64 [n_cells][n_origins], n_samples) per parent cell since the last
+        reset; synchronises."""
+        n_origins = getattr(self, "_tag_shape", (1, 1))[0]
+        s, c = np.zeros((self.n_cells, n_origins), np.uint64), np.zeros((self.n_cells, n_origins), np.uint64)
+        ns = C.c_int64(0)
+        self._ck(self.lib.cpf_get_route_field(self.h, _ptr(s), _ptr(c), C.byref(ns)))
+        return s, c, ns.value
+
+    def rtd_by_route(self, dt: float):
+        """Residence-time distribution per route: (edges in seconds [n_bins + 1], counts uint64 [n_origins][n_sinks][n_bins]);
+        the edges are ``rtd``'s."""
+        counts = self.route_histogram()
+        bin_cycles, n_bins = self._age_bins
+        edges = np.arange(n_bins + 1, dtype=np.float64) * (bin_cycles * float(dt))
+        edges[-1] = np.inf
+        return edges, counts
+
+    def mean_age_by_origin(self, dt: float) -> np.ndarray:
+        """[n_cells][n_origins]: mean age in seconds of the particles of each origin found in a cell over the samples taken, NaN
+        where none was."""
+        s, c, _ = self.route_field()
+        out = np.full(s.shape, np.nan)
+        np.divide(s.astype(np.float64), c.astype(np.float64), out=out, where=c > 0)
+        return out * float(dt)
+
     def cell_ranges_dev(self, weights, n_ranks, cell_lo):
         self._ck(self.lib.cpf_cell_ranges_dev(self.h, weights, n_ranks, cell_lo))
 
@@ -786,6 +836,10 @@ class CudaParticles:
     origins (1 where the key is absent), once the cloud is located: every absorption adds to ``transfer()[origin, group]``, and
     wherever an occupancy sample is taken the per-origin field is sampled too, for ``origin_fraction()``.  The initial cloud has
     origin 0, so number real sources from 1 to tell it apart.
+
+    One more: ``routeStats`` (default false), which needs ``ageBins`` > 0 and tagging.  Routes (``Context.route_enable``) then start
+    behind age tracking and tagging: every absorption also adds to ``rtd_by_route()``, and wherever the age field is sampled the
+    age field per origin is sampled too, for ``mean_age_by_origin()``.
     """
 
     def __init__(self, mesh, U, particle_dict: Optional[dict] = None, device: int = 0,
@@ -815,6 +869,9 @@ class CudaParticles:
             raise ValueError("sinkGroups needs recycleInterval > 0 and sinkCells")
         if self.sourceOrigins is not None and (self.recycleInterval <= 0 or self.sourceTriangles is None):
             raise ValueError("sourceOrigins needs recycleInterval > 0 and sourceTriangles")
+        self.routeStats = bool(d.get("routeStats", False))
+        if self.routeStats and not (self.ageBins > 0 and self.tags):
+            raise ValueError("routeStats needs ageBins > 0 and tagging (sinkGroups or sourceOrigins)")
         # hard-coded switches of the fragment (src/initCuda.H:64-72)
         self.usingAdvection = True
         self.usingBrownianMotion = True
@@ -849,6 +906,8 @@ class CudaParticles:
                 self.ctx.set_sink_groups(self.sinkCells, self.sinkGroups)
             if self.sourceOrigins is not None:
                 self.ctx.set_source_origins(self.sourceOrigins)
+        if self.routeStats:
+            self.ctx.route_enable()
         if self.writer is not None:
             # frame 0 carries the velocities of one advect and out-of-domain particles as inactive, like the reference
             # (src/initCuda.H:184-201): a cycle of zero length (moves nothing, does not count as a step)
@@ -901,6 +960,8 @@ class CudaParticles:
                     self.ctx.age_sample()
                 if self.tags:
                     self.ctx.tag_sample()
+                if self.routeStats:
+                    self.ctx.route_sample()
         return n_cycles
 
     def particles(self):
@@ -930,6 +991,16 @@ class CudaParticles:
         """Each origin's share per cell over the samples ``occupancyInterval`` took, NaN where no particle was found
         (``Context.origin_fraction``)."""
         return self.ctx.origin_fraction()
+
+    def rtd_by_route(self):
+        """Residence-time distribution per (origin, sink group), (edges in seconds, counts), with ``routeStats`` set
+        (``Context.rtd_by_route``)."""
+        return self.ctx.rtd_by_route(self.dt)
+
+    def mean_age_by_origin(self):
+        """Mean age in seconds per cell and origin over the samples ``occupancyInterval`` took, with ``routeStats`` set
+        (``Context.mean_age_by_origin``)."""
+        return self.ctx.mean_age_by_origin(self.dt)
 
     def close(self):
         self.ctx.close()

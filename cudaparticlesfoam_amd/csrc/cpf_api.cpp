@@ -128,6 +128,15 @@ struct Tags {
 };
 constexpr int32_t kTagMax = 16;
 
+// Routes of the context's own cloud (cpf_route_*; cpf_routes.hip): tables sized by age's nBins and tags' nOrigins, nSinks, so the
+// group lives only while both are on and is replaced by an empty one with either of them.
+struct Routes {
+    bool on = false;
+    DevBuf<unsigned long long> hist;        // [nOrigins][nSinks][nBins] absorptions by route and age / binCycles
+    DevBuf<unsigned long long> field;       // [nParent][nOrigins][2] = age sum, count of the samples since the last reset
+    int64_t samples = 0;
+};
+
 // asynchronous output (cpf_write_vtu_async): one frame in flight.  Lives as long as the context.
 struct FrameWriter {
     std::thread thread;
@@ -200,7 +209,7 @@ struct cpf_context {
     bool vertexFast = true;                     // cpf_set_option("vertex_fast")
     uint32_t seed = 1591593751u;                // cuda/particles.cu:544
     // ---- the groups
-    Mesh mesh; TetField tet; Cloud cloud; Age age; Tags tags; FrameWriter frame; Timing timing;
+    Mesh mesh; TetField tet; Cloud cloud; Age age; Tags tags; Routes routes; FrameWriter frame; Timing timing;
     // ---- what lives as long as the context
     DevBuf<char> scratch;
     size_t scratchBytes = 0;
@@ -297,11 +306,21 @@ int ensureScratch(cpf_context* ctx, size_t bytes) {
     return CPF_OK;
 }
 
+// routes off (cpf_route_disable; age or tags going off or starting anew): a pass over the tables may still be running
+int dropRoutes(cpf_context* ctx) {
+    if (!ctx->routes.on) return CPF_OK;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->routes = Routes{};
+    return CPF_OK;
+}
+
 // age tracking off (cpf_age_disable, a new cloud): a pass over the stamps may still be running
 int dropAge(cpf_context* ctx) {
     if (!ctx->age.on) return CPF_OK;
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->routes = Routes{};                                 // (sized by nBins)
     ctx->age = Age{};
     return CPF_OK;
 }
@@ -311,6 +330,7 @@ int dropTags(cpf_context* ctx) {
     if (!ctx->tags.on) return CPF_OK;
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->routes = Routes{};                                 // (sized by nOrigins and nSinks)
     ctx->tags = Tags{};
     return CPF_OK;
 }
@@ -369,6 +389,7 @@ int setMeshImpl(cpf_context* ctx, const double* points, int64_t nPoints, const L
     ctx->tet = TetField{};
     ctx->age = Age{};
     ctx->tags = Tags{};
+    ctx->routes = Routes{};
     ctx->streamState.flatField = false;
     ctx->mesh.host = std::move(t);
     ctx->mesh.nParent = nCells;
@@ -917,6 +938,7 @@ int cpf_alloc_particles(cpf_context* ctx, int64_t capacity) {
     ctx->cloud = Cloud{};
     ctx->age = Age{};
     ctx->tags = Tags{};
+    ctx->routes = Routes{};
     const size_t c = (size_t)capacity;
     CPF_HIP(ctx, ctx->cloud.cur.alloc(c));
     CPF_HIP(ctx, ctx->cloud.vel.alloc(c * 3));
@@ -1486,6 +1508,19 @@ int cpf_sink_apply(cpf_context* ctx) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_sink_apply: call cpf_set_mesh first");
     CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_sink_apply: no located particles");
+    if (ctx->routes.on) {
+        // routes (so tags and age are on): ONE pass in place of the two below, which adds what they add and the joint histogram
+        // besides (cpf_routes.hip)
+        if (!ctx->mesh.sinkMask) return CPF_OK;
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        int r = ensureRecycleCounts(ctx);
+        if (r) return r;
+        CPF_HIP(ctx, cpf::route_absorb(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->age.birth, ctx->tags.origin, ctx->cloud.n,
+                                       ctx->mesh.sinkMask, ctx->mesh.host.nCells, ctx->tags.sinkGroup, ctx->recycleCounts,
+                                       ctx->stepCounter, ctx->age.binCycles, ctx->age.nBins, ctx->tags.nOrigins, ctx->tags.nSinks,
+                                       ctx->age.hist, ctx->tags.transfer, ctx->routes.hist));
+        return CPF_OK;
+    }
     if (ctx->tags.on && ctx->mesh.sinkMask) {
         // tagging: a read-only pass of its own counts (origin, sink group) of everybody the sink is about to absorb (cpf_tags.hip)
         CPF_HIP(ctx, hipSetDevice(ctx->device));
@@ -1766,6 +1801,7 @@ int cpf_age_enable(cpf_context* ctx, int32_t binCycles, int32_t nBins) {
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass over the old tables may still be running)
     ctx->age = Age{};
+    ctx->routes = Routes{};                                 // (nBins may change)
     Age a;                                                  // moved in whole: a failure part-way leaves tracking off
     const size_t n = (size_t)ctx->cloud.n, nField = (size_t)ctx->mesh.nParent * 2;
     CPF_HIP(ctx, a.birth.alloc(n));
@@ -1884,6 +1920,7 @@ int cpf_tag_enable(cpf_context* ctx, int32_t nOrigins, int32_t nSinks) {
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass over the old tables may still be running)
     ctx->tags = Tags{};
+    ctx->routes = Routes{};                                 // (nOrigins and nSinks may change)
     Tags t;                                                 // moved in whole: a failure part-way leaves tagging off
     const size_t n = (size_t)ctx->cloud.n, nDerived = (size_t)ctx->mesh.host.nCells, nField = (size_t)ctx->mesh.nParent * nOrigins;
     CPF_HIP(ctx, t.origin.alloc(n));
@@ -2025,6 +2062,78 @@ int cpf_tag_set_origins(cpf_context* ctx, const uint8_t* origin) {
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, hipMemcpyAsync(ctx->tags.origin, origin, (size_t)ctx->cloud.n, hipMemcpyHostToDevice, ctx->stream));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPF_OK;
+}
+
+// ---- routes: the residence-time histogram per (origin, sink group), the age field per origin (cpf_routes.hip) ---------------
+int cpf_route_enable(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->age.on && ctx->tags.on, CPF_ERR_STATE, "cpf_route_enable: call cpf_age_enable and cpf_tag_enable first");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass over the old tables may still be running)
+    ctx->routes = Routes{};
+    Routes t;                                               // moved in whole: a failure part-way leaves routes off
+    const size_t nHist = (size_t)ctx->tags.nOrigins * ctx->tags.nSinks * ctx->age.nBins,
+                 nField = (size_t)ctx->mesh.nParent * ctx->tags.nOrigins * 2;
+    CPF_HIP(ctx, t.hist.alloc(nHist));
+    CPF_HIP(ctx, t.field.alloc(nField));
+    CPF_HIP(ctx, hipMemsetAsync(t.hist, 0, nHist * 8, ctx->stream));
+    CPF_HIP(ctx, hipMemsetAsync(t.field, 0, nField * 8, ctx->stream));
+    t.on = true;
+    ctx->routes = std::move(t);
+    return CPF_OK;
+}
+
+int cpf_route_disable(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    return dropRoutes(ctx);
+}
+
+int cpf_route_sample(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->routes.on, CPF_ERR_STATE, "cpf_route_sample: call cpf_route_enable first");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, cpf::route_field(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->age.birth, ctx->tags.origin, ctx->cloud.n,
+                                  ctx->mesh.parentOf, ctx->mesh.host.nCells, ctx->mesh.nParent, ctx->tags.nOrigins, ctx->stepCounter,
+                                  ctx->routes.field));
+    ++ctx->routes.samples;
+    return CPF_OK;
+}
+
+int cpf_route_reset(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->routes.on, CPF_ERR_STATE, "cpf_route_reset: call cpf_route_enable first");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemsetAsync(ctx->routes.hist, 0, (size_t)ctx->tags.nOrigins * ctx->tags.nSinks * ctx->age.nBins * 8, ctx->stream));
+    CPF_HIP(ctx, hipMemsetAsync(ctx->routes.field, 0, (size_t)ctx->mesh.nParent * ctx->tags.nOrigins * 16, ctx->stream));
+    ctx->routes.samples = 0;
+    return CPF_OK;
+}
+
+int cpf_get_route_histogram(cpf_context* ctx, uint64_t* bins) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->routes.on, CPF_ERR_STATE, "cpf_get_route_histogram: call cpf_route_enable first");
+    CPF_REQUIRE(ctx, bins, CPF_ERR_ARG, "cpf_get_route_histogram: null array");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemcpyAsync(bins, ctx->routes.hist, (size_t)ctx->tags.nOrigins * ctx->tags.nSinks * ctx->age.nBins * 8,
+                                hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPF_OK;
+}
+
+int cpf_get_route_field(cpf_context* ctx, uint64_t* ageSum, uint64_t* count, int64_t* nSamples) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->routes.on, CPF_ERR_STATE, "cpf_get_route_field: call cpf_route_enable first");
+    if (nSamples) *nSamples = ctx->routes.samples;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nv = (size_t)ctx->mesh.nParent * ctx->tags.nOrigins;
+    std::vector<unsigned long long> h(nv * 2);
+    if (ageSum || count) CPF_HIP(ctx, hipMemcpyAsync(h.data(), ctx->routes.field, nv * 16, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t c = 0; c < nv; ++c) {
+        if (ageSum) ageSum[c] = h[2 * c];
+        if (count) count[c] = h[2 * c + 1];
+    }
     return CPF_OK;
 }
 

@@ -322,6 +322,17 @@ hipError_t tag_stamp(hipStream_t st, const int32_t* cell, const int64_t* gid, ui
                      int32_t nKept, const uint8_t* originOfKept, uint32_t seed, uint32_t epoch, int32_t boxOrigin);
 hipError_t tag_field(hipStream_t st, const int32_t* cell, const int64_t* gid, const uint8_t* origin, int64_t n, const int32_t* parentOf,
                      int64_t nDerived, int64_t nParent, int32_t nOrigins, unsigned long long* field);
+// routes (cpf_routes.hip), on age's birth[] and tags' origin[] and sinkGroup[].  route_absorb: sink_apply, and for every particle
+// it absorbs the adds of tag_transfer and age_absorb and routeHist[(origin * nSinks + group) * nBins + min(age / binCycles,
+// nBins - 1)] += 1.  route_field: for every i with 0 <= cell[i] < nDerived, field[2 * v] += age and field[2 * v + 1] += 1 with
+// v = parent * nOrigins + origin[id] (parentOf null: the ids are parent ids already)
+hipError_t route_absorb(hipStream_t st, int32_t* cell, const int64_t* gid, const uint32_t* birth, const uint8_t* origin, int64_t n,
+                        const uint32_t* mask, int64_t nDerived, const uint8_t* sinkGroup, unsigned long long* absorbed, uint32_t now,
+                        int32_t binCycles, int32_t nBins, int32_t nOrigins, int32_t nSinks, unsigned long long* hist,
+                        unsigned long long* transfer, unsigned long long* routeHist);
+hipError_t route_field(hipStream_t st, const int32_t* cell, const int64_t* gid, const uint32_t* birth, const uint8_t* origin, int64_t n,
+                       const int32_t* parentOf, int64_t nDerived, int64_t nParent, int32_t nOrigins, uint32_t now,
+                       unsigned long long* field);
 hipError_t unpack_arrivals(hipStream_t st, double* x, double* y, double* z, int32_t* cell, int64_t* gid,
                            int64_t nStay, const double* recvbuf, int64_t nRecv);
 // output of a sharded cloud (cpf_shard_gather): records of kOutputDoubles doubles = x, y, z, cell, gid, vx, vy, vz

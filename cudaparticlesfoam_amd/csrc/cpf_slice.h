@@ -69,15 +69,15 @@ __device__ inline void load_slice(const int32_t* __restrict__ cell, int64_t n, b
 // The sink's pass over a slice.  The sink set is a bitmask over DERIVED cells; a mask of at most kSinkLdsWords words is staged in
 // LDS while the loads are in flight (pitzDaily: 383 words), a larger one is read through L2 (a cell-sorted slice touches a handful
 // of its words).  The hits of a wave are counted with ballot + popcount and summed per workgroup: returns that sum, in every
-// thread, behind a barrier.  kHit: `hit` gets the lane's own hits, bit 4 k + j: element j of quad k was absorbed.
+// thread, behind a barrier.  kHit: `hit` gets the lane's own hits, bit 4 k + j: element j of quad k was absorbed.  `v` gets the
+// lane's quads as they were loaded, BEFORE the pass marked anybody (cpf_routes.hip asks a hit's cell for its sink group).
 template <bool kVec, bool kHit>
 __device__ inline unsigned sink_pass(int32_t* __restrict__ cell, int64_t n, const uint32_t* __restrict__ mask, int nDerived,
-                                     int maskWords, unsigned& hit) {
+                                     int maskWords, unsigned& hit, int4 (&v)[kSliceLoads]) {
     __shared__ uint32_t sMask[kSinkLdsWords];
     __shared__ unsigned sHits;
     const int lane = threadIdx.x & 63;
     const int64_t base = slice_base<kSliceLoads>();
-    int4 v[kSliceLoads];
     load_slice(cell, n, kVec, 0, v);                        // (past the end: 0, which is neither in a sink nor dead)
     const bool staged = maskWords <= kSinkLdsWords;
     if (staged)
@@ -119,6 +119,13 @@ __device__ inline unsigned sink_pass(int32_t* __restrict__ cell, int64_t n, cons
     if (lane == 0 && hits != 0u) atomicAdd(&sHits, hits);
     __syncthreads();
     return sHits;
+}
+// (the same for a kernel that has no use for the loaded quads)
+template <bool kVec, bool kHit>
+__device__ inline unsigned sink_pass(int32_t* __restrict__ cell, int64_t n, const uint32_t* __restrict__ mask, int nDerived,
+                                     int maskWords, unsigned& hit) {
+    int4 v[kSliceLoads];
+    return sink_pass<kVec, kHit>(cell, n, mask, nDerived, maskWords, hit, v);
 }
 
 // bit 4 k + j: element j of quad k is a dead slot, cell < 0 (past the end: pad the loads with 0)

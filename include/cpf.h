@@ -551,7 +551,8 @@ int cpf_age_set_births(cpf_context* ctx, const uint32_t* birth);
  * cpf_respawn_source_dev) and the replacement fragments neither read nor write an origin.  While it is on,
  *   cpf_sink_apply      first counts, in a read-only pass of its own, transfer[origin][group] += 1 for every particle it is about
  *                       to absorb, then marks and counts exactly what it marks and counts without it -- with age tracking on or
- *                       off: the residence-time histogram stays ONE histogram, not one per destination;
+ *                       off: cpf_get_age_histogram stays ONE histogram, not one per destination (the routes group below keeps
+ *                       the one per origin and sink group, and then does all of this in a single pass);
  *   cpf_respawn_box     first gives every CANDIDATE (slot with cell < 0) the box's origin (cpf_set_box_origin; 0 by default), then
  *                       places exactly the particles it places without it;
  *   cpf_respawn_source  first gives every candidate the origin of the triangle that this call's epoch picks for its id
@@ -600,6 +601,44 @@ int cpf_tag_set_origins(cpf_context* ctx, const uint8_t* origin);
  * the host.  No context, no device. */
 int cpf_source_picks_host(uint32_t seed, const int64_t* gid, int64_t n, uint32_t epoch, const uint32_t* hi, int64_t nKept,
                           int32_t* pick);
+
+/* ---------------------------------------------------------------------------------------------
+ * routes: the residence time per origin and sink group (route = origin x sink group)
+ * NO REFERENCE COUNTERPART for any entry of this group.  It keeps nothing per particle: it reads the stamps of age tracking and the
+ * origins and sink groups of tagging together, and exists only while BOTH are on.  nOrigins, nSinks, nBins and binCycles below are
+ * the values cpf_tag_enable and cpf_age_enable were given.  Its state is two tables of 64-bit integers,
+ *   routeHist[nOrigins][nSinks][nBins]   an absorbed particle of origin o in a sink cell of group g with age a (cycles, as in the age
+ *                                        group) adds 1 to bin min(a / binCycles, nBins - 1) of route (o, g);
+ *   routeField[nCells][nOrigins]         age sum and count per PARENT cell and origin, over the samples taken,
+ * so every result is the same bits whatever the order of the cloud.  Summed over its bins routeHist is cpf_get_transfer's matrix,
+ * summed over its routes cpf_get_age_histogram's; routeField's counts are cpf_get_tag_field's and its age sums, summed over the
+ * origins, cpf_get_age_field's -- each over the same calls since a common reset.
+ * Routes cover the CONTEXT-OWNED cloud only, like age and tags: not cpf_shard_*, not the _dev entries, not the replacement
+ * fragments.  While they are on, cpf_sink_apply runs ONE pass in place of the tagging pass and the age pass: it marks exactly the
+ * particles it marks without them and adds the same numbers to `absorbed`, to the transfer matrix and to the age histogram, and
+ * adds to routeHist besides.  While they are off every call launches exactly what it launches without this group.
+ * Everything that turns age tracking or tagging off, or starts either anew, turns routes off (the sizes may have changed):
+ * cpf_age_enable, cpf_age_disable, cpf_tag_enable, cpf_tag_disable, cpf_alloc_particles, cpf_seed_box, cpf_set_particles and
+ * cpf_set_mesh*.  Every entry but cpf_route_enable and cpf_route_disable returns CPF_ERR_STATE while they are off.
+ * ------------------------------------------------------------------------------------------- */
+/* NO REFERENCE COUNTERPART.  Turns routes on, or starts them anew: both tables zeroed, a sample count of 0.  CPF_ERR_STATE unless
+ * age tracking and tagging are both on. */
+int cpf_route_enable(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  Turns routes off and frees their tables (no error when they are off already). */
+int cpf_route_disable(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  One sample of the age field per origin: every live particle (cell >= 0) adds its age to the sum of
+ * (its PARENT cell, its origin) and 1 to the count; dead slots are skipped, as cpf_age_sample and cpf_tag_sample skip them; the
+ * sample count goes up by one.  Asynchronous on the context's stream. */
+int cpf_route_sample(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  Zeroes routeHist, routeField and their sample count (asynchronous) and nothing else: cpf_age_reset and
+ * cpf_tag_reset in turn leave the route tables alone. */
+int cpf_route_reset(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  Waits for the context's stream; bins[nOrigins][nSinks][nBins] since the last cpf_route_reset. */
+int cpf_get_route_histogram(cpf_context* ctx, uint64_t* bins);
+/* NO REFERENCE COUNTERPART.  Waits for the context's stream; ageSum[nCells][nOrigins], count[nCells][nOrigins] per PARENT cell and
+ * *nSamples since the last cpf_route_reset (each nullable).  The mean age in a cell of the tracer from origin o is
+ * ageSum / count cycles. */
+int cpf_get_route_field(cpf_context* ctx, uint64_t* ageSum, uint64_t* count, int64_t* nSamples);
 
 /* ---------------------------------------------------------------------------------------------
  * device-array level (framework hosts that own the particle arrays, multi-GPU sharding)

@@ -74,6 +74,14 @@ def collect_tags():
     return parse(r.stderr, ("tag_",))
 
 
+def collect_routes():
+    """The same rows for the route kernels (cpf_routes.hip: route_absorb_kernel, route_field_kernel); collect() does not list
+    them.  The absorb kernel's LDS is its static part: its age histogram and its staged joint histogram (4 bytes a word, 32 KB
+    at most) are dynamic."""
+    r = subprocess.run(hipcc_cmd("cpf_routes.hip") + ["-c", "-o", "/dev/null"], capture_output=True, text=True)
+    return parse(r.stderr, ("route_",))
+
+
 def kernel_bodies(asm):
     """mangled kernel name -> its instructions (labels, directives and comments dropped).  Only what the listing types as a
     function: a library's constant table (rocprim has one) is a _Z label too, and the text behind the last one is the metadata."""
