@@ -186,6 +186,16 @@ SIGNATURES = {
     "cpf_route_reset": (_int, [_ctx]),
     "cpf_get_route_histogram": (_int, [_ctx, _vp]),
     "cpf_get_route_field": (_int, [_ctx, _vp, _vp, C.POINTER(_i64)]),
+    "cpf_exposure_enable": (_int, [_ctx, _dbl, _i32]),
+    "cpf_exposure_disable": (_int, [_ctx]),
+    "cpf_set_exposure_field": (_int, [_ctx, _vp, _i64]),
+    "cpf_exposure_accumulate": (_int, [_ctx, _dbl]),
+    "cpf_exposure_reset": (_int, [_ctx]),
+    "cpf_get_dose_histogram": (_int, [_ctx, _vp]),
+    "cpf_get_doses": (_int, [_ctx, _vp]),
+    "cpf_exposure_get_doses": (_int, [_ctx, _vp]),
+    "cpf_exposure_set_doses": (_int, [_ctx, _vp]),
+    "cpf_exposure_bins_host": (_int, [_vp, _i64, _dbl, _i32, _vp]),
     "cpf_source_picks_host": (_int, [_u32, _vp, _i64, _u32, _vp, _i64, _vp]),
     "cpf_set_velocity": (_int, [_ctx, _vp, _i64]),
     "cpf_set_velocity_dev": (_int, [_ctx, _vp, _i64]),

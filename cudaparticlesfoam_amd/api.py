@@ -509,6 +509,70 @@ class Context:
         np.divide(s.astype(np.float64), c.astype(np.float64), out=out, where=c > 0)
         return out * float(dt)
 
+    # -- exposure: a dose per particle summed along its path, the dose histogram at the sink (include/cpf.h "exposure")
+    def exposure_enable(self, bin_width: float, n_bins: int = 1):
+        """Turns exposure of the context-owned cloud on (or starts it anew): every dose is 0, the rate field all zero; ``n_bins``
+        dose bins of ``bin_width``, the last one open-ended, per (origin, sink group) if tagging is on at this moment."""
+        self._ck(self.lib.cpf_exposure_enable(self.h, float(bin_width), int(n_bins)))
+        self._dose_bins = (float(bin_width), int(n_bins), getattr(self, "_tag_shape", (1, 1)) if self._tags_on() else (1, 1))
+
+    def _tags_on(self) -> bool:
+        """Whether tagging is on in the library right now: a new cloud or mesh turns it off behind ``_tag_shape``'s back, and
+        the read-back of the transfer matrix (room for 16 x 16) answers if and only if it is on."""
+        t = np.zeros(256, np.uint64)
+        return self.lib.cpf_get_transfer(self.h, _ptr(t)) == L.CPF_OK
+
+    def exposure_disable(self):
+        self._ck(self.lib.cpf_exposure_disable(self.h))
+
+    def set_exposure_field(self, rate):
+        """One rate per cell of the mesh as given, finite and >= 0: what a particle in that cell accumulates per unit of
+        ``exposure_accumulate``'s scale."""
+        r = np.ascontiguousarray(rate, dtype=np.float64).reshape(-1)
+        self._ck(self.lib.cpf_set_exposure_field(self.h, _ptr(r) if r.size else None, r.size))
+
+    def exposure_accumulate(self, scale: float):
+        """dose += scale * rate[cell] for every live particle; asynchronous."""
+        self._ck(self.lib.cpf_exposure_accumulate(self.h, float(scale)))
+
+    def exposure_reset(self):
+        """Zeroes the dose histogram; the doses stay."""
+        self._ck(self.lib.cpf_exposure_reset(self.h))
+
+    def dose_histogram(self) -> np.ndarray:
+        """uint64 [n_origins][n_sinks][n_bins]: absorptions since the last reset by origin, sink group and dose bin; synchronises."""
+        _, n_bins, shape = getattr(self, "_dose_bins", (1.0, 1, (1, 1)))
+        h = np.zeros(tuple(shape) + (n_bins,), np.uint64)
+        self._ck(self.lib.cpf_get_dose_histogram(self.h, _ptr(h)))
+        return h
+
+    def doses(self) -> np.ndarray:
+        """float64 [n] in particle-id order: the dose, -1 for a dead slot; synchronises."""
+        d = np.empty(self.n, np.float64)
+        self._ck(self.lib.cpf_get_doses(self.h, _ptr(d)))
+        return d
+
+    def exposure_doses(self) -> np.ndarray:
+        """float64 [n] in particle-id order: the dose table itself, dead slots included (checkpoints)."""
+        d = np.empty(self.n, np.float64)
+        self._ck(self.lib.cpf_exposure_get_doses(self.h, _ptr(d)))
+        return d
+
+    def exposure_set_doses(self, doses):
+        d = np.ascontiguousarray(doses, dtype=np.float64).reshape(-1)
+        if d.size != self.n:
+            raise ValueError("exposure_set_doses: %d doses for %d particles" % (d.size, self.n))
+        self._ck(self.lib.cpf_exposure_set_doses(self.h, _ptr(d)))
+
+    def dose_distribution(self):
+        """Dose distribution at the sink: (edges [n_bins + 1], counts uint64 [n_origins][n_sinks][n_bins]); the last bin is
+        open-ended (its upper edge is inf)."""
+        counts = self.dose_histogram()
+        bin_width, n_bins, _ = self._dose_bins
+        edges = np.arange(n_bins + 1, dtype=np.float64) * bin_width
+        edges[-1] = np.inf
+        return edges, counts
+
     def cell_ranges_dev(self, weights, n_ranks, cell_lo):
         self._ck(self.lib.cpf_cell_ranges_dev(self.h, weights, n_ranks, cell_lo))
 
@@ -788,10 +852,10 @@ DICT_DEFAULTS = dict(                       # src/initCuda.H:49-57 (getOrDefault
 
 
 def _next_chunk(step: int, remaining: int, save_interval: int, occupancy_interval: int, has_writer: bool,
-                will_write: bool, recycle_interval: int = 0) -> int:
+                will_write: bool, recycle_interval: int = 0, *, exposure_interval: int = 0) -> int:
     """Cycles the next launch of ``CudaParticles.advect`` fuses: a cycle that writes a frame runs alone; otherwise everything up
     to the next output point (with a writer), the next occupancy sample (``occupancy_interval`` > 0), the next recycle point
-    (``recycle_interval`` > 0) and the end of the call."""
+    (``recycle_interval`` > 0), the next exposure point (``exposure_interval`` > 0) and the end of the call."""
     if will_write:
         return 1
     chunk = remaining
@@ -801,6 +865,8 @@ def _next_chunk(step: int, remaining: int, save_interval: int, occupancy_interva
         chunk = min(chunk, occupancy_interval - (step % occupancy_interval))
     if recycle_interval > 0:
         chunk = min(chunk, recycle_interval - (step % recycle_interval))
+    if exposure_interval > 0:
+        chunk = min(chunk, exposure_interval - (step % exposure_interval))
     return max(1, chunk)
 
 
@@ -840,6 +906,13 @@ class CudaParticles:
     One more: ``routeStats`` (default false), which needs ``ageBins`` > 0 and tagging.  Routes (``Context.route_enable``) then start
     behind age tracking and tagging: every absorption also adds to ``rtd_by_route()``, and wherever the age field is sampled the
     age field per origin is sampled too, for ``mean_age_by_origin()``.
+
+    Four more: ``exposureField`` (one rate per cell, per second, finite and >= 0; default None = off), ``exposureInterval`` (cycles;
+    default 1), ``doseBins`` (default 1) and ``doseBinWidth`` (needed when ``doseBins`` > 1).  With a field, exposure
+    (``Context.exposure_enable``) starts behind age tracking, tagging and routes: at every cycle count that is a multiple of
+    ``exposureInterval`` every live particle adds (the time since the last such point) x (the rate of the cell it is in) to its
+    dose, before the recycle point's absorption if one is due; every absorption adds to ``dose_distribution()``, and a respawned
+    particle starts from 0.
     """
 
     def __init__(self, mesh, U, particle_dict: Optional[dict] = None, device: int = 0,
@@ -872,6 +945,27 @@ class CudaParticles:
         self.routeStats = bool(d.get("routeStats", False))
         if self.routeStats and not (self.ageBins > 0 and self.tags):
             raise ValueError("routeStats needs ageBins > 0 and tagging (sinkGroups or sourceOrigins)")
+        self.exposureField = d.get("exposureField", None)
+        self.exposureInterval = int(d.get("exposureInterval", 1))
+        self.doseBins = int(d.get("doseBins", 1))
+        self.doseBinWidth = d.get("doseBinWidth", None)
+        if self.exposureField is None:
+            if any(k in d for k in ("exposureInterval", "doseBins", "doseBinWidth")):
+                raise ValueError("exposureInterval, doseBins and doseBinWidth need exposureField")
+        else:
+            self.exposureField = np.ascontiguousarray(self.exposureField, dtype=np.float64).reshape(-1)
+            if not (np.all(np.isfinite(self.exposureField)) and np.all(self.exposureField >= 0)):
+                raise ValueError("exposureField must be finite and >= 0")
+            if self.exposureInterval < 1:
+                raise ValueError("exposureInterval must be >= 1")
+            if self.doseBins < 1:
+                raise ValueError("doseBins must be >= 1")
+            if self.doseBinWidth is None and self.doseBins == 1:
+                self.doseBinWidth = 1.0                                 # (one open-ended bin: any width)
+            if self.doseBinWidth is None or not (math.isfinite(float(self.doseBinWidth)) and float(self.doseBinWidth) > 0):
+                raise ValueError("doseBins > 1 needs a positive doseBinWidth")
+            self.doseBinWidth = float(self.doseBinWidth)
+        self._exposure_pending = 0.0            # time advected since the last exposure point
         # hard-coded switches of the fragment (src/initCuda.H:64-72)
         self.usingAdvection = True
         self.usingBrownianMotion = True
@@ -908,6 +1002,9 @@ class CudaParticles:
                 self.ctx.set_source_origins(self.sourceOrigins)
         if self.routeStats:
             self.ctx.route_enable()
+        if self.exposureField is not None:
+            self.ctx.exposure_enable(self.doseBinWidth, self.doseBins)
+            self.ctx.set_exposure_field(self.exposureField)
         if self.writer is not None:
             # frame 0 carries the velocities of one advect and out-of-domain particles as inactive, like the reference
             # (src/initCuda.H:184-201): a cycle of zero length (moves nothing, does not count as a step)
@@ -941,13 +1038,21 @@ class CudaParticles:
                 self.step % self.saveInterval == 0 or run_time_value == self.particleEndTime)
             # cycles until the next output point run inside ONE launch (U is frozen during the loop)
             chunk = _next_chunk(self.step, n_cycles - done, self.saveInterval, self.occupancyInterval,
-                                self.writer is not None, will_write, self.recycleInterval)
+                                self.writer is not None, will_write, self.recycleInterval,
+                                exposure_interval=self.exposureInterval if self.exposureField is not None else 0)
             flags = self._flags(will_write) | (L.STEP_FUSE_CYCLES if chunk > 1 else 0)
             self.ctx.step(cycle_dt, D, chunk, flags)
             if will_write:                                                             # advect.H:166-169
                 self._write(self.step + 1)
             self.step += chunk                                                         # advect.H:182
             done += chunk
+            if self.exposureField is not None:
+                # the time of the cycles just done goes to the cell each particle is in at the next exposure point, which comes
+                # BEFORE the recycle point's absorption: the absorbed carry their last interval
+                self._exposure_pending += cycle_dt * chunk
+                if self.step % self.exposureInterval == 0:
+                    self.ctx.exposure_accumulate(self._exposure_pending)
+                    self._exposure_pending = 0.0
             if self.recycleInterval > 0 and self.step % self.recycleInterval == 0:
                 self.ctx.sink_apply()
                 if self.sourceTriangles is not None:
@@ -1001,6 +1106,15 @@ class CudaParticles:
         """Mean age in seconds per cell and origin over the samples ``occupancyInterval`` took, with ``routeStats`` set
         (``Context.mean_age_by_origin``)."""
         return self.ctx.mean_age_by_origin(self.dt)
+
+    def dose_distribution(self):
+        """Dose distribution of the absorbed particles, (edges, counts [n_origins][n_sinks][n_bins]), with ``exposureField`` set
+        (``Context.dose_distribution``)."""
+        return self.ctx.dose_distribution()
+
+    def doses(self):
+        """The dose of every particle in id order, -1 for a dead slot, with ``exposureField`` set (``Context.doses``)."""
+        return self.ctx.doses()
 
     def close(self):
         self.ctx.close()

@@ -16,6 +16,7 @@
 
 #include "cpf.h"
 #include "cpf_device.h"
+#include "cpf_exposure_bins.h"   // exposure_bin (cpf_exposure_bins_host)
 #include "cpf_internal.h"
 #include "cpf_own.h"
 #include "cpf_philox.h"    // respawn_position (cpf_respawn_positions_host)
@@ -137,6 +138,19 @@ struct Routes {
     int64_t samples = 0;
 };
 
+// Exposure of the context's own cloud (cpf_exposure_*; cpf_exposure.hip).  The doses belong to a cloud, the rates to a mesh, the
+// histogram's shape to tagging: a new cloud, a new mesh and tagging going on or off each replace the group with an empty one.
+struct Exposure {
+    bool on = false;
+    double binWidth = 0.0, invWidth = 0.0;  // invWidth = 1.0 / binWidth, computed once (cpf_exposure_bins.h)
+    int32_t nBins = 0, nOrigins = 1, nSinks = 1;
+    bool tagged = false;                    // tagging was on at enable time: origin and sink group are read, else both are 0
+    DevBuf<double> dose;                    // [cloud.n] by particle id: the sum since the particle last became live
+    DevBuf<double> rate;                    // [host.nCells] per DERIVED cell: the caller's field expanded through `first`
+    DevBuf<unsigned long long> hist;        // [nOrigins][nSinks][nBins] absorptions by origin, sink group and dose bin
+};
+constexpr int32_t kExposureWords = 4096;    // histogram words at most: exposure_absorb_kernel stages them in LDS
+
 // asynchronous output (cpf_write_vtu_async): one frame in flight.  Lives as long as the context.
 struct FrameWriter {
     std::thread thread;
@@ -209,7 +223,7 @@ struct cpf_context {
     bool vertexFast = true;                     // cpf_set_option("vertex_fast")
     uint32_t seed = 1591593751u;                // cuda/particles.cu:544
     // ---- the groups
-    Mesh mesh; TetField tet; Cloud cloud; Age age; Tags tags; Routes routes; FrameWriter frame; Timing timing;
+    Mesh mesh; TetField tet; Cloud cloud; Age age; Tags tags; Routes routes; Exposure exposure; FrameWriter frame; Timing timing;
     // ---- what lives as long as the context
     DevBuf<char> scratch;
     size_t scratchBytes = 0;
@@ -306,6 +320,15 @@ int ensureScratch(cpf_context* ctx, size_t bytes) {
     return CPF_OK;
 }
 
+// exposure off (cpf_exposure_disable; a new cloud; tagging going on or off): a pass over the tables may still be running
+int dropExposure(cpf_context* ctx) {
+    if (!ctx->exposure.on) return CPF_OK;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->exposure = Exposure{};
+    return CPF_OK;
+}
+
 // routes off (cpf_route_disable; age or tags going off or starting anew): a pass over the tables may still be running
 int dropRoutes(cpf_context* ctx) {
     if (!ctx->routes.on) return CPF_OK;
@@ -327,6 +350,7 @@ int dropAge(cpf_context* ctx) {
 
 // tagging off (cpf_tag_disable, a new cloud): a pass over the origins may still be running
 int dropTags(cpf_context* ctx) {
+    if (int r = dropExposure(ctx)) return r;                // (the shape of its histogram is tagging's, on or off)
     if (!ctx->tags.on) return CPF_OK;
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -390,6 +414,7 @@ int setMeshImpl(cpf_context* ctx, const double* points, int64_t nPoints, const L
     ctx->age = Age{};
     ctx->tags = Tags{};
     ctx->routes = Routes{};
+    ctx->exposure = Exposure{};
     ctx->streamState.flatField = false;
     ctx->mesh.host = std::move(t);
     ctx->mesh.nParent = nCells;
@@ -939,6 +964,7 @@ int cpf_alloc_particles(cpf_context* ctx, int64_t capacity) {
     ctx->age = Age{};
     ctx->tags = Tags{};
     ctx->routes = Routes{};
+    ctx->exposure = Exposure{};
     const size_t c = (size_t)capacity;
     CPF_HIP(ctx, ctx->cloud.cur.alloc(c));
     CPF_HIP(ctx, ctx->cloud.vel.alloc(c * 3));
@@ -1508,6 +1534,15 @@ int cpf_sink_apply(cpf_context* ctx) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_sink_apply: call cpf_set_mesh first");
     CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_sink_apply: no located particles");
+    if (ctx->exposure.on && ctx->mesh.sinkMask) {
+        // exposure: a read-only pass of its own bins the dose of everybody the sink is about to absorb, before anyone is marked
+        // (cpf_exposure.hip); then whichever of the three paths below applies, as without it
+        const Exposure& e = ctx->exposure;
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        CPF_HIP(ctx, cpf::exposure_absorb(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, e.dose, e.tagged ? ctx->tags.origin.get() : nullptr,
+                                          ctx->cloud.n, ctx->mesh.sinkMask, ctx->mesh.host.nCells,
+                                          e.tagged ? ctx->tags.sinkGroup.get() : nullptr, e.invWidth, e.nBins, e.nOrigins, e.nSinks, e.hist));
+    }
     if (ctx->routes.on) {
         // routes (so tags and age are on): ONE pass in place of the two below, which adds what they add and the joint histogram
         // besides (cpf_routes.hip)
@@ -1579,6 +1614,11 @@ int cpf_respawn_box(cpf_context* ctx, const double lower[3], const double upper[
         CPF_HIP(ctx, hipSetDevice(ctx->device));
         CPF_HIP(ctx, cpf::tag_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->tags.origin, ctx->cloud.n, nullptr, 0,
                                     nullptr, ctx->seed, ctx->cloud.respawnEpoch, ctx->tags.boxOrigin));
+    }
+    if (ctx->exposure.on && boxOk && maxCount != 0) {
+        // exposure: every candidate starts from dose +0.0, under the conditions of age's stamp
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        CPF_HIP(ctx, cpf::exposure_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->exposure.dose, ctx->cloud.n));
     }
     int r = cpf_respawn_box_dev(ctx, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell, ctx->cloud.cur.gid,
                                 ctx->cloud.n, lower, upper, maxCount, ctx->cloud.respawnEpoch);
@@ -1784,6 +1824,11 @@ int cpf_respawn_source(cpf_context* ctx, int64_t maxCount) {
                                     ctx->mesh.sourceHi, (int32_t)ctx->mesh.sourceKept, ctx->tags.originOfKept, ctx->seed,
                                     ctx->cloud.respawnEpoch, 0));
     }
+    if (ctx->exposure.on && maxCount != 0) {
+        // exposure: every candidate starts from dose +0.0, as in cpf_respawn_box
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        CPF_HIP(ctx, cpf::exposure_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->exposure.dose, ctx->cloud.n));
+    }
     int r = cpf_respawn_source_dev(ctx, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell, ctx->cloud.cur.gid,
                                    ctx->cloud.n, maxCount, ctx->cloud.respawnEpoch);
     if (r) return r;
@@ -1921,6 +1966,7 @@ int cpf_tag_enable(cpf_context* ctx, int32_t nOrigins, int32_t nSinks) {
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass over the old tables may still be running)
     ctx->tags = Tags{};
     ctx->routes = Routes{};                                 // (nOrigins and nSinks may change)
+    ctx->exposure = Exposure{};                             // (... and its histogram is shaped by them)
     Tags t;                                                 // moved in whole: a failure part-way leaves tagging off
     const size_t n = (size_t)ctx->cloud.n, nDerived = (size_t)ctx->mesh.host.nCells, nField = (size_t)ctx->mesh.nParent * nOrigins;
     CPF_HIP(ctx, t.origin.alloc(n));
@@ -2134,6 +2180,141 @@ int cpf_get_route_field(cpf_context* ctx, uint64_t* ageSum, uint64_t* count, int
         if (ageSum) ageSum[c] = h[2 * c];
         if (count) count[c] = h[2 * c + 1];
     }
+    return CPF_OK;
+}
+
+// ---- exposure: a dose per particle id summed along the path, the dose histogram at the sink (cpf_exposure.hip) -------------
+int cpf_exposure_enable(cpf_context* ctx, double binWidth, int32_t nBins) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_exposure_enable: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_exposure_enable: no located particles");
+    CPF_REQUIRE(ctx, std::isfinite(binWidth) && binWidth > 0.0, CPF_ERR_ARG, "cpf_exposure_enable: binWidth must be finite and > 0");
+    const int32_t nOrigins = ctx->tags.on ? ctx->tags.nOrigins : 1, nSinks = ctx->tags.on ? ctx->tags.nSinks : 1;
+    CPF_REQUIRE(ctx, nBins >= 1 && (int64_t)nOrigins * nSinks * nBins <= kExposureWords, CPF_ERR_ARG,
+                "cpf_exposure_enable: nOrigins * nSinks * nBins must be in [1, 4096]");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass over the old tables may still be running)
+    ctx->exposure = Exposure{};
+    Exposure e;                                             // moved in whole: a failure part-way leaves exposure off
+    const size_t n = (size_t)ctx->cloud.n, nDerived = (size_t)ctx->mesh.host.nCells, nHist = (size_t)nOrigins * nSinks * nBins;
+    CPF_HIP(ctx, e.dose.alloc(n));
+    CPF_HIP(ctx, e.rate.alloc(nDerived));
+    CPF_HIP(ctx, e.hist.alloc(nHist));
+    CPF_HIP(ctx, hipMemsetAsync(e.dose, 0, n * 8, ctx->stream));            // (+0.0)
+    CPF_HIP(ctx, hipMemsetAsync(e.rate, 0, nDerived * 8, ctx->stream));
+    CPF_HIP(ctx, hipMemsetAsync(e.hist, 0, nHist * 8, ctx->stream));
+    e.on = true; e.binWidth = binWidth; e.invWidth = 1.0 / binWidth; e.nBins = nBins;
+    e.nOrigins = nOrigins; e.nSinks = nSinks; e.tagged = ctx->tags.on;
+    ctx->exposure = std::move(e);
+    return CPF_OK;
+}
+
+int cpf_exposure_disable(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    return dropExposure(ctx);
+}
+
+int cpf_set_exposure_field(cpf_context* ctx, const double* rate, int64_t nCells) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->exposure.on, CPF_ERR_STATE, "cpf_set_exposure_field: call cpf_exposure_enable first");
+    CPF_REQUIRE(ctx, rate && nCells == ctx->mesh.nParent, CPF_ERR_ARG, "cpf_set_exposure_field: one value per cell of the mesh as given");
+    for (int64_t c = 0; c < nCells; ++c)
+        CPF_REQUIRE(ctx, std::isfinite(rate[c]) && rate[c] >= 0.0, CPF_ERR_ARG,
+                    "cpf_set_exposure_field: the rate of cell " + std::to_string(c) + " is not finite and >= 0");
+    // one value per DERIVED cell: every derived cell of a parent gets the parent's
+    const int64_t nDerived = ctx->mesh.host.nCells;
+    const double* src = rate;
+    std::vector<double> expanded;
+    if (!ctx->mesh.first.empty()) {
+        expanded.resize((size_t)nDerived);
+        for (int64_t c = 0; c < nCells; ++c)
+            for (int64_t d = ctx->mesh.first[(size_t)c]; d < ctx->mesh.first[(size_t)c + 1]; ++d) expanded[(size_t)d] = rate[c];
+        src = expanded.data();
+    }
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemcpyAsync(ctx->exposure.rate, src, (size_t)nDerived * 8, hipMemcpyHostToDevice, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (the copy reads the caller's array, or `expanded`)
+    return CPF_OK;
+}
+
+int cpf_exposure_accumulate(cpf_context* ctx, double scale) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->exposure.on, CPF_ERR_STATE, "cpf_exposure_accumulate: call cpf_exposure_enable first");
+    CPF_REQUIRE(ctx, std::isfinite(scale) && scale >= 0.0, CPF_ERR_ARG, "cpf_exposure_accumulate: scale must be finite and >= 0");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, cpf::exposure_accumulate(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->exposure.rate, ctx->exposure.dose,
+                                          ctx->cloud.n, ctx->mesh.host.nCells, scale));
+    return CPF_OK;
+}
+
+int cpf_exposure_reset(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->exposure.on, CPF_ERR_STATE, "cpf_exposure_reset: call cpf_exposure_enable first");
+    const Exposure& e = ctx->exposure;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemsetAsync(e.hist, 0, (size_t)e.nOrigins * e.nSinks * e.nBins * 8, ctx->stream));
+    return CPF_OK;
+}
+
+int cpf_get_dose_histogram(cpf_context* ctx, uint64_t* bins) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->exposure.on, CPF_ERR_STATE, "cpf_get_dose_histogram: call cpf_exposure_enable first");
+    CPF_REQUIRE(ctx, bins, CPF_ERR_ARG, "cpf_get_dose_histogram: null array");
+    const Exposure& e = ctx->exposure;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemcpyAsync(bins, e.hist, (size_t)e.nOrigins * e.nSinks * e.nBins * 8, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPF_OK;
+}
+
+int cpf_exposure_get_doses(cpf_context* ctx, double* dose) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->exposure.on, CPF_ERR_STATE, "cpf_exposure_get_doses: call cpf_exposure_enable first");
+    CPF_REQUIRE(ctx, dose, CPF_ERR_ARG, "cpf_exposure_get_doses: null array");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemcpyAsync(dose, ctx->exposure.dose, (size_t)ctx->cloud.n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPF_OK;
+}
+
+int cpf_exposure_set_doses(cpf_context* ctx, const double* dose) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->exposure.on, CPF_ERR_STATE, "cpf_exposure_set_doses: call cpf_exposure_enable first");
+    CPF_REQUIRE(ctx, dose, CPF_ERR_ARG, "cpf_exposure_set_doses: null array");
+    for (int64_t i = 0; i < ctx->cloud.n; ++i)              // (what the accumulate rule can produce: no NaN, nothing negative, no -0.0)
+        CPF_REQUIRE(ctx, dose[i] >= 0.0 && !std::signbit(dose[i]), CPF_ERR_ARG,
+                    "cpf_exposure_set_doses: the dose of particle " + std::to_string(i) + " is negative or not a number");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemcpyAsync(ctx->exposure.dose, dose, (size_t)ctx->cloud.n * 8, hipMemcpyHostToDevice, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPF_OK;
+}
+
+int cpf_get_doses(cpf_context* ctx, double* dose) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->exposure.on, CPF_ERR_STATE, "cpf_get_doses: call cpf_exposure_enable first");
+    CPF_REQUIRE(ctx, dose, CPF_ERR_ARG, "cpf_get_doses: null array");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    // a read-back for checks and restarts, not a hot path: the cells in id order (cpf_get_ages' pass), the rest on the host
+    const size_t n = (size_t)ctx->cloud.n;
+    int r = ensureScratch(ctx, n * 4);
+    if (r) return r;
+    int32_t* dC = (int32_t*)ctx->scratch.get();
+    CPF_HIP(ctx, cpf::launch_pack_by_gid(ctx->stream, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell,
+                                         ctx->cloud.cur.gid, nullptr, nullptr, dC, nullptr, ctx->cloud.n));
+    std::vector<int32_t> cell(n);
+    CPF_HIP(ctx, hipMemcpyAsync(cell.data(), dC, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipMemcpyAsync(dose, ctx->exposure.dose, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; ++i)
+        if (cell[i] < 0) dose[i] = -1.0;
+    return CPF_OK;
+}
+
+int cpf_exposure_bins_host(const double* dose, int64_t n, double binWidth, int32_t nBins, int32_t* bin) {
+    if (n < 0 || !std::isfinite(binWidth) || !(binWidth > 0.0) || nBins < 1 || (n > 0 && (!dose || !bin))) return CPF_ERR_ARG;
+    const double invWidth = 1.0 / binWidth;
+    for (int64_t i = 0; i < n; ++i) bin[i] = cpf::exposure_bin(dose[i], invWidth, nBins);
     return CPF_OK;
 }
 

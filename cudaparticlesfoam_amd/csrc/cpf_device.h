@@ -333,6 +333,17 @@ hipError_t route_absorb(hipStream_t st, int32_t* cell, const int64_t* gid, const
 hipError_t route_field(hipStream_t st, const int32_t* cell, const int64_t* gid, const uint32_t* birth, const uint8_t* origin, int64_t n,
                        const int32_t* parentOf, int64_t nDerived, int64_t nParent, int32_t nOrigins, uint32_t now,
                        unsigned long long* field);
+// exposure (cpf_exposure.hip).  dose[id] (n doubles, id = gid[slot]; gid null: the slot), rate[d] one double per DERIVED cell.
+// exposure_accumulate: dose[id] = dose[id] + scale * rate[cell[i]] for every i with 0 <= cell[i] < nDerived and a rate that is
+// not zero.  exposure_absorb: reads only; hist[(origin * nSinks + group) * nBins + exposure_bin(dose[id], invWidth, nBins)] += 1
+// for every i that sink_apply would absorb (cpf_exposure_bins.h; origin and sinkGroup both null: no tagging, origin and group 0;
+// nOrigins * nSinks * nBins <= 4096).  exposure_stamp: dose[id] = +0.0 for every slot with cell < 0
+hipError_t exposure_accumulate(hipStream_t st, const int32_t* cell, const int64_t* gid, const double* rate, double* dose, int64_t n,
+                               int64_t nDerived, double scale);
+hipError_t exposure_absorb(hipStream_t st, const int32_t* cell, const int64_t* gid, const double* dose, const uint8_t* origin, int64_t n,
+                           const uint32_t* mask, int64_t nDerived, const uint8_t* sinkGroup, double invWidth, int32_t nBins,
+                           int32_t nOrigins, int32_t nSinks, unsigned long long* hist);
+hipError_t exposure_stamp(hipStream_t st, const int32_t* cell, const int64_t* gid, double* dose, int64_t n);
 hipError_t unpack_arrivals(hipStream_t st, double* x, double* y, double* z, int32_t* cell, int64_t* gid,
                            int64_t nStay, const double* recvbuf, int64_t nRecv);
 // output of a sharded cloud (cpf_shard_gather): records of kOutputDoubles doubles = x, y, z, cell, gid, vx, vy, vz

@@ -641,6 +641,65 @@ int cpf_get_route_histogram(cpf_context* ctx, uint64_t* bins);
 int cpf_get_route_field(cpf_context* ctx, uint64_t* ageSum, uint64_t* count, int64_t* nSamples);
 
 /* ---------------------------------------------------------------------------------------------
+ * exposure: what a particle accumulated on its way (the integral of a cell field along its path), and the distribution of that
+ * dose over the particles the sink absorbs -- the UV dose of a reactor, a damage index, the time spent in a marked zone
+ * NO REFERENCE COUNTERPART for any entry of this group.  The state is
+ *   dose[id]                            one double per PARTICLE ID (the order of cpf_get_particles): +0.0 at enable and whenever a
+ *                                       respawn makes the particle a candidate; a table by id is moved by neither sort, and no
+ *                                       step kernel knows of it;
+ *   rate[cell]                          one double per cell, finite and >= 0, all zero until cpf_set_exposure_field;
+ *   doseHist[nOrigins][nSinks][nBins]   64-bit counters.  With tagging on AT ENABLE TIME nOrigins and nSinks are cpf_tag_enable's,
+ *                                       otherwise both are 1.
+ * Every operation is rounded on its own (no fused multiply-add):
+ *   accumulate   dose[id] = dose[id] + scale * rate[cell of id] for every live particle, one add per particle and call, in call
+ *                order -- the same bits as the same sums on the host, whatever the order of the cloud.  A particle in a cell whose
+ *                rate is exactly 0 is not touched (the same bits);
+ *   bin          k = dose * invWidth with invWidth = 1.0 / binWidth computed once; bin = k >= nBins - 1 ? nBins - 1 : (int)k.  The
+ *                last bin is open-ended.  cpf_exposure_bins_host states the rule.
+ * Exposure covers the CONTEXT-OWNED cloud only: cpf_shard_*, the _dev entries and the replacement fragments neither read nor write
+ * a dose.  While it is on,
+ *   cpf_sink_apply      first adds, in a read-only pass of its own before anyone is marked, 1 to
+ *                       doseHist[origin][group][bin(dose)] for every particle it is about to absorb (origin and group as
+ *                       cpf_get_transfer reads them; both 0 without tagging), then does exactly what it does without this group,
+ *                       with age tracking, tagging and routes on or off: the same cloud, counters, transfer matrix, age histogram
+ *                       and route tables;
+ *   cpf_respawn_box, cpf_respawn_source   first set dose = +0.0 for every CANDIDATE (slot with cell < 0), under the conditions of
+ *                       age's stamp (a box or source the call accepts, maxCount != 0), then place exactly the particles they place
+ *                       without it.
+ * While it is off every call launches exactly what it launches without this group.
+ * The doses belong to a cloud, the rates to a mesh and the histogram's shape to tagging: cpf_alloc_particles, cpf_seed_box,
+ * cpf_set_particles, cpf_set_mesh*, cpf_tag_enable and cpf_tag_disable turn exposure off.  Age tracking and routes are independent
+ * of it.  Every entry but cpf_exposure_enable, cpf_exposure_disable and cpf_exposure_bins_host returns CPF_ERR_STATE while it is
+ * off.
+ * ------------------------------------------------------------------------------------------- */
+/* NO REFERENCE COUNTERPART.  Turns exposure on, or starts it anew: dose[n] = +0.0, rate zeroed, a zeroed histogram.  CPF_ERR_STATE
+ * without a mesh or without located particles; CPF_ERR_ARG unless binWidth is finite and > 0, nBins >= 1 and
+ * nOrigins * nSinks * nBins <= 4096. */
+int cpf_exposure_enable(cpf_context* ctx, double binWidth, int32_t nBins);
+/* NO REFERENCE COUNTERPART.  Turns exposure off and frees its tables (no error when it is off already). */
+int cpf_exposure_disable(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  rate[nCells], one value per cell of the mesh AS GIVEN (every derived cell of a decomposed cell gets its
+ * parent's value).  CPF_ERR_ARG unless nCells is the mesh's and every value is finite and >= 0.  Waits for the context's stream. */
+int cpf_set_exposure_field(cpf_context* ctx, const double* rate, int64_t nCells);
+/* NO REFERENCE COUNTERPART.  One step of the sum, see "accumulate" above: scale is the time the particles spent since the last
+ * call (or any other weight), finite and >= 0, else CPF_ERR_ARG.  Dead slots are skipped.  Asynchronous on the context's stream. */
+int cpf_exposure_accumulate(cpf_context* ctx, double scale);
+/* NO REFERENCE COUNTERPART.  Zeroes the histogram (asynchronous); the doses and the rates stay. */
+int cpf_exposure_reset(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  Waits for the context's stream; bins[nOrigins][nSinks][nBins] since the last cpf_exposure_reset. */
+int cpf_get_dose_histogram(cpf_context* ctx, uint64_t* bins);
+/* NO REFERENCE COUNTERPART.  Waits for the context's stream; dose[n] in particle-id order, -1.0 for a dead slot (cell < 0). */
+int cpf_get_doses(cpf_context* ctx, double* dose);
+/* NO REFERENCE COUNTERPART.  The table itself, host arrays of n entries in particle-id order, dead slots included, for checkpoint
+ * and restart.  Both wait for the context's stream.  The setter takes what accumulate can produce -- CPF_ERR_ARG for a NaN, a
+ * negative value or -0.0; +infinity is a dose (of the last bin). */
+int cpf_exposure_get_doses(cpf_context* ctx, double* dose);
+int cpf_exposure_set_doses(cpf_context* ctx, const double* dose);
+/* NO REFERENCE COUNTERPART.  The bin rule on the host (no context, no device): bin[i] of dose[i], i < n, see "bin" above; -1 for a
+ * dose that has none (NaN, negative).  CPF_ERR_ARG unless binWidth is finite and > 0 and nBins >= 1. */
+int cpf_exposure_bins_host(const double* dose, int64_t n, double binWidth, int32_t nBins, int32_t* bin);
+
+/* ---------------------------------------------------------------------------------------------
  * device-array level (framework hosts that own the particle arrays, multi-GPU sharding)
  * SoA fp64 positions x,y,z [n]; cell [n] int32; gid [n] int64 global particle id (nullable:
  * gid = index); vel [n][3] (nullable unless CPF_STEP_STORE_VEL).

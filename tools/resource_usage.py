@@ -82,6 +82,14 @@ def collect_routes():
     return parse(r.stderr, ("route_",))
 
 
+def collect_exposure():
+    """The same rows for the exposure kernels (cpf_exposure.hip: exposure_accumulate_kernel, exposure_absorb_kernel,
+    exposure_stamp_kernel); collect() does not list them.  The absorb kernel's LDS is its static part: its histogram (4 bytes a
+    word, 16 KB at most) is dynamic."""
+    r = subprocess.run(hipcc_cmd("cpf_exposure.hip") + ["-c", "-o", "/dev/null"], capture_output=True, text=True)
+    return parse(r.stderr, ("exposure_",))
+
+
 def kernel_bodies(asm):
     """mangled kernel name -> its instructions (labels, directives and comments dropped).  Only what the listing types as a
     function: a library's constant table (rocprim has one) is a _Z label too, and the text behind the last one is the metadata."""
