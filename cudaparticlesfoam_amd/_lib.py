@@ -196,6 +196,14 @@ SIGNATURES = {
     "cpf_exposure_get_doses": (_int, [_ctx, _vp]),
     "cpf_exposure_set_doses": (_int, [_ctx, _vp]),
     "cpf_exposure_bins_host": (_int, [_vp, _i64, _dbl, _i32, _vp]),
+    "cpf_zone_enable": (_int, [_ctx, _i32]),
+    "cpf_zone_disable": (_int, [_ctx]),
+    "cpf_set_zone_map": (_int, [_ctx, _vp, _i64]),
+    "cpf_zone_sample": (_int, [_ctx]),
+    "cpf_zone_reset": (_int, [_ctx]),
+    "cpf_get_zone_flows": (_int, [_ctx, _vp, _vp]),
+    "cpf_zone_get_last": (_int, [_ctx, _vp]),
+    "cpf_zone_set_last": (_int, [_ctx, _vp]),
     "cpf_source_picks_host": (_int, [_u32, _vp, _i64, _u32, _vp, _i64, _vp]),
     "cpf_set_velocity": (_int, [_ctx, _vp, _i64]),
     "cpf_set_velocity_dev": (_int, [_ctx, _vp, _i64]),

@@ -573,6 +573,61 @@ class Context:
         edges[-1] = np.inf
         return edges, counts
 
+    # -- zones: the zone of every particle at the last sample, the zone-to-zone transition counts (include/cpf.h "zones")
+    def zone_enable(self, n_zones: int):
+        """Turns zones of the context-owned cloud on (or starts them anew): every particle is outside, the map all 0, the table
+        zeroed; ``1 <= n_zones <= 63``."""
+        self._ck(self.lib.cpf_zone_enable(self.h, int(n_zones)))
+        self._n_zones = int(n_zones)
+
+    def zone_disable(self):
+        self._ck(self.lib.cpf_zone_disable(self.h))
+
+    def set_zone_map(self, zone):
+        """One zone in [0, n_zones) per cell of the mesh as given."""
+        z = np.ascontiguousarray(zone, dtype=np.int32).reshape(-1)
+        self._ck(self.lib.cpf_set_zone_map(self.h, _ptr(z) if z.size else None, z.size))
+
+    def zone_sample(self):
+        """flow[last zone][zone now] += 1 for every live particle, and the zone now becomes its last; asynchronous."""
+        self._ck(self.lib.cpf_zone_sample(self.h))
+
+    def zone_reset(self):
+        """Zeroes the table and the sample count; the last zones and the map stay."""
+        self._ck(self.lib.cpf_zone_reset(self.h))
+
+    def zone_flows(self):
+        """(F uint64 [n_zones + 1][n_zones + 1], n_samples) since the last reset: F[p][z] transitions from zone p at one sample
+        to zone z at the next; index n_zones is "outside" (row: first seen, column: absorbed); synchronises."""
+        k = getattr(self, "_n_zones", 1) + 1
+        f = np.zeros((k, k), np.uint64)
+        ns = C.c_int64(0)
+        self._ck(self.lib.cpf_get_zone_flows(self.h, _ptr(f), C.byref(ns)))
+        return f, ns.value
+
+    def zone_last(self) -> np.ndarray:
+        """uint8 [n] in particle-id order: the zone at the last sample, 0xFF for outside (checkpoints)."""
+        a = np.empty(self.n, np.uint8)
+        self._ck(self.lib.cpf_zone_get_last(self.h, _ptr(a)))
+        return a
+
+    def zone_set_last(self, last):
+        a = np.ascontiguousarray(last, dtype=np.uint8).reshape(-1)
+        if a.size != self.n:
+            raise ValueError("zone_set_last: %d bytes for %d particles" % (a.size, self.n))
+        self._ck(self.lib.cpf_zone_set_last(self.h, _ptr(a)))
+
+    def zone_exchange_rates(self, sample_dt: float) -> np.ndarray:
+        """[n_zones + 1][n_zones + 1] particles per second from zone p to zone z over the samples taken, ``sample_dt`` apart: the
+        off-diagonal of F / (n_samples * sample_dt), the diagonal 0; NaN without a sample."""
+        f, ns = self.zone_flows()
+        return zone_exchange_rates(f, ns, sample_dt)
+
+    def zone_residence(self, sample_dt: float) -> np.ndarray:
+        """[n_zones] mean time of a visit to each zone in seconds: the samples found in it over the entries into it, NaN where
+        nobody entered."""
+        return zone_residence(self.zone_flows()[0], sample_dt)
+
     def cell_ranges_dev(self, weights, n_ranks, cell_lo):
         self._ck(self.lib.cpf_cell_ranges_dev(self.h, weights, n_ranks, cell_lo))
 
@@ -851,11 +906,33 @@ DICT_DEFAULTS = dict(                       # src/initCuda.H:49-57 (getOrDefault
     dt=1e-4, diffusionCoeff=5.7e-6, saveInterval=10)
 
 
+def zone_exchange_rates(flow, n_samples: int, sample_dt: float) -> np.ndarray:
+    """``Context.zone_exchange_rates`` on a table: off-diagonal flow / (n_samples * sample_dt), the diagonal 0; plain numpy."""
+    f = np.asarray(flow).astype(np.float64)
+    rates = f / (float(n_samples) * float(sample_dt)) if n_samples > 0 else np.full(f.shape, np.nan)
+    np.fill_diagonal(rates, 0.0)
+    return rates
+
+
+def zone_residence(flow, sample_dt: float) -> np.ndarray:
+    """``Context.zone_residence`` on a table [k + 1][k + 1]: per zone z < k, sample_dt * colsum_z / (colsum_z - flow[z][z]) -- the
+    samples that found a particle in z over those that found it there for the first time of a visit --, NaN where nobody
+    entered; plain numpy."""
+    f = np.asarray(flow).astype(np.float64)
+    k = f.shape[0] - 1
+    col = f.sum(axis=0)[:k]
+    entered = col - np.diagonal(f)[:k]
+    out = np.full(k, np.nan)
+    np.divide(float(sample_dt) * col, entered, out=out, where=entered > 0)
+    return out
+
+
 def _next_chunk(step: int, remaining: int, save_interval: int, occupancy_interval: int, has_writer: bool,
-                will_write: bool, recycle_interval: int = 0, *, exposure_interval: int = 0) -> int:
+                will_write: bool, recycle_interval: int = 0, *, exposure_interval: int = 0, zone_interval: int = 0) -> int:
     """Cycles the next launch of ``CudaParticles.advect`` fuses: a cycle that writes a frame runs alone; otherwise everything up
     to the next output point (with a writer), the next occupancy sample (``occupancy_interval`` > 0), the next recycle point
-    (``recycle_interval`` > 0), the next exposure point (``exposure_interval`` > 0) and the end of the call."""
+    (``recycle_interval`` > 0), the next exposure point (``exposure_interval`` > 0), the next zone point (``zone_interval`` > 0)
+    and the end of the call."""
     if will_write:
         return 1
     chunk = remaining
@@ -867,6 +944,8 @@ def _next_chunk(step: int, remaining: int, save_interval: int, occupancy_interva
         chunk = min(chunk, recycle_interval - (step % recycle_interval))
     if exposure_interval > 0:
         chunk = min(chunk, exposure_interval - (step % exposure_interval))
+    if zone_interval > 0:
+        chunk = min(chunk, zone_interval - (step % zone_interval))
     return max(1, chunk)
 
 
@@ -913,6 +992,12 @@ class CudaParticles:
     ``exposureInterval`` every live particle adds (the time since the last such point) x (the rate of the cell it is in) to its
     dose, before the recycle point's absorption if one is due; every absorption adds to ``dose_distribution()``, and a respawned
     particle starts from 0.
+
+    Two more: ``zoneMap`` (one non-negative int per cell; default None = off; max + 1 zones, 63 at most) and ``zoneInterval``
+    (cycles; default 1).  With a map, zones (``Context.zone_enable``) start behind exposure: at every cycle count that is a
+    multiple of ``zoneInterval`` every live particle adds one to ``zone_flows()[0][its zone at the last such point][its zone
+    now]``, before the recycle point's absorption if one is due, so the absorbed leave from the zone they are in;
+    ``zone_residence()`` is the mean time of a visit per zone.
     """
 
     def __init__(self, mesh, U, particle_dict: Optional[dict] = None, device: int = 0,
@@ -966,6 +1051,20 @@ class CudaParticles:
                 raise ValueError("doseBins > 1 needs a positive doseBinWidth")
             self.doseBinWidth = float(self.doseBinWidth)
         self._exposure_pending = 0.0            # time advected since the last exposure point
+        self.zoneMap = d.get("zoneMap", None)
+        self.zoneInterval = int(d.get("zoneInterval", 1))
+        if self.zoneMap is None:
+            if "zoneInterval" in d:
+                raise ValueError("zoneInterval needs zoneMap")
+        else:
+            zone_map = np.asarray(self.zoneMap).reshape(-1)
+            if zone_map.size == 0 or not np.issubdtype(zone_map.dtype, np.integer) or np.any(zone_map < 0):
+                raise ValueError("zoneMap must be one non-negative int per cell")
+            if int(zone_map.max()) + 1 > 63:
+                raise ValueError("zoneMap has %d zones, 63 at most" % (int(zone_map.max()) + 1))
+            if self.zoneInterval < 1:
+                raise ValueError("zoneInterval must be >= 1")
+            self.zoneMap = np.ascontiguousarray(zone_map, dtype=np.int32)
         # hard-coded switches of the fragment (src/initCuda.H:64-72)
         self.usingAdvection = True
         self.usingBrownianMotion = True
@@ -1005,6 +1104,9 @@ class CudaParticles:
         if self.exposureField is not None:
             self.ctx.exposure_enable(self.doseBinWidth, self.doseBins)
             self.ctx.set_exposure_field(self.exposureField)
+        if self.zoneMap is not None:
+            self.ctx.zone_enable(int(self.zoneMap.max()) + 1)
+            self.ctx.set_zone_map(self.zoneMap)
         if self.writer is not None:
             # frame 0 carries the velocities of one advect and out-of-domain particles as inactive, like the reference
             # (src/initCuda.H:184-201): a cycle of zero length (moves nothing, does not count as a step)
@@ -1039,7 +1141,8 @@ class CudaParticles:
             # cycles until the next output point run inside ONE launch (U is frozen during the loop)
             chunk = _next_chunk(self.step, n_cycles - done, self.saveInterval, self.occupancyInterval,
                                 self.writer is not None, will_write, self.recycleInterval,
-                                exposure_interval=self.exposureInterval if self.exposureField is not None else 0)
+                                exposure_interval=self.exposureInterval if self.exposureField is not None else 0,
+                                zone_interval=self.zoneInterval if self.zoneMap is not None else 0)
             flags = self._flags(will_write) | (L.STEP_FUSE_CYCLES if chunk > 1 else 0)
             self.ctx.step(cycle_dt, D, chunk, flags)
             if will_write:                                                             # advect.H:166-169
@@ -1053,6 +1156,8 @@ class CudaParticles:
                 if self.step % self.exposureInterval == 0:
                     self.ctx.exposure_accumulate(self._exposure_pending)
                     self._exposure_pending = 0.0
+            if self.zoneMap is not None and self.step % self.zoneInterval == 0:
+                self.ctx.zone_sample()                                                 # (BEFORE the absorption: they leave from here)
             if self.recycleInterval > 0 and self.step % self.recycleInterval == 0:
                 self.ctx.sink_apply()
                 if self.sourceTriangles is not None:
@@ -1115,6 +1220,15 @@ class CudaParticles:
     def doses(self):
         """The dose of every particle in id order, -1 for a dead slot, with ``exposureField`` set (``Context.doses``)."""
         return self.ctx.doses()
+
+    def zone_flows(self):
+        """(F [n_zones + 1][n_zones + 1], n_samples): transitions between zones from one zone point to the next, with ``zoneMap``
+        set (``Context.zone_flows``)."""
+        return self.ctx.zone_flows()
+
+    def zone_residence(self):
+        """Mean time of a visit per zone in seconds, with ``zoneMap`` set (``Context.zone_residence``)."""
+        return self.ctx.zone_residence(self.zoneInterval * self.dt)
 
     def close(self):
         self.ctx.close()

@@ -151,6 +151,19 @@ struct Exposure {
 };
 constexpr int32_t kExposureWords = 4096;    // histogram words at most: exposure_absorb_kernel stages them in LDS
 
+// Zones of the context's own cloud (cpf_zone_*; cpf_zones.hip).  The last zones belong to a cloud, the map to a mesh: a new cloud
+// and a new mesh each replace the group with an empty one.  Age, tags, routes and exposure know nothing of it, nor it of them.
+struct Zones {
+    bool on = false;
+    int32_t nZones = 0;
+    DevBuf<uint8_t> zoneOf;                 // [host.nCells] per DERIVED cell: the caller's map expanded through `first`
+    DevBuf<uint8_t> last;                   // [cloud.n] by particle id: the zone at the last sample, kZoneOutside: none
+    DevBuf<unsigned long long> flow;        // [nZones + 1][nZones + 1] transitions from sample to sample; index nZones: outside
+    int64_t samples = 0;
+};
+constexpr int32_t kZoneMax = 63;            // zones at most: zone_sample_kernel stages (nZones + 1)^2 <= 4096 words in LDS
+constexpr uint8_t kZoneOutside = 0xFF;
+
 // asynchronous output (cpf_write_vtu_async): one frame in flight.  Lives as long as the context.
 struct FrameWriter {
     std::thread thread;
@@ -223,7 +236,7 @@ struct cpf_context {
     bool vertexFast = true;                     // cpf_set_option("vertex_fast")
     uint32_t seed = 1591593751u;                // cuda/particles.cu:544
     // ---- the groups
-    Mesh mesh; TetField tet; Cloud cloud; Age age; Tags tags; Routes routes; Exposure exposure; FrameWriter frame; Timing timing;
+    Mesh mesh; TetField tet; Cloud cloud; Age age; Tags tags; Routes routes; Exposure exposure; Zones zones; FrameWriter frame; Timing timing;
     // ---- what lives as long as the context
     DevBuf<char> scratch;
     size_t scratchBytes = 0;
@@ -329,6 +342,15 @@ int dropExposure(cpf_context* ctx) {
     return CPF_OK;
 }
 
+// zones off (cpf_zone_disable; a new cloud): a pass over the tables may still be running
+int dropZones(cpf_context* ctx) {
+    if (!ctx->zones.on) return CPF_OK;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->zones = Zones{};
+    return CPF_OK;
+}
+
 // routes off (cpf_route_disable; age or tags going off or starting anew): a pass over the tables may still be running
 int dropRoutes(cpf_context* ctx) {
     if (!ctx->routes.on) return CPF_OK;
@@ -415,6 +437,7 @@ int setMeshImpl(cpf_context* ctx, const double* points, int64_t nPoints, const L
     ctx->tags = Tags{};
     ctx->routes = Routes{};
     ctx->exposure = Exposure{};
+    ctx->zones = Zones{};
     ctx->streamState.flatField = false;
     ctx->mesh.host = std::move(t);
     ctx->mesh.nParent = nCells;
@@ -965,6 +988,7 @@ int cpf_alloc_particles(cpf_context* ctx, int64_t capacity) {
     ctx->tags = Tags{};
     ctx->routes = Routes{};
     ctx->exposure = Exposure{};
+    ctx->zones = Zones{};
     const size_t c = (size_t)capacity;
     CPF_HIP(ctx, ctx->cloud.cur.alloc(c));
     CPF_HIP(ctx, ctx->cloud.vel.alloc(c * 3));
@@ -980,6 +1004,7 @@ int cpf_seed_box(cpf_context* ctx, int64_t n, const double lower[3], const doubl
     if (ctx->cloud.cap < n) { int r = cpf_alloc_particles(ctx, n); if (r) return r; }
     if (int r = dropAge(ctx)) return r;                     // (a new cloud: the stamps were the old one's)
     if (int r = dropTags(ctx)) return r;                    // (... and so were the origins)
+    if (int r = dropZones(ctx)) return r;                   // (... and the last zones)
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, cpf::launch_seed_box(ctx->stream, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, 0, n, lower, upper, order));
     CPF_HIP(ctx, cpf::launch_iota64(ctx->stream, ctx->cloud.cur.gid, n, 0));
@@ -995,6 +1020,8 @@ int cpf_set_particles(cpf_context* ctx, int64_t n, const double* xyz, const int3
     int r = dropAge(ctx);                                   // (a new cloud: the stamps were the old one's)
     if (r) return r;
     r = dropTags(ctx);                                      // (... and so were the origins)
+    if (r) return r;
+    r = dropZones(ctx);                                     // (... and the last zones)
     if (r) return r;
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     ctx->cloud.zSettled = false;
@@ -1543,6 +1570,14 @@ int cpf_sink_apply(cpf_context* ctx) {
                                           ctx->cloud.n, ctx->mesh.sinkMask, ctx->mesh.host.nCells,
                                           e.tagged ? ctx->tags.sinkGroup.get() : nullptr, e.invWidth, e.nBins, e.nOrigins, e.nSinks, e.hist));
     }
+    if (ctx->zones.on && ctx->mesh.sinkMask) {
+        // zones: a read-only pass of its own counts, by the zone of their last sample, everybody the sink is about to absorb as
+        // leaving for "outside", before anyone is marked (cpf_zones.hip); then whichever of the three paths below applies
+        const Zones& zn = ctx->zones;
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        CPF_HIP(ctx, cpf::zone_leave(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, zn.last, ctx->cloud.n, ctx->mesh.sinkMask,
+                                     ctx->mesh.host.nCells, zn.nZones, zn.flow));
+    }
     if (ctx->routes.on) {
         // routes (so tags and age are on): ONE pass in place of the two below, which adds what they add and the joint histogram
         // besides (cpf_routes.hip)
@@ -1619,6 +1654,11 @@ int cpf_respawn_box(cpf_context* ctx, const double lower[3], const double upper[
         // exposure: every candidate starts from dose +0.0, under the conditions of age's stamp
         CPF_HIP(ctx, hipSetDevice(ctx->device));
         CPF_HIP(ctx, cpf::exposure_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->exposure.dose, ctx->cloud.n));
+    }
+    if (ctx->zones.on && boxOk && maxCount != 0) {
+        // zones: every candidate is outside until its next sample, under the conditions of age's stamp
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        CPF_HIP(ctx, cpf::zone_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->zones.last, ctx->cloud.n));
     }
     int r = cpf_respawn_box_dev(ctx, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell, ctx->cloud.cur.gid,
                                 ctx->cloud.n, lower, upper, maxCount, ctx->cloud.respawnEpoch);
@@ -1828,6 +1868,11 @@ int cpf_respawn_source(cpf_context* ctx, int64_t maxCount) {
         // exposure: every candidate starts from dose +0.0, as in cpf_respawn_box
         CPF_HIP(ctx, hipSetDevice(ctx->device));
         CPF_HIP(ctx, cpf::exposure_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->exposure.dose, ctx->cloud.n));
+    }
+    if (ctx->zones.on && maxCount != 0) {
+        // zones: every candidate is outside until its next sample, as in cpf_respawn_box
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        CPF_HIP(ctx, cpf::zone_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->zones.last, ctx->cloud.n));
     }
     int r = cpf_respawn_source_dev(ctx, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell, ctx->cloud.cur.gid,
                                    ctx->cloud.n, maxCount, ctx->cloud.respawnEpoch);
@@ -2315,6 +2360,110 @@ int cpf_exposure_bins_host(const double* dose, int64_t n, double binWidth, int32
     if (n < 0 || !std::isfinite(binWidth) || !(binWidth > 0.0) || nBins < 1 || (n > 0 && (!dose || !bin))) return CPF_ERR_ARG;
     const double invWidth = 1.0 / binWidth;
     for (int64_t i = 0; i < n; ++i) bin[i] = cpf::exposure_bin(dose[i], invWidth, nBins);
+    return CPF_OK;
+}
+
+// ---- zones: the zone of every particle id at the last sample, the zone-to-zone transition counts (cpf_zones.hip) ------------
+int cpf_zone_enable(cpf_context* ctx, int32_t nZones) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_zone_enable: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_zone_enable: no located particles");
+    CPF_REQUIRE(ctx, nZones >= 1 && nZones <= kZoneMax, CPF_ERR_ARG, "cpf_zone_enable: nZones must be in [1, 63]");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass over the old tables may still be running)
+    ctx->zones = Zones{};
+    Zones zn;                                               // moved in whole: a failure part-way leaves zones off
+    const size_t n = (size_t)ctx->cloud.n, nDerived = (size_t)ctx->mesh.host.nCells, nFlow = (size_t)(nZones + 1) * (nZones + 1);
+    CPF_HIP(ctx, zn.zoneOf.alloc(nDerived));
+    CPF_HIP(ctx, zn.last.alloc(n));
+    CPF_HIP(ctx, zn.flow.alloc(nFlow));
+    CPF_HIP(ctx, hipMemsetAsync(zn.zoneOf, 0, nDerived, ctx->stream));
+    CPF_HIP(ctx, hipMemsetAsync(zn.last, kZoneOutside, n, ctx->stream));
+    CPF_HIP(ctx, hipMemsetAsync(zn.flow, 0, nFlow * 8, ctx->stream));
+    zn.on = true; zn.nZones = nZones;
+    ctx->zones = std::move(zn);
+    return CPF_OK;
+}
+
+int cpf_zone_disable(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    return dropZones(ctx);
+}
+
+int cpf_set_zone_map(cpf_context* ctx, const int32_t* zone, int64_t nCells) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->zones.on, CPF_ERR_STATE, "cpf_set_zone_map: call cpf_zone_enable first");
+    CPF_REQUIRE(ctx, zone && nCells == ctx->mesh.nParent, CPF_ERR_ARG, "cpf_set_zone_map: one value per cell of the mesh as given");
+    for (int64_t c = 0; c < nCells; ++c)
+        CPF_REQUIRE(ctx, zone[c] >= 0 && zone[c] < ctx->zones.nZones, CPF_ERR_ARG,
+                    "cpf_set_zone_map: the zone of cell " + std::to_string(c) + " is not in [0, nZones)");
+    // one byte per DERIVED cell: every derived cell of a parent gets the parent's
+    const int64_t nDerived = ctx->mesh.host.nCells;
+    std::vector<uint8_t> expanded((size_t)nDerived);
+    if (!ctx->mesh.first.empty()) {
+        for (int64_t c = 0; c < nCells; ++c)
+            for (int64_t d = ctx->mesh.first[(size_t)c]; d < ctx->mesh.first[(size_t)c + 1]; ++d) expanded[(size_t)d] = (uint8_t)zone[c];
+    } else {
+        for (int64_t c = 0; c < nCells; ++c) expanded[(size_t)c] = (uint8_t)zone[c];
+    }
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemcpyAsync(ctx->zones.zoneOf, expanded.data(), (size_t)nDerived, hipMemcpyHostToDevice, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (the copy reads `expanded`)
+    return CPF_OK;
+}
+
+int cpf_zone_sample(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->zones.on, CPF_ERR_STATE, "cpf_zone_sample: call cpf_zone_enable first");
+    Zones& zn = ctx->zones;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, cpf::zone_sample(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, zn.zoneOf, zn.last, ctx->cloud.n,
+                                  ctx->mesh.host.nCells, zn.nZones, zn.flow));
+    ++zn.samples;
+    return CPF_OK;
+}
+
+int cpf_zone_reset(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->zones.on, CPF_ERR_STATE, "cpf_zone_reset: call cpf_zone_enable first");
+    Zones& zn = ctx->zones;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemsetAsync(zn.flow, 0, (size_t)(zn.nZones + 1) * (zn.nZones + 1) * 8, ctx->stream));
+    zn.samples = 0;
+    return CPF_OK;
+}
+
+int cpf_get_zone_flows(cpf_context* ctx, uint64_t* flow, int64_t* nSamples) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->zones.on, CPF_ERR_STATE, "cpf_get_zone_flows: call cpf_zone_enable first");
+    const Zones& zn = ctx->zones;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    if (flow) CPF_HIP(ctx, hipMemcpyAsync(flow, zn.flow, (size_t)(zn.nZones + 1) * (zn.nZones + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (nSamples) *nSamples = zn.samples;
+    return CPF_OK;
+}
+
+int cpf_zone_get_last(cpf_context* ctx, uint8_t* last) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->zones.on, CPF_ERR_STATE, "cpf_zone_get_last: call cpf_zone_enable first");
+    CPF_REQUIRE(ctx, last, CPF_ERR_ARG, "cpf_zone_get_last: null array");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemcpyAsync(last, ctx->zones.last, (size_t)ctx->cloud.n, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CPF_OK;
+}
+
+int cpf_zone_set_last(cpf_context* ctx, const uint8_t* last) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->zones.on, CPF_ERR_STATE, "cpf_zone_set_last: call cpf_zone_enable first");
+    CPF_REQUIRE(ctx, last, CPF_ERR_ARG, "cpf_zone_set_last: null array");
+    for (int64_t i = 0; i < ctx->cloud.n; ++i)              // (what the sample rule can produce)
+        CPF_REQUIRE(ctx, last[i] < ctx->zones.nZones || last[i] == kZoneOutside, CPF_ERR_ARG,
+                    "cpf_zone_set_last: the byte of particle " + std::to_string(i) + " is neither a zone nor 0xFF");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemcpyAsync(ctx->zones.last, last, (size_t)ctx->cloud.n, hipMemcpyHostToDevice, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CPF_OK;
 }
 

@@ -344,6 +344,16 @@ hipError_t exposure_absorb(hipStream_t st, const int32_t* cell, const int64_t* g
                            const uint32_t* mask, int64_t nDerived, const uint8_t* sinkGroup, double invWidth, int32_t nBins,
                            int32_t nOrigins, int32_t nSinks, unsigned long long* hist);
 hipError_t exposure_stamp(hipStream_t st, const int32_t* cell, const int64_t* gid, double* dose, int64_t n);
+// zones (cpf_zones.hip).  last[id] (n bytes, id = gid[slot]; gid null: the slot) is the zone particle id was in at the last sample,
+// 0xFF: none; zoneOf[d] the zone of DERIVED cell d, below nZones; flow[nZones + 1][nZones + 1], row and column nZones: outside.
+// zone_sample: for every i with 0 <= cell[i] < nDerived, flow[last[id]][zoneOf[cell[i]]] += 1 and last[id] = that zone where it
+// differs.  zone_leave: reads only; flow[last[id]][nZones] += 1 for every i that sink_apply would absorb.  zone_stamp:
+// last[id] = 0xFF for every slot with cell < 0.  1 <= nZones <= 63
+hipError_t zone_sample(hipStream_t st, const int32_t* cell, const int64_t* gid, const uint8_t* zoneOf, uint8_t* last, int64_t n,
+                       int64_t nDerived, int32_t nZones, unsigned long long* flow);
+hipError_t zone_leave(hipStream_t st, const int32_t* cell, const int64_t* gid, const uint8_t* last, int64_t n, const uint32_t* mask,
+                      int64_t nDerived, int32_t nZones, unsigned long long* flow);
+hipError_t zone_stamp(hipStream_t st, const int32_t* cell, const int64_t* gid, uint8_t* last, int64_t n);
 hipError_t unpack_arrivals(hipStream_t st, double* x, double* y, double* z, int32_t* cell, int64_t* gid,
                            int64_t nStay, const double* recvbuf, int64_t nRecv);
 // output of a sharded cloud (cpf_shard_gather): records of kOutputDoubles doubles = x, y, z, cell, gid, vx, vy, vz

@@ -700,6 +700,58 @@ int cpf_exposure_set_doses(cpf_context* ctx, const double* dose);
 int cpf_exposure_bins_host(const double* dose, int64_t n, double binWidth, int32_t nBins, int32_t* bin);
 
 /* ---------------------------------------------------------------------------------------------
+ * zones: how much of the cloud goes from one compartment of the mesh to another between two samples, and how long a visit to a
+ * compartment lasts -- the exchange matrix a compartment model asks of a CFD run (a recirculation bubble against its core flow,
+ * two branches against their stem)
+ * NO REFERENCE COUNTERPART for any entry of this group.  The state is
+ *   zoneOf[cell]                        one zone in [0, nZones) per cell, all 0 until cpf_set_zone_map;
+ *   last[id]                            one byte per PARTICLE ID (the order of cpf_get_particles): the zone the particle was in at
+ *                                       the last sample, 0xFF = "outside": not sampled since enable, or since a respawn made it
+ *                                       a candidate; a table by id is moved by neither sort, and no step kernel knows of it;
+ *   flow[nZones + 1][nZones + 1]        64-bit counters, row-major, row = from, column = to; index nZones is "outside";
+ *   nSamples                            the samples taken since the last cpf_zone_reset.
+ * Every rule is a rule on integers, so every result is the same bits whatever the order of the cloud:
+ *   sample       for every live particle: p = last[id] (0xFF read as nZones), z = zoneOf[cell of id]; flow[p][z] += 1; last[id] = z
+ *                where p != z.  Dead slots are skipped: nothing is counted and last is untouched;
+ *   leave        flow[p][nZones] += 1 for every particle the sink is about to absorb; last is not written;
+ *   stamp        last[id] = 0xFF for every CANDIDATE of a respawn (slot with cell < 0).
+ * A particle that passes through a zone between two samples is not seen in it: this is a transition count between samples, not
+ * a crossing rule.  Zones cover the CONTEXT-OWNED cloud only: cpf_shard_*, the _dev entries and the replacement fragments neither
+ * read nor write them.  While they are on,
+ *   cpf_sink_apply      first runs "leave", in a read-only pass of its own before anyone is marked (and only if a sink set
+ *                       exists), then does exactly what it does without this group, with age tracking, tagging, routes and
+ *                       exposure on or off: the same cloud, counters, transfer matrix, age histogram, route tables and dose
+ *                       histogram;
+ *   cpf_respawn_box, cpf_respawn_source   first run "stamp", under the conditions of age's stamp (a box or source the call
+ *                       accepts, maxCount != 0), then place exactly the particles they place without it.
+ * While they are off every call launches exactly what it launches without this group.
+ * The last zones belong to a cloud and the map to a mesh: cpf_alloc_particles, cpf_seed_box, cpf_set_particles and cpf_set_mesh*
+ * turn zones off.  Age tracking, tagging, routes and exposure are independent of them, in both directions.  Every entry but
+ * cpf_zone_enable and cpf_zone_disable returns CPF_ERR_STATE while they are off.
+ * ------------------------------------------------------------------------------------------- */
+/* NO REFERENCE COUNTERPART.  Turns zones on, or starts them anew: last[n] = 0xFF, the map all 0, a zeroed table, nSamples = 0.
+ * CPF_ERR_STATE without a mesh or without located particles; CPF_ERR_ARG unless 1 <= nZones <= 63. */
+int cpf_zone_enable(cpf_context* ctx, int32_t nZones);
+/* NO REFERENCE COUNTERPART.  Turns zones off and frees their tables (no error when they are off already). */
+int cpf_zone_disable(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  zone[nCells], one value per cell of the mesh AS GIVEN (every derived cell of a decomposed cell gets its
+ * parent's value).  CPF_ERR_ARG unless nCells is the mesh's and every value is in [0, nZones); on error the map is unchanged.
+ * Waits for the context's stream. */
+int cpf_set_zone_map(cpf_context* ctx, const int32_t* zone, int64_t nCells);
+/* NO REFERENCE COUNTERPART.  One sample, see "sample" above; nSamples goes up by one.  Asynchronous on the context's stream. */
+int cpf_zone_sample(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  Zeroes the table (asynchronous) and nSamples; last and the map stay. */
+int cpf_zone_reset(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  Waits for the context's stream; flow[nZones + 1][nZones + 1] and *nSamples since the last
+ * cpf_zone_reset (each nullable). */
+int cpf_get_zone_flows(cpf_context* ctx, uint64_t* flow, int64_t* nSamples);
+/* NO REFERENCE COUNTERPART.  The table of last zones itself, host arrays of n bytes in particle-id order, dead slots included,
+ * for checkpoint and restart.  Both wait for the context's stream.  The setter takes what a sample or a stamp can produce --
+ * CPF_ERR_ARG for a byte that is neither below nZones nor 0xFF. */
+int cpf_zone_get_last(cpf_context* ctx, uint8_t* last);
+int cpf_zone_set_last(cpf_context* ctx, const uint8_t* last);
+
+/* ---------------------------------------------------------------------------------------------
  * device-array level (framework hosts that own the particle arrays, multi-GPU sharding)
  * SoA fp64 positions x,y,z [n]; cell [n] int32; gid [n] int64 global particle id (nullable:
  * gid = index); vel [n][3] (nullable unless CPF_STEP_STORE_VEL).

@@ -90,6 +90,14 @@ def collect_exposure():
     return parse(r.stderr, ("exposure_",))
 
 
+def collect_zones():
+    """The same rows for the zone kernels (cpf_zones.hip: zone_sample_kernel, zone_leave_kernel, zone_stamp_kernel); collect()
+    does not list them.  The sample kernel's LDS is its static part: its table ((nZones + 1)^2 words of 4 bytes, 16 KB at most) is
+    dynamic."""
+    r = subprocess.run(hipcc_cmd("cpf_zones.hip") + ["-c", "-o", "/dev/null"], capture_output=True, text=True)
+    return parse(r.stderr, ("zone_",))
+
+
 def kernel_bodies(asm):
     """mangled kernel name -> its instructions (labels, directives and comments dropped).  Only what the listing types as a
     function: a library's constant table (rocprim has one) is a _Z label too, and the text behind the last one is the metadata."""
