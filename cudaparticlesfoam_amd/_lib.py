@@ -72,6 +72,16 @@ class ShardStats(C.Structure):
                 ("commDeviceMs", _dbl), ("commEvents", _i64), ("overlapDepth", _i32), ("nRanks", _i32), ("rank", _i32)]
 
 
+class SinkRecord(C.Structure):
+    """cpf_sink_record (include/cpf.h "sink log"): 64 bytes, the layout of ``api.SINK_LOG_DTYPE``"""
+    _fields_ = [("id", _i64), ("apply", _u32), ("cycle", _u32), ("x", _dbl), ("y", _dbl), ("z", _dbl), ("dose", _dbl),
+                ("age", _u32), ("cell", _i32), ("origin", C.c_uint8), ("group", C.c_uint8), ("zone", C.c_uint8),
+                ("fields", C.c_uint8), ("reserved", _u32)]
+
+
+SINK_LOG_AGE, SINK_LOG_TAGS, SINK_LOG_EXPOSURE, SINK_LOG_ZONES = 1, 2, 4, 8     # bits of cpf_sink_record.fields
+
+
 _shard = C.c_void_p
 # the cpf_shard_* entry points: exported by the product library AND, over a host-memory stand-in device, by the tests' own
 # tests/host_shard/libcpf_shard_host.so (see bind_shard_signatures)
@@ -204,6 +214,11 @@ SIGNATURES = {
     "cpf_get_zone_flows": (_int, [_ctx, _vp, _vp]),
     "cpf_zone_get_last": (_int, [_ctx, _vp]),
     "cpf_zone_set_last": (_int, [_ctx, _vp]),
+    "cpf_sink_log_enable": (_int, [_ctx, _i64]),
+    "cpf_sink_log_disable": (_int, [_ctx]),
+    "cpf_sink_log_clear": (_int, [_ctx]),
+    "cpf_sink_log_counts": (_int, [_ctx, C.POINTER(_i64), C.POINTER(_i64)]),
+    "cpf_sink_log_read": (_int, [_ctx, _vp, _i64, C.POINTER(_i64)]),
     "cpf_source_picks_host": (_int, [_u32, _vp, _i64, _u32, _vp, _i64, _vp]),
     "cpf_set_velocity": (_int, [_ctx, _vp, _i64]),
     "cpf_set_velocity_dev": (_int, [_ctx, _vp, _i64]),

@@ -26,6 +26,14 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+# cpf_sink_record (include/cpf.h "sink log"): what ``Context.sink_log_read`` returns, 64 bytes a record, little-endian
+SINK_LOG_DTYPE = np.dtype({
+    "names": ["id", "apply", "cycle", "x", "y", "z", "dose", "age", "cell", "origin", "group", "zone", "fields", "reserved"],
+    "formats": ["<i8", "<u4", "<u4", "<f8", "<f8", "<f8", "<f8", "<u4", "<i4", "u1", "u1", "u1", "u1", "<u4"],
+    "offsets": [0, 8, 12, 16, 24, 32, 40, 48, 52, 56, 57, 58, 59, 60],
+    "itemsize": 64})
+
+
 class Context:
     """One GPU, one mesh, one (optional) context-owned particle cloud."""
 
@@ -628,6 +636,40 @@ class Context:
         nobody entered."""
         return zone_residence(self.zone_flows()[0], sample_dt)
 
+    # -- the sink log: one record per absorbed particle, appended on the device (include/cpf.h "sink log")
+    def sink_log_enable(self, capacity: int):
+        """Turns the sink log of the context-owned cloud on (or starts it anew) with room for ``capacity`` records: from now on
+        every ``sink_apply`` first appends one ``SINK_LOG_DTYPE`` record per particle it is about to absorb."""
+        self._ck(self.lib.cpf_sink_log_enable(self.h, int(capacity)))
+
+    def sink_log_disable(self):
+        self._ck(self.lib.cpf_sink_log_disable(self.h))
+
+    def sink_log_counts(self):
+        """(stored, dropped): the records held, and the absorbed particles that found the buffer full; synchronises."""
+        stored, dropped = C.c_int64(), C.c_int64()
+        self._ck(self.lib.cpf_sink_log_counts(self.h, C.byref(stored), C.byref(dropped)))
+        return stored.value, dropped.value
+
+    def sink_log_read(self, max_records: Optional[int] = None) -> np.ndarray:
+        """The stored records sorted by (apply, id), all of them or the first ``max_records``; the log stays as it is;
+        synchronises."""
+        room = self.sink_log_counts()[0] if max_records is None else int(max_records)
+        rec = np.zeros(max(room, 0), SINK_LOG_DTYPE)
+        got = C.c_int64()
+        self._ck(self.lib.cpf_sink_log_read(self.h, _ptr(rec) if rec.size else None, room, C.byref(got)))
+        return rec[:got.value]
+
+    def sink_log_clear(self):
+        """Forgets the records (and the dropped count); ``apply`` goes on counting.  Asynchronous."""
+        self._ck(self.lib.cpf_sink_log_clear(self.h))
+
+    def sink_log_drain(self) -> np.ndarray:
+        """``sink_log_read()``, then ``sink_log_clear()``."""
+        rec = self.sink_log_read()
+        self.sink_log_clear()
+        return rec
+
     def cell_ranges_dev(self, weights, n_ranks, cell_lo):
         self._ck(self.lib.cpf_cell_ranges_dev(self.h, weights, n_ranks, cell_lo))
 
@@ -998,6 +1040,11 @@ class CudaParticles:
     multiple of ``zoneInterval`` every live particle adds one to ``zone_flows()[0][its zone at the last such point][its zone
     now]``, before the recycle point's absorption if one is due, so the absorbed leave from the zone they are in;
     ``zone_residence()`` is the mean time of a visit per zone.
+
+    One more: ``sinkLog`` (a capacity in records; default 0 = off), which needs ``recycleInterval`` > 0 and ``sinkCells``.  The
+    sink log (``Context.sink_log_enable``) then starts behind zones: every absorption appends one ``SINK_LOG_DTYPE`` record --
+    id, cycle, exit point, age, origin, sink group, dose and zone, as far as those groups are on.  ``sink_log()`` drains it;
+    nothing else does, and what finds the log full is counted as dropped.
     """
 
     def __init__(self, mesh, U, particle_dict: Optional[dict] = None, device: int = 0,
@@ -1065,6 +1112,12 @@ class CudaParticles:
             if self.zoneInterval < 1:
                 raise ValueError("zoneInterval must be >= 1")
             self.zoneMap = np.ascontiguousarray(zone_map, dtype=np.int32)
+        self.sinkLog = d.get("sinkLog", 0)
+        if isinstance(self.sinkLog, bool) or not isinstance(self.sinkLog, (int, np.integer)) or self.sinkLog < 0:
+            raise ValueError("sinkLog must be a non-negative int, the capacity in records")
+        self.sinkLog = int(self.sinkLog)
+        if self.sinkLog > 0 and (self.recycleInterval <= 0 or self.sinkCells is None):
+            raise ValueError("sinkLog needs recycleInterval > 0 and sinkCells")
         # hard-coded switches of the fragment (src/initCuda.H:64-72)
         self.usingAdvection = True
         self.usingBrownianMotion = True
@@ -1107,6 +1160,8 @@ class CudaParticles:
         if self.zoneMap is not None:
             self.ctx.zone_enable(int(self.zoneMap.max()) + 1)
             self.ctx.set_zone_map(self.zoneMap)
+        if self.sinkLog > 0:
+            self.ctx.sink_log_enable(self.sinkLog)
         if self.writer is not None:
             # frame 0 carries the velocities of one advect and out-of-domain particles as inactive, like the reference
             # (src/initCuda.H:184-201): a cycle of zero length (moves nothing, does not count as a step)
@@ -1229,6 +1284,13 @@ class CudaParticles:
     def zone_residence(self):
         """Mean time of a visit per zone in seconds, with ``zoneMap`` set (``Context.zone_residence``)."""
         return self.ctx.zone_residence(self.zoneInterval * self.dt)
+
+    def sink_log(self):
+        """(records, dropped) with ``sinkLog`` set: the ``SINK_LOG_DTYPE`` records of the absorbed since the last call, sorted by
+        (apply, id), and how many more found the log full; the log is empty afterwards (``Context.sink_log_drain``).  Nothing else
+        drains it: call often enough for the capacity."""
+        dropped = self.ctx.sink_log_counts()[1]
+        return self.ctx.sink_log_drain(), dropped
 
     def close(self):
         self.ctx.close()

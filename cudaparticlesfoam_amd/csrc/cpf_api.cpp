@@ -164,6 +164,17 @@ struct Zones {
 constexpr int32_t kZoneMax = 63;            // zones at most: zone_sample_kernel stages (nZones + 1)^2 <= 4096 words in LDS
 constexpr uint8_t kZoneOutside = 0xFF;
 
+// Sink log of the context's own cloud (cpf_sink_log_*; cpf_sinklog.hip).  The records speak of a cloud and a mesh: a new cloud and
+// a new mesh each replace the group with an empty one.  The five groups above know nothing of it; it reads their tables at an
+// apply, whichever of them are on then.
+struct SinkLog {
+    bool on = false;
+    int64_t capacity = 0;
+    uint32_t apply = 0;                     // logged applies since enable: the next one's index
+    DevBuf<cpf_sink_record> rec;            // [capacity]
+    DevBuf<unsigned long long> cursor;      // [1] absorbed particles since enable or the last clear, stored or not
+};
+
 // asynchronous output (cpf_write_vtu_async): one frame in flight.  Lives as long as the context.
 struct FrameWriter {
     std::thread thread;
@@ -236,7 +247,7 @@ struct cpf_context {
     bool vertexFast = true;                     // cpf_set_option("vertex_fast")
     uint32_t seed = 1591593751u;                // cuda/particles.cu:544
     // ---- the groups
-    Mesh mesh; TetField tet; Cloud cloud; Age age; Tags tags; Routes routes; Exposure exposure; Zones zones; FrameWriter frame; Timing timing;
+    Mesh mesh; TetField tet; Cloud cloud; Age age; Tags tags; Routes routes; Exposure exposure; Zones zones; SinkLog sinkLog; FrameWriter frame; Timing timing;
     // ---- what lives as long as the context
     DevBuf<char> scratch;
     size_t scratchBytes = 0;
@@ -351,6 +362,15 @@ int dropZones(cpf_context* ctx) {
     return CPF_OK;
 }
 
+// the sink log off (cpf_sink_log_disable; a new cloud): a pass may still be appending
+int dropSinkLog(cpf_context* ctx) {
+    if (!ctx->sinkLog.on) return CPF_OK;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->sinkLog = SinkLog{};
+    return CPF_OK;
+}
+
 // routes off (cpf_route_disable; age or tags going off or starting anew): a pass over the tables may still be running
 int dropRoutes(cpf_context* ctx) {
     if (!ctx->routes.on) return CPF_OK;
@@ -438,6 +458,7 @@ int setMeshImpl(cpf_context* ctx, const double* points, int64_t nPoints, const L
     ctx->routes = Routes{};
     ctx->exposure = Exposure{};
     ctx->zones = Zones{};
+    ctx->sinkLog = SinkLog{};
     ctx->streamState.flatField = false;
     ctx->mesh.host = std::move(t);
     ctx->mesh.nParent = nCells;
@@ -989,6 +1010,7 @@ int cpf_alloc_particles(cpf_context* ctx, int64_t capacity) {
     ctx->routes = Routes{};
     ctx->exposure = Exposure{};
     ctx->zones = Zones{};
+    ctx->sinkLog = SinkLog{};
     const size_t c = (size_t)capacity;
     CPF_HIP(ctx, ctx->cloud.cur.alloc(c));
     CPF_HIP(ctx, ctx->cloud.vel.alloc(c * 3));
@@ -1005,6 +1027,7 @@ int cpf_seed_box(cpf_context* ctx, int64_t n, const double lower[3], const doubl
     if (int r = dropAge(ctx)) return r;                     // (a new cloud: the stamps were the old one's)
     if (int r = dropTags(ctx)) return r;                    // (... and so were the origins)
     if (int r = dropZones(ctx)) return r;                   // (... and the last zones)
+    if (int r = dropSinkLog(ctx)) return r;                 // (... and the records)
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, cpf::launch_seed_box(ctx->stream, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, 0, n, lower, upper, order));
     CPF_HIP(ctx, cpf::launch_iota64(ctx->stream, ctx->cloud.cur.gid, n, 0));
@@ -1022,6 +1045,8 @@ int cpf_set_particles(cpf_context* ctx, int64_t n, const double* xyz, const int3
     r = dropTags(ctx);                                      // (... and so were the origins)
     if (r) return r;
     r = dropZones(ctx);                                     // (... and the last zones)
+    if (r) return r;
+    r = dropSinkLog(ctx);                                   // (... and the records)
     if (r) return r;
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     ctx->cloud.zSettled = false;
@@ -1561,6 +1586,28 @@ int cpf_sink_apply(cpf_context* ctx) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_sink_apply: call cpf_set_mesh first");
     CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_sink_apply: no located particles");
+    if (ctx->sinkLog.on && ctx->mesh.sinkMask) {
+        // the sink log: a read-only pass of its own appends one record for everybody the sink is about to absorb, made of what the
+        // cloud and the tables of the groups that are on hold now, before anyone is marked (cpf_sinklog.hip); then everything
+        // below, as without it
+        SinkLog& lg = ctx->sinkLog;
+        cpf::SinkLogView v{};
+        v.x = ctx->cloud.cur.x; v.y = ctx->cloud.cur.y; v.z = ctx->cloud.cur.z; v.cell = ctx->cloud.cur.cell; v.gid = ctx->cloud.cur.gid;
+        v.birth = ctx->age.on ? ctx->age.birth.get() : nullptr;
+        v.origin = ctx->tags.on ? ctx->tags.origin.get() : nullptr;
+        v.sinkGroup = ctx->tags.on ? ctx->tags.sinkGroup.get() : nullptr;
+        v.dose = ctx->exposure.on ? ctx->exposure.dose.get() : nullptr;
+        v.last = ctx->zones.on ? ctx->zones.last.get() : nullptr;
+        v.parentOf = ctx->mesh.parentOf.get();
+        v.mask = ctx->mesh.sinkMask; v.cursor = lg.cursor; v.rec = lg.rec;
+        v.n = ctx->cloud.n; v.capacity = lg.capacity;
+        v.now = ctx->stepCounter; v.apply = lg.apply;
+        v.fields = (ctx->age.on ? CPF_SINK_LOG_AGE : 0u) | (ctx->tags.on ? CPF_SINK_LOG_TAGS : 0u) |
+                   (ctx->exposure.on ? CPF_SINK_LOG_EXPOSURE : 0u) | (ctx->zones.on ? CPF_SINK_LOG_ZONES : 0u);
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        CPF_HIP(ctx, cpf::sink_log(ctx->stream, v, ctx->mesh.host.nCells));
+        ++lg.apply;
+    }
     if (ctx->exposure.on && ctx->mesh.sinkMask) {
         // exposure: a read-only pass of its own bins the dose of everybody the sink is about to absorb, before anyone is marked
         // (cpf_exposure.hip); then whichever of the three paths below applies, as without it
@@ -2360,6 +2407,80 @@ int cpf_exposure_bins_host(const double* dose, int64_t n, double binWidth, int32
     if (n < 0 || !std::isfinite(binWidth) || !(binWidth > 0.0) || nBins < 1 || (n > 0 && (!dose || !bin))) return CPF_ERR_ARG;
     const double invWidth = 1.0 / binWidth;
     for (int64_t i = 0; i < n; ++i) bin[i] = cpf::exposure_bin(dose[i], invWidth, nBins);
+    return CPF_OK;
+}
+
+// ---- the sink log: one record per absorbed particle, appended on the device (cpf_sinklog.hip) ----------------------------------
+int cpf_sink_log_enable(cpf_context* ctx, int64_t capacity) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_sink_log_enable: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_sink_log_enable: no located particles");
+    CPF_REQUIRE(ctx, capacity >= 1 && capacity < ((int64_t)1 << 40), CPF_ERR_ARG, "cpf_sink_log_enable: capacity must be in [1, 2^40)");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass may still be appending to the old buffer)
+    ctx->sinkLog = SinkLog{};
+    SinkLog lg;                                             // moved in whole: a failure part-way leaves the log off
+    CPF_HIP(ctx, lg.rec.alloc((size_t)capacity));
+    CPF_HIP(ctx, lg.cursor.alloc(1));
+    CPF_HIP(ctx, hipMemsetAsync(lg.cursor, 0, 8, ctx->stream));
+    lg.on = true; lg.capacity = capacity;
+    ctx->sinkLog = std::move(lg);
+    return CPF_OK;
+}
+
+int cpf_sink_log_disable(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    return dropSinkLog(ctx);
+}
+
+int cpf_sink_log_clear(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->sinkLog.on, CPF_ERR_STATE, "cpf_sink_log_clear: call cpf_sink_log_enable first");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemsetAsync(ctx->sinkLog.cursor, 0, 8, ctx->stream));
+    return CPF_OK;
+}
+
+namespace {
+// the cursor as the device holds it once the stream has drained
+int sinkLogCursor(cpf_context* ctx, uint64_t* cursor) {
+    unsigned long long c = 0;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipMemcpyAsync(&c, ctx->sinkLog.cursor, 8, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *cursor = (uint64_t)c;
+    return CPF_OK;
+}
+}  // namespace
+
+int cpf_sink_log_counts(cpf_context* ctx, int64_t* stored, int64_t* dropped) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->sinkLog.on, CPF_ERR_STATE, "cpf_sink_log_counts: call cpf_sink_log_enable first");
+    uint64_t cursor = 0;
+    if (int r = sinkLogCursor(ctx, &cursor)) return r;
+    const uint64_t kept = std::min(cursor, (uint64_t)ctx->sinkLog.capacity);
+    if (stored) *stored = (int64_t)kept;
+    if (dropped) *dropped = (int64_t)(cursor - kept);
+    return CPF_OK;
+}
+
+int cpf_sink_log_read(cpf_context* ctx, cpf_sink_record* rec, int64_t maxRecords, int64_t* nRead) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->sinkLog.on, CPF_ERR_STATE, "cpf_sink_log_read: call cpf_sink_log_enable first");
+    CPF_REQUIRE(ctx, maxRecords >= 0 && (rec || maxRecords == 0), CPF_ERR_ARG, "cpf_sink_log_read: bad arguments");
+    uint64_t cursor = 0;
+    if (int r = sinkLogCursor(ctx, &cursor)) return r;
+    const size_t kept = (size_t)std::min(cursor, (uint64_t)ctx->sinkLog.capacity);
+    const size_t take = std::min(kept, (size_t)maxRecords);
+    if (nRead) *nRead = (int64_t)take;
+    if (take == 0) return CPF_OK;
+    // the order on the device is whichever workgroup reserved first: sorted here by the unique key (apply, id)
+    std::vector<cpf_sink_record> all(kept);
+    CPF_HIP(ctx, hipMemcpy(all.data(), ctx->sinkLog.rec, kept * sizeof(cpf_sink_record), hipMemcpyDeviceToHost));
+    std::sort(all.begin(), all.end(), [](const cpf_sink_record& a, const cpf_sink_record& b) {
+        return a.apply != b.apply ? a.apply < b.apply : a.id < b.id;
+    });
+    std::memcpy(rec, all.data(), take * sizeof(cpf_sink_record));
     return CPF_OK;
 }
 

@@ -354,6 +354,27 @@ hipError_t zone_sample(hipStream_t st, const int32_t* cell, const int64_t* gid, 
 hipError_t zone_leave(hipStream_t st, const int32_t* cell, const int64_t* gid, const uint8_t* last, int64_t n, const uint32_t* mask,
                       int64_t nDerived, int32_t nZones, unsigned long long* flow);
 hipError_t zone_stamp(hipStream_t st, const int32_t* cell, const int64_t* gid, uint8_t* last, int64_t n);
+// sink log (cpf_sinklog.hip).  Reads only, but for the cursor and the records: for every i that sink_apply would absorb, one
+// cpf_sink_record at rec[k], k the index a returning add on *cursor reserved, unless k >= capacity.  The tables by id (birth,
+// origin, dose, last: n entries, id = gid[slot]; gid null: the slot) and by DERIVED cell (sinkGroup, parentOf) are nullable:
+// null is "that group is off" (parentOf: no cell decomposed), and the record's field takes its off value (include/cpf.h).
+struct SinkLogView {
+    const double *x, *y, *z;
+    const int32_t* cell;
+    const int64_t* gid;
+    const uint32_t* birth;
+    const uint8_t* origin;
+    const double* dose;
+    const uint8_t* last;
+    const uint8_t* sinkGroup;
+    const int32_t* parentOf;
+    const uint32_t* mask;
+    unsigned long long* cursor;
+    cpf_sink_record* rec;                   // 16-byte aligned
+    int64_t n, capacity;
+    uint32_t now, apply, fields;
+};
+hipError_t sink_log(hipStream_t st, const SinkLogView& v, int64_t nDerived);
 hipError_t unpack_arrivals(hipStream_t st, double* x, double* y, double* z, int32_t* cell, int64_t* gid,
                            int64_t nStay, const double* recvbuf, int64_t nRecv);
 // output of a sharded cloud (cpf_shard_gather): records of kOutputDoubles doubles = x, y, z, cell, gid, vx, vy, vz

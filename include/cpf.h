@@ -752,6 +752,72 @@ int cpf_zone_get_last(cpf_context* ctx, uint8_t* last);
 int cpf_zone_set_last(cpf_context* ctx, const uint8_t* last);
 
 /* ---------------------------------------------------------------------------------------------
+ * sink log: one record per absorbed particle, appended on the device -- who was absorbed, when, where and with what state: the
+ * list every table of the groups above is a reduction of (an exact percentile of the residence time, the joint distribution of
+ * age and dose, where on the outlet a feed's tracer leaves, the ids to hand to the inlet of another domain)
+ * NO REFERENCE COUNTERPART for any entry of this group.  The state is a buffer of `capacity` records on the device, a 64-bit
+ * cursor there that counts every absorbed particle since the last enable or clear, and `apply`, the number of logged
+ * cpf_sink_apply calls since the last enable.  A record is 64 bytes, little-endian:
+ * ------------------------------------------------------------------------------------------- */
+typedef struct cpf_sink_record {
+    int64_t id;         /*  0  particle id (the order of cpf_get_particles) */
+    uint32_t apply;     /*  8  index of this cpf_sink_apply among those logged since cpf_sink_log_enable, from 0 */
+    uint32_t cycle;     /* 12  the context's step counter at the apply (the clock age tracking uses) */
+    double x;           /* 16  the position as stored: the point the particle was found at, the same bits as cpf_get_particles */
+    double y;           /* 24  */
+    double z;           /* 32  */
+    double dose;        /* 40  dose[id] as exposure's absorb pass reads it; 0.0 while exposure is off */
+    uint32_t age;       /* 48  cycle - birth[id], the unsigned 32-bit difference of cpf_get_ages; 0 while age tracking is off */
+    int32_t cell;       /* 52  the cell of the mesh AS GIVEN the particle was found in */
+    uint8_t origin;     /* 56  origin[id]; 0xFF while tagging is off */
+    uint8_t group;      /* 57  the sink group of `cell`; 0xFF while tagging is off */
+    uint8_t zone;       /* 58  last[id], the zone at the last sample (0xFF = outside); 0xFF while zones are off */
+    uint8_t fields;     /* 59  which groups were on at this apply: CPF_SINK_LOG_AGE | _TAGS | _EXPOSURE | _ZONES */
+    uint32_t reserved;  /* 60  0 */
+} cpf_sink_record;
+#define CPF_SINK_LOG_AGE 1
+#define CPF_SINK_LOG_TAGS 2
+#define CPF_SINK_LOG_EXPOSURE 4
+#define CPF_SINK_LOG_ZONES 8
+#ifdef __cplusplus
+static_assert(sizeof(cpf_sink_record) == 64, "a sink-log record is 64 bytes");
+#else
+_Static_assert(sizeof(cpf_sink_record) == 64, "a sink-log record is 64 bytes");
+#endif
+/* While the log is on and a sink set exists,
+ *   cpf_sink_apply      first runs ONE read-only pass, ahead of exposure's and zones' passes and before anyone is marked, which
+ *                       appends one record for every particle the sink is about to absorb (a live cell whose bit is set in the
+ *                       sink set); then it does exactly what it does without the log, with the five other groups on or off: the
+ *                       cloud, the counters and every table are the same bits.  A group switched on or off between two applies
+ *                       shows in `fields`.
+ * Capacity: the cursor counts every absorbed particle; a record whose index is >= capacity is not written.  stored = min(cursor,
+ * capacity), dropped = cursor - stored.  All records of an apply that fitted are complete; WHICH records of an overflowing apply
+ * are the stored ones is unspecified (whichever workgroup reserved first), but each stored one is whole and no id is stored twice.
+ * Order: the order on the device is unspecified; cpf_sink_log_read returns the records sorted by (apply, id).  An id sits in
+ * exactly one slot, so the key is unique: while dropped == 0 the bytes returned are a pure function of the run, whatever the
+ * order of the cloud.
+ * It logs what the sink absorbs, where it is found -- not a crossing of the outlet --, and no respawn.  The log covers the
+ * CONTEXT-OWNED cloud only: cpf_shard_*, the _dev entries (cpf_sink_apply_dev among them) and the replacement fragments neither
+ * read nor write it.  While it is off every call launches exactly what it launches without this group.
+ * The records belong to a cloud and a mesh: cpf_alloc_particles, cpf_seed_box, cpf_set_particles and cpf_set_mesh* turn the log
+ * off.  Age tracking, tagging, routes, exposure and zones are independent of it, in both directions.  Every entry but
+ * cpf_sink_log_enable and cpf_sink_log_disable returns CPF_ERR_STATE while it is off.
+ * ------------------------------------------------------------------------------------------- */
+/* NO REFERENCE COUNTERPART.  Turns the log on with room for `capacity` records, or starts it anew: cursor and apply are 0.
+ * CPF_ERR_STATE without a mesh or without located particles; CPF_ERR_ARG unless capacity >= 1. */
+int cpf_sink_log_enable(cpf_context* ctx, int64_t capacity);
+/* NO REFERENCE COUNTERPART.  Turns the log off and frees the buffer (no error when it is off already). */
+int cpf_sink_log_disable(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  Zeroes the cursor (asynchronous): the next record is the first; apply goes on counting. */
+int cpf_sink_log_clear(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  Waits for the context's stream; *stored and *dropped as above (each nullable). */
+int cpf_sink_log_counts(cpf_context* ctx, int64_t* stored, int64_t* dropped);
+/* NO REFERENCE COUNTERPART.  Waits for the context's stream; copies the first min(stored, maxRecords) records of the stored
+ * ones sorted by (apply, id) to rec and writes their number to *nRead (nullable).  CPF_ERR_ARG for maxRecords < 0 or a null rec
+ * with maxRecords > 0.  The log is not changed. */
+int cpf_sink_log_read(cpf_context* ctx, cpf_sink_record* rec, int64_t maxRecords, int64_t* nRead);
+
+/* ---------------------------------------------------------------------------------------------
  * device-array level (framework hosts that own the particle arrays, multi-GPU sharding)
  * SoA fp64 positions x,y,z [n]; cell [n] int32; gid [n] int64 global particle id (nullable:
  * gid = index); vel [n][3] (nullable unless CPF_STEP_STORE_VEL).

@@ -98,6 +98,13 @@ def collect_zones():
     return parse(r.stderr, ("zone_",))
 
 
+def collect_sinklog():
+    """The same rows for the sink log's kernel (cpf_sinklog.hip: sink_log_kernel); collect() does not list it.  All its LDS is
+    static."""
+    r = subprocess.run(hipcc_cmd("cpf_sinklog.hip") + ["-c", "-o", "/dev/null"], capture_output=True, text=True)
+    return parse(r.stderr, ("sink_log_",))
+
+
 def kernel_bodies(asm):
     """mangled kernel name -> its instructions (labels, directives and comments dropped).  Only what the listing types as a
     function: a library's constant table (rocprim has one) is a _Z label too, and the text behind the last one is the metadata."""
