@@ -1,6 +1,6 @@
 // C-ABI layer of libcudaParticleAdvection.so: context, device memory, call-order checks, errors.
-// Every entry point declared in include/cpf.h is defined here; kernels live in cpf_kernels.hip,
-// cpf_sort.hip and cpf_handoff.hip, the host-side mesh ingest in cpf_mesh.cpp.
+// The entry points declared in include/cpf.h are defined here, but for the tracer ledger's (cpf_ledger.cpp); kernels live in
+// cpf_kernels.hip, cpf_sort.hip and cpf_handoff.hip, the host-side mesh ingest in cpf_mesh.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,265 +15,15 @@
 #include <vector>
 
 #include "cpf.h"
+#include "cpf_context.h"   // cpf_context and its groups, fail, CPF_HIP, CPF_REQUIRE
 #include "cpf_device.h"
-#include "cpf_exposure_bins.h"   // exposure_bin (cpf_exposure_bins_host)
 #include "cpf_internal.h"
 #include "cpf_own.h"
 #include "cpf_philox.h"    // respawn_position (cpf_respawn_positions_host)
 #include "cpf_walk.h"      // VertexField
 
-// (device-scope release is all a time stamp needs; measured against the default flags: no difference)
-#ifndef CPF_TIMING_EVENT_FLAGS
-#define CPF_TIMING_EVENT_FLAGS hipEventReleaseToDevice
-#endif
-
-namespace {
-using cpf::DevBuf; using cpf::Event; using cpf::PinnedBuf;
-
-// What the context owns, grouped by lifetime: each group goes away as a whole -- assigned over with an empty one, or with the
-// context.  The members are owners (cpf_own.h): nothing here is freed by hand.
-
-// The mesh: the host tables and every device table made from them.  Replaced by cpf_set_mesh.
-struct Mesh {
-    bool have = false, haveU = false;
-    cpf::HostTables host;
-    DevBuf<int32_t> cellOff, nbr, groupOff, groupNbr;
-    DevBuf<double4> planes;
-    DevBuf<double4> U;
-    DevBuf<double> U3;          // staging for host uploads
-    DevBuf<double> boxRec;      // 128-byte box records (meshes of axis-aligned boxes with records; cpf_walk.h "box records")
-    DevBuf<double4> cellRec;    // packed per-cell records (all-hex meshes; mixed meshes: cpf_walk.h "cell records")
-    int64_t nSecondRecords = 0; // second records (cells with 7..12 slots), behind the nCells first ones
-    DevBuf<float> cellBox;      // per-cell boxes for the sort key
-    DevBuf<int32_t> curveRank;  // per-cell rank along the Morton curve: the sort's major key for sparse clouds ("sort_curve")
-    DevBuf<int32_t> binOff, binCells;
-    size_t bytes = 0;           // of the device tables (cpf_mesh_info)
-    // warped / concave cells (cpf_mesh.cpp: measure_mesh, derive_mesh; DESIGN.md "Warped cells")
-    cpf_mesh_quality quality{};         // of the mesh as the caller gave it
-    int64_t nParent = 0;                // cells of the mesh as given: == host.nCells unless cells were decomposed
-    std::vector<int32_t> first;         // [nParent+1] derived cells of parent c: first[c] .. first[c+1] (decomposed meshes only)
-    DevBuf<int32_t> parentOf;           // [host.nCells] parent of every derived cell; null: no cell decomposed
-    DevBuf<double> Uparent;             // [nParent][3] staging of cpf_set_velocity on a decomposed mesh
-    std::vector<double> volume;         // [nParent] OpenFOAM's cell volumes of the mesh as given (cpf_get_cell_volumes)
-    // per-cell occupancy (cpf_occupancy_sample*; cpf_occupancy.hip): it belongs to the mesh and goes with it
-    DevBuf<unsigned long long> occupancy;   // [nParent] accumulated counts; null until the first sample
-    int64_t occupancySamples = 0;           // samples added since the last reset
-    // recycling (cpf_set_sink_cells; cpf_recycle.hip): the sink set belongs to the mesh and goes with it
-    DevBuf<uint32_t> sinkMask;              // one bit per DERIVED cell, ceil(host.nCells / 32) words; null: no sink set
-    // patch source (cpf_set_source_triangles; cpf_inlet.hip): it belongs to the mesh too
-    DevBuf<double> sourceRec;               // [sourceKept][16] triangle records; null: no source
-    DevBuf<uint32_t> sourceHi;              // [sourceKept] bounds, padded with 0xFFFFFFFF to a multiple of 4 entries
-    int64_t sourceKept = 0;
-    std::vector<double> sourceRecHost;      // the table as built (cpf_get_source_table)
-    std::vector<uint32_t> sourceHiHost;
-};
-
-// "VertexVelocity" advect only: the tet decomposition and one velocity per tet-mesh vertex.  It belongs to the mesh it was made
-// for (cpf_set_tets checks it against that mesh's cell count): a new mesh starts without one.  Built by cpf_set_tets into a
-// local and moved in whole, so nTets, tetsPerCell and the cone pair never describe tables that do not exist.
-struct TetField {
-    DevBuf<double> pos; DevBuf<int32_t> tets; DevBuf<double> vel;
-    int64_t nVerts = 0, nTets = 0; int tetsPerCell = 0; bool haveVel = false;
-    DevBuf<double> cone;        // cone-locate tet records (cpf_walk.h, VertexField), if the decomposition admits them
-    DevBuf<double> apex;        // ... and the cells' apexes: both or neither
-    std::string coneWhy;        // why the tables were not built (cpf_step_kernel_name says so)
-};
-
-struct CloudArrays {
-    DevBuf<double> x, y, z;
-    DevBuf<int32_t> cell;
-    DevBuf<int64_t> gid;
-    hipError_t alloc(size_t c) {                // (stops at the first failure)
-        hipError_t e;
-        (void)((e = x.alloc(c)) || (e = y.alloc(c)) || (e = z.alloc(c)) || (e = cell.alloc(c)) || (e = gid.alloc(c)));
-        return e;
-    }
-};
-// The context's own cloud.  Replaced by cpf_alloc_particles.
-struct Cloud {
-    int64_t cap = 0, n = 0;
-    CloudArrays cur;
-    // second set of x, y, z, cell, gid: the sort writes the reordered cloud there and the sets swap roles (no copy back);
-    // allocated by the first sort, all five or none
-    CloudArrays spare;
-    DevBuf<double> vel;
-    bool located = false;
-    // z of the cloud is a fixed point of the flat cycle (CPF_STEP_Z_SETTLED): set behind a flat launch that streamed z, cleared
-    // by everything else that writes x, y, z or cell -- except a sort, which only permutes
-    bool zSettled = false;
-    uint32_t respawnEpoch = 0;  // cpf_respawn_box calls on this cloud so far: the epoch of the next one's positions
-};
-
-// Tracer age of the context's own cloud (cpf_age_*; cpf_age.hip).  The stamps belong to a cloud, the field to a mesh: a new cloud
-// and a new mesh each replace the group with an empty one.
-struct Age {
-    bool on = false;
-    int32_t binCycles = 1, nBins = 0;
-    DevBuf<uint32_t> birth;                 // [cloud.n] by particle id: the cycle counter when the particle last became live
-    DevBuf<unsigned long long> hist;        // [nBins] absorptions by age / binCycles, the last bin open-ended
-    DevBuf<unsigned long long> field;       // [nParent][2] = age sum, count of the samples since the last reset
-    int64_t samples = 0;
-};
-
-// Tracer tags of the context's own cloud (cpf_tag_*; cpf_tags.hip).  The origins belong to a cloud, the groups and the field to a
-// mesh: a new cloud and a new mesh each replace the group with an empty one.
-struct Tags {
-    bool on = false;
-    int32_t nOrigins = 1, nSinks = 1, boxOrigin = 0;
-    DevBuf<uint8_t> origin;                 // [cloud.n] by particle id: the origin of the respawn that last made the particle live
-    DevBuf<uint8_t> sinkGroup;              // [host.nCells] the group of every DERIVED cell (read for cells of the sink mask only)
-    DevBuf<uint8_t> originOfKept;           // [sourceKept] the origin of every kept record of the source table; null: no source
-    DevBuf<unsigned long long> transfer;    // [nOrigins][nSinks] absorptions (room for kTagMax x kTagMax)
-    DevBuf<unsigned long long> field;       // [nParent][nOrigins] counts of the samples since the last reset
-    int64_t samples = 0;
-};
-constexpr int32_t kTagMax = 16;
-
-// Routes of the context's own cloud (cpf_route_*; cpf_routes.hip): tables sized by age's nBins and tags' nOrigins, nSinks, so the
-// group lives only while both are on and is replaced by an empty one with either of them.
-struct Routes {
-    bool on = false;
-    DevBuf<unsigned long long> hist;        // [nOrigins][nSinks][nBins] absorptions by route and age / binCycles
-    DevBuf<unsigned long long> field;       // [nParent][nOrigins][2] = age sum, count of the samples since the last reset
-    int64_t samples = 0;
-};
-
-// Exposure of the context's own cloud (cpf_exposure_*; cpf_exposure.hip).  The doses belong to a cloud, the rates to a mesh, the
-// histogram's shape to tagging: a new cloud, a new mesh and tagging going on or off each replace the group with an empty one.
-struct Exposure {
-    bool on = false;
-    double binWidth = 0.0, invWidth = 0.0;  // invWidth = 1.0 / binWidth, computed once (cpf_exposure_bins.h)
-    int32_t nBins = 0, nOrigins = 1, nSinks = 1;
-    bool tagged = false;                    // tagging was on at enable time: origin and sink group are read, else both are 0
-    DevBuf<double> dose;                    // [cloud.n] by particle id: the sum since the particle last became live
-    DevBuf<double> rate;                    // [host.nCells] per DERIVED cell: the caller's field expanded through `first`
-    DevBuf<unsigned long long> hist;        // [nOrigins][nSinks][nBins] absorptions by origin, sink group and dose bin
-};
-constexpr int32_t kExposureWords = 4096;    // histogram words at most: exposure_absorb_kernel stages them in LDS
-
-// Zones of the context's own cloud (cpf_zone_*; cpf_zones.hip).  The last zones belong to a cloud, the map to a mesh: a new cloud
-// and a new mesh each replace the group with an empty one.  Age, tags, routes and exposure know nothing of it, nor it of them.
-struct Zones {
-    bool on = false;
-    int32_t nZones = 0;
-    DevBuf<uint8_t> zoneOf;                 // [host.nCells] per DERIVED cell: the caller's map expanded through `first`
-    DevBuf<uint8_t> last;                   // [cloud.n] by particle id: the zone at the last sample, kZoneOutside: none
-    DevBuf<unsigned long long> flow;        // [nZones + 1][nZones + 1] transitions from sample to sample; index nZones: outside
-    int64_t samples = 0;
-};
-constexpr int32_t kZoneMax = 63;            // zones at most: zone_sample_kernel stages (nZones + 1)^2 <= 4096 words in LDS
-constexpr uint8_t kZoneOutside = 0xFF;
-
-// Sink log of the context's own cloud (cpf_sink_log_*; cpf_sinklog.hip).  The records speak of a cloud and a mesh: a new cloud and
-// a new mesh each replace the group with an empty one.  The five groups above know nothing of it; it reads their tables at an
-// apply, whichever of them are on then.
-struct SinkLog {
-    bool on = false;
-    int64_t capacity = 0;
-    uint32_t apply = 0;                     // logged applies since enable: the next one's index
-    DevBuf<cpf_sink_record> rec;            // [capacity]
-    DevBuf<unsigned long long> cursor;      // [1] absorbed particles since enable or the last clear, stored or not
-};
-
-// asynchronous output (cpf_write_vtu_async): one frame in flight.  Lives as long as the context.
-struct FrameWriter {
-    std::thread thread;
-    bool live = false;
-    int status = CPF_OK;
-    // the frame's snapshot: packed in particle-id order on the compute stream into `snapDev`, copied to pinned host memory on
-    // `io` behind an event, read by the worker thread only -- the step loop's stream never waits for PCIe (round 6)
-    DevBuf<char> snapDev;
-    PinnedBuf<char> snapHost;
-    size_t snapBytes = 0;
-    cpf::Stream io;
-    Event evSnap, evCopied;
-    double ke = 0.0;                            // of the frame the worker wrote last (valid after its join)
-    std::mutex keMutex; std::condition_variable keCv; bool keReady = false;
-};
-
-// cpf_timing_*: event pairs round step launches.  Lives as long as the context.
-struct Timing {
-    int stride = 1;                             // "timing_stride": bracket every k-th step launch only
-    uint64_t launch = 0;
-    bool on = false;
-    std::vector<std::pair<Event, Event>> recorded;
-    std::vector<Event> pool;
-    hipError_t take(Event& ev) {
-        if (pool.empty()) return ev.create(CPF_TIMING_EVENT_FLAGS);
-        ev = std::move(pool.back()); pool.pop_back();
-        return hipSuccess;
-    }
-    void give_back(Event& ev) { if (ev) pool.push_back(std::move(ev)); }
-    // sums the recorded pairs and hands their events back, from the oldest on: all of them (the caller has synchronised), or,
-    // polling, those whose end has been reached -- launches complete in stream order
-    hipError_t drain(bool poll, int64_t* launches, double* total_ms) {
-        double tot = 0.0; size_t done = 0; hipError_t e = hipSuccess;
-        for (; done < recorded.size(); ++done) {
-            auto& p = recorded[done];
-            if (poll && (e = hipEventQuery(p.second)) != hipSuccess) break;
-            float ms = 0.f;
-            if ((e = hipEventElapsedTime(&ms, p.first, p.second)) != hipSuccess) break;
-            tot += (double)ms;
-            give_back(p.first); give_back(p.second);
-        }
-        recorded.erase(recorded.begin(), recorded.begin() + (std::ptrdiff_t)done);
-        if (e != hipSuccess && e != hipErrorNotReady) return e;
-        *launches = (int64_t)done;
-        *total_ms = tot;
-        return hipSuccess;
-    }
-};
-}  // namespace
-
-// Members are destroyed in reverse order: everything below is released before `ownStream` is.
-struct cpf_context {
-    int device = 0;
-    cpf::Stream ownStream;
-    hipStream_t stream = nullptr;               // ownStream, or the caller's (cpf_set_stream)
-    mutable std::string err;
-    // ---- options: they survive a new mesh and a new cloud
-    bool zFold = true;               // "z_fold": mirror the kicked end point about the planes of a one-cell-thick mesh before the walk
-    bool boxRecords = true;         // "box_records": 0 = never use them (diagnostics; bit-identical either way)
-    int sortMethod = 2;             // "sort_method": the (key, index) sort: 2 = this library's radix sort (cpf_sort.hip, rt_sort_pairs), 0 = hipcub's;
-                                    // the same order either way
-    int sortCurve = -1;             // "sort_curve": -1 = Morton rank when the cloud has fewer than 8 particles per cell, 0 = cell id, 1 = Morton rank
-    int sortInterval = 50;                      // "sort_interval": cpf_step re-sorts the owned cloud by cell every N cycles
-    bool stats = false;                         // "stats": per-launch counters (steps, cells visited, reflections, lost)
-    int stepVariant = -1;                       // cpf_set_option("step_variant"), see include/cpf.h: -1 = choose per launch
-    bool vtuBinary = false;                     // cpf_set_option("vtu_binary"): frames with raw appended arrays instead of the reference's ASCII
-    bool mixedRecords = true;                   // cpf_set_option("mixed_records"): build cell records for hex-dominant meshes too (before cpf_set_mesh)
-    double nonplanarTol = cpf::kNonPlanarTolDefault;    // "nonplanar_tol" (before cpf_set_mesh)
-    bool splitNonplanar = true;                         // "split_nonplanar" (before cpf_set_mesh): 0 = one plane per face everywhere
-    bool vertexFast = true;                     // cpf_set_option("vertex_fast")
-    uint32_t seed = 1591593751u;                // cuda/particles.cu:544
-    // ---- the groups
-    Mesh mesh; TetField tet; Cloud cloud; Age age; Tags tags; Routes routes; Exposure exposure; Zones zones; SinkLog sinkLog; FrameWriter frame; Timing timing;
-    // ---- what lives as long as the context
-    DevBuf<char> scratch;
-    size_t scratchBytes = 0;
-    // [kCounterSlots][4] = steps, hops, reflections, lost, sharded by block id (one hot word would
-    // serialise every block of every launch on a single L2 atomic unit), then 4 scratch words
-    DevBuf<unsigned long long> counters;
-    DevBuf<unsigned long long> recycleCounts;   // [0] absorbed, [1] drawn, [2] placed (cpf_get_recycle_counts); allocated at first use
-    DevBuf<unsigned long long> occupied;        // [0] occupied cells, [1] live particles of the last sort (device) ...
-    PinnedBuf<unsigned long long> h_occupied;   // ... and their pinned host copy (StreamState::occupiedHost)
-    Event evFieldFlag;                          // recorded behind the read-back of "the field has a z component" (cpf_set_velocity_dev)
-    bool fieldFlagPending = false;              // ... and not yet seen complete: until then the field counts as having one
-    // "a live particle's z is not finite", written by a flat launch that streams z (StreamState::zBad, pinned); evZBad is recorded
-    // behind such a launch, and while zBadPending the launch's verdict has not been read: the first launch that would leave z
-    // alone waits for it -- one wait per unsettling event, no pass over the cloud
-    PinnedBuf<unsigned> h_zBad;
-    Event evZBad;
-    bool zBadPending = false;
-    DevBuf<unsigned> grab;                      // the streaming kernel's chunk counters ...
-    DevBuf<double> hitSpill;                    // ... and the overflow area of its hit pool: StreamState views them
-    cpf::StreamState streamState;               // chunk counter + tuning of the streaming step kernel
-    uint32_t stepCounter = 0;
-    uint32_t lastSortStep = 0;
-    int64_t lastStepN = -1;                     // particle count of the most recent step launch (cpf_step_kernel_name)
-    int lastStepCycles = 1;                     // ... and its cycles per launch
-    bool lastStepZSettled = false;              // what the most recent cpf_step_dev left behind on ITS arrays (cpf_shard.cpp)
-};
+using namespace cpf::state;
+using cpf::ensureScratch; using cpf::fail; using cpf::gridView; using cpf::meshView;
 
 namespace {
 
@@ -288,28 +38,20 @@ struct WriterRegistry {
     ~WriterRegistry();
 } g_writers;
 
-int fail(const cpf_context* ctx, int code, const std::string& msg) {
-    if (ctx) ctx->err = msg;
-    else { std::lock_guard<std::mutex> lk(g_mutex); g_createError = msg; }
-    return code;
-}
-
-#define CPF_HIP(ctx, call)                                                                              \
-    do {                                                                                                \
-        hipError_t e__ = (call);                                                                        \
-        if (e__ != hipSuccess)                                                                          \
-            return fail(ctx, CPF_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__));          \
-    } while (0)
-
-#define CPF_REQUIRE(ctx, cond, code, msg) \
-    do { if (!(cond)) return fail(ctx, code, msg); } while (0)
-
 // What kind of mesh the tables describe: all-hex, and for any other mesh whose cells have records (`records`) which kinds of
 // record can turn up -- 0: none, 1: padded ones only, 2: two-record and / or header cells too (cpf_walk.h "cell records")
 bool isAllHex(const cpf::HostTables& t) { return t.minCellFaces == 6 && t.maxCellFaces == 6 && t.nGroups() == 0; }
 int mixedKind(const cpf::HostTables& t, bool records) { return (records && !isAllHex(t)) ? (t.nBigCells > 0 ? 2 : 1) : 0; }
 // a mesh that is not all-hex gets records where at most a quarter of its cells have more than TWELVE slots ("mixed_records")
 bool mixedRecordsFit(const cpf::HostTables& t) { return t.nHugeCells * 4 <= t.nCells; }
+}  // namespace
+
+namespace cpf {     // (declared in cpf_context.h)
+int fail(const cpf_context* ctx, int code, const std::string& msg) {
+    if (ctx) ctx->err = msg;
+    else { std::lock_guard<std::mutex> lk(g_mutex); g_createError = msg; }
+    return code;
+}
 
 cpf::MeshView meshView(const cpf_context* c) {
     cpf::MeshView m;
@@ -343,64 +85,18 @@ int ensureScratch(cpf_context* ctx, size_t bytes) {
     ctx->scratchBytes = bytes;
     return CPF_OK;
 }
+}  // namespace cpf
 
-// exposure off (cpf_exposure_disable; a new cloud; tagging going on or off): a pass over the tables may still be running
-int dropExposure(cpf_context* ctx) {
-    if (!ctx->exposure.on) return CPF_OK;
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->exposure = Exposure{};
+extern "C" int ensureRecycleCounts(cpf_context* ctx) {
+    if (ctx->recycleCounts) return CPF_OK;
+    DevBuf<unsigned long long> c;
+    CPF_HIP(ctx, c.alloc(4));
+    CPF_HIP(ctx, hipMemsetAsync(c, 0, 4 * 8, ctx->stream));
+    ctx->recycleCounts = std::move(c);
     return CPF_OK;
 }
 
-// zones off (cpf_zone_disable; a new cloud): a pass over the tables may still be running
-int dropZones(cpf_context* ctx) {
-    if (!ctx->zones.on) return CPF_OK;
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->zones = Zones{};
-    return CPF_OK;
-}
-
-// the sink log off (cpf_sink_log_disable; a new cloud): a pass may still be appending
-int dropSinkLog(cpf_context* ctx) {
-    if (!ctx->sinkLog.on) return CPF_OK;
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->sinkLog = SinkLog{};
-    return CPF_OK;
-}
-
-// routes off (cpf_route_disable; age or tags going off or starting anew): a pass over the tables may still be running
-int dropRoutes(cpf_context* ctx) {
-    if (!ctx->routes.on) return CPF_OK;
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->routes = Routes{};
-    return CPF_OK;
-}
-
-// age tracking off (cpf_age_disable, a new cloud): a pass over the stamps may still be running
-int dropAge(cpf_context* ctx) {
-    if (!ctx->age.on) return CPF_OK;
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->routes = Routes{};                                 // (sized by nBins)
-    ctx->age = Age{};
-    return CPF_OK;
-}
-
-// tagging off (cpf_tag_disable, a new cloud): a pass over the origins may still be running
-int dropTags(cpf_context* ctx) {
-    if (int r = dropExposure(ctx)) return r;                // (the shape of its histogram is tagging's, on or off)
-    if (!ctx->tags.on) return CPF_OK;
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->routes = Routes{};                                 // (sized by nOrigins and nSinks)
-    ctx->tags = Tags{};
-    return CPF_OK;
-}
-
+namespace {
 int sortEndBit(const cpf_context* ctx) {
     int bits = 1;
     while (((int64_t)1 << bits) < ctx->mesh.host.nCells + 2) ++bits;   // the all-ones key of lost/frozen sorts last
@@ -453,12 +149,7 @@ int setMeshImpl(cpf_context* ctx, const double* points, int64_t nPoints, const L
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->mesh = Mesh{};
     ctx->tet = TetField{};
-    ctx->age = Age{};
-    ctx->tags = Tags{};
-    ctx->routes = Routes{};
-    ctx->exposure = Exposure{};
-    ctx->zones = Zones{};
-    ctx->sinkLog = SinkLog{};
+    cpf::ledger_clear(ctx);
     ctx->streamState.flatField = false;
     ctx->mesh.host = std::move(t);
     ctx->mesh.nParent = nCells;
@@ -1005,12 +696,7 @@ int cpf_alloc_particles(cpf_context* ctx, int64_t capacity) {
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->cloud = Cloud{};
-    ctx->age = Age{};
-    ctx->tags = Tags{};
-    ctx->routes = Routes{};
-    ctx->exposure = Exposure{};
-    ctx->zones = Zones{};
-    ctx->sinkLog = SinkLog{};
+    cpf::ledger_clear(ctx);
     const size_t c = (size_t)capacity;
     CPF_HIP(ctx, ctx->cloud.cur.alloc(c));
     CPF_HIP(ctx, ctx->cloud.vel.alloc(c * 3));
@@ -1024,10 +710,7 @@ int cpf_seed_box(cpf_context* ctx, int64_t n, const double lower[3], const doubl
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, lower && upper && n > 0, CPF_ERR_ARG, "cpf_seed_box: bad arguments");
     if (ctx->cloud.cap < n) { int r = cpf_alloc_particles(ctx, n); if (r) return r; }
-    if (int r = dropAge(ctx)) return r;                     // (a new cloud: the stamps were the old one's)
-    if (int r = dropTags(ctx)) return r;                    // (... and so were the origins)
-    if (int r = dropZones(ctx)) return r;                   // (... and the last zones)
-    if (int r = dropSinkLog(ctx)) return r;                 // (... and the records)
+    if (int r = cpf::ledger_new_cloud(ctx)) return r;       // (the stamps, origins, doses, last zones and records were the old one's)
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     CPF_HIP(ctx, cpf::launch_seed_box(ctx->stream, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, 0, n, lower, upper, order));
     CPF_HIP(ctx, cpf::launch_iota64(ctx->stream, ctx->cloud.cur.gid, n, 0));
@@ -1040,13 +723,7 @@ int cpf_set_particles(cpf_context* ctx, int64_t n, const double* xyz, const int3
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, xyz && n > 0, CPF_ERR_ARG, "cpf_set_particles: bad arguments");
     if (ctx->cloud.cap < n) { int r = cpf_alloc_particles(ctx, n); if (r) return r; }
-    int r = dropAge(ctx);                                   // (a new cloud: the stamps were the old one's)
-    if (r) return r;
-    r = dropTags(ctx);                                      // (... and so were the origins)
-    if (r) return r;
-    r = dropZones(ctx);                                     // (... and the last zones)
-    if (r) return r;
-    r = dropSinkLog(ctx);                                   // (... and the records)
+    int r = cpf::ledger_new_cloud(ctx);                     // (as in cpf_seed_box)
     if (r) return r;
     CPF_HIP(ctx, hipSetDevice(ctx->device));
     ctx->cloud.zSettled = false;
@@ -1530,17 +1207,6 @@ int cpf_get_occupancy(cpf_context* ctx, uint64_t* counts, int64_t* nSamples) {
 }
 
 // ---- recycling: sink cells and a source box (cpf_recycle.hip) ---------------------------------
-namespace {
-int ensureRecycleCounts(cpf_context* ctx) {
-    if (ctx->recycleCounts) return CPF_OK;
-    DevBuf<unsigned long long> c;
-    CPF_HIP(ctx, c.alloc(4));
-    CPF_HIP(ctx, hipMemsetAsync(c, 0, 4 * 8, ctx->stream));
-    ctx->recycleCounts = std::move(c);
-    return CPF_OK;
-}
-}  // namespace
-
 int cpf_set_sink_cells(cpf_context* ctx, const int32_t* parentCells, int64_t n) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_set_sink_cells: call cpf_set_mesh first");
@@ -1586,75 +1252,10 @@ int cpf_sink_apply(cpf_context* ctx) {
     CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
     CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_sink_apply: call cpf_set_mesh first");
     CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_sink_apply: no located particles");
-    if (ctx->sinkLog.on && ctx->mesh.sinkMask) {
-        // the sink log: a read-only pass of its own appends one record for everybody the sink is about to absorb, made of what the
-        // cloud and the tables of the groups that are on hold now, before anyone is marked (cpf_sinklog.hip); then everything
-        // below, as without it
-        SinkLog& lg = ctx->sinkLog;
-        cpf::SinkLogView v{};
-        v.x = ctx->cloud.cur.x; v.y = ctx->cloud.cur.y; v.z = ctx->cloud.cur.z; v.cell = ctx->cloud.cur.cell; v.gid = ctx->cloud.cur.gid;
-        v.birth = ctx->age.on ? ctx->age.birth.get() : nullptr;
-        v.origin = ctx->tags.on ? ctx->tags.origin.get() : nullptr;
-        v.sinkGroup = ctx->tags.on ? ctx->tags.sinkGroup.get() : nullptr;
-        v.dose = ctx->exposure.on ? ctx->exposure.dose.get() : nullptr;
-        v.last = ctx->zones.on ? ctx->zones.last.get() : nullptr;
-        v.parentOf = ctx->mesh.parentOf.get();
-        v.mask = ctx->mesh.sinkMask; v.cursor = lg.cursor; v.rec = lg.rec;
-        v.n = ctx->cloud.n; v.capacity = lg.capacity;
-        v.now = ctx->stepCounter; v.apply = lg.apply;
-        v.fields = (ctx->age.on ? CPF_SINK_LOG_AGE : 0u) | (ctx->tags.on ? CPF_SINK_LOG_TAGS : 0u) |
-                   (ctx->exposure.on ? CPF_SINK_LOG_EXPOSURE : 0u) | (ctx->zones.on ? CPF_SINK_LOG_ZONES : 0u);
-        CPF_HIP(ctx, hipSetDevice(ctx->device));
-        CPF_HIP(ctx, cpf::sink_log(ctx->stream, v, ctx->mesh.host.nCells));
-        ++lg.apply;
-    }
-    if (ctx->exposure.on && ctx->mesh.sinkMask) {
-        // exposure: a read-only pass of its own bins the dose of everybody the sink is about to absorb, before anyone is marked
-        // (cpf_exposure.hip); then whichever of the three paths below applies, as without it
-        const Exposure& e = ctx->exposure;
-        CPF_HIP(ctx, hipSetDevice(ctx->device));
-        CPF_HIP(ctx, cpf::exposure_absorb(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, e.dose, e.tagged ? ctx->tags.origin.get() : nullptr,
-                                          ctx->cloud.n, ctx->mesh.sinkMask, ctx->mesh.host.nCells,
-                                          e.tagged ? ctx->tags.sinkGroup.get() : nullptr, e.invWidth, e.nBins, e.nOrigins, e.nSinks, e.hist));
-    }
-    if (ctx->zones.on && ctx->mesh.sinkMask) {
-        // zones: a read-only pass of its own counts, by the zone of their last sample, everybody the sink is about to absorb as
-        // leaving for "outside", before anyone is marked (cpf_zones.hip); then whichever of the three paths below applies
-        const Zones& zn = ctx->zones;
-        CPF_HIP(ctx, hipSetDevice(ctx->device));
-        CPF_HIP(ctx, cpf::zone_leave(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, zn.last, ctx->cloud.n, ctx->mesh.sinkMask,
-                                     ctx->mesh.host.nCells, zn.nZones, zn.flow));
-    }
-    if (ctx->routes.on) {
-        // routes (so tags and age are on): ONE pass in place of the two below, which adds what they add and the joint histogram
-        // besides (cpf_routes.hip)
-        if (!ctx->mesh.sinkMask) return CPF_OK;
-        CPF_HIP(ctx, hipSetDevice(ctx->device));
-        int r = ensureRecycleCounts(ctx);
-        if (r) return r;
-        CPF_HIP(ctx, cpf::route_absorb(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->age.birth, ctx->tags.origin, ctx->cloud.n,
-                                       ctx->mesh.sinkMask, ctx->mesh.host.nCells, ctx->tags.sinkGroup, ctx->recycleCounts,
-                                       ctx->stepCounter, ctx->age.binCycles, ctx->age.nBins, ctx->tags.nOrigins, ctx->tags.nSinks,
-                                       ctx->age.hist, ctx->tags.transfer, ctx->routes.hist));
-        return CPF_OK;
-    }
-    if (ctx->tags.on && ctx->mesh.sinkMask) {
-        // tagging: a read-only pass of its own counts (origin, sink group) of everybody the sink is about to absorb (cpf_tags.hip)
-        CPF_HIP(ctx, hipSetDevice(ctx->device));
-        CPF_HIP(ctx, cpf::tag_transfer(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->tags.origin, ctx->cloud.n,
-                                       ctx->mesh.sinkMask, ctx->mesh.host.nCells, ctx->tags.sinkGroup, ctx->tags.nOrigins,
-                                       ctx->tags.nSinks, ctx->tags.transfer));
-    }
-    if (!ctx->age.on) return cpf_sink_apply_dev(ctx, ctx->cloud.cur.cell, ctx->cloud.n);
-    // age tracking: the same pass, which also bins the age of every particle it absorbs (cpf_age.hip)
-    if (!ctx->mesh.sinkMask) return CPF_OK;
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    int r = ensureRecycleCounts(ctx);
-    if (r) return r;
-    CPF_HIP(ctx, cpf::age_absorb(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->age.birth, ctx->cloud.n, ctx->mesh.sinkMask,
-                                 ctx->mesh.host.nCells, ctx->recycleCounts, ctx->stepCounter, ctx->age.binCycles, ctx->age.nBins,
-                                 ctx->age.hist));
-    return CPF_OK;
+    // the groups of the ledger that are on run their passes first; age's and route's mark and count as the plain pass does
+    bool marked = false;
+    if (int r = cpf::ledger_sink_passes(ctx, &marked)) return r;
+    return marked ? CPF_OK : cpf_sink_apply_dev(ctx, ctx->cloud.cur.cell, ctx->cloud.n);
 }
 
 int cpf_respawn_box_dev(cpf_context* ctx, double* x, double* y, double* z, int32_t* cell, const int64_t* gid, int64_t n,
@@ -1685,28 +1286,9 @@ int cpf_respawn_box(cpf_context* ctx, const double lower[3], const double upper[
     CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_respawn_box: no located particles");
     bool boxOk = lower && upper;                    // (a box the respawn is about to refuse: no stamp either)
     for (int k = 0; k < 3 && boxOk; ++k) boxOk = std::isfinite(lower[k]) && std::isfinite(upper[k]) && upper[k] >= lower[k];
-    if (ctx->age.on && boxOk && maxCount != 0) {
-        // age tracking: every candidate is born now -- the ones this call leaves dead have no age, and are stamped again by the
-        // call that places them
-        CPF_HIP(ctx, hipSetDevice(ctx->device));
-        CPF_HIP(ctx, cpf::age_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->age.birth, ctx->cloud.n, ctx->stepCounter));
-    }
-    if (ctx->tags.on && boxOk && maxCount != 0) {
-        // tagging: every candidate gets the box's origin, under the conditions of age's stamp
-        CPF_HIP(ctx, hipSetDevice(ctx->device));
-        CPF_HIP(ctx, cpf::tag_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->tags.origin, ctx->cloud.n, nullptr, 0,
-                                    nullptr, ctx->seed, ctx->cloud.respawnEpoch, ctx->tags.boxOrigin));
-    }
-    if (ctx->exposure.on && boxOk && maxCount != 0) {
-        // exposure: every candidate starts from dose +0.0, under the conditions of age's stamp
-        CPF_HIP(ctx, hipSetDevice(ctx->device));
-        CPF_HIP(ctx, cpf::exposure_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->exposure.dose, ctx->cloud.n));
-    }
-    if (ctx->zones.on && boxOk && maxCount != 0) {
-        // zones: every candidate is outside until its next sample, under the conditions of age's stamp
-        CPF_HIP(ctx, hipSetDevice(ctx->device));
-        CPF_HIP(ctx, cpf::zone_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->zones.last, ctx->cloud.n));
-    }
+    // the ledger: every candidate is stamped now -- the ones this call leaves dead are stamped again by the call that places them
+    if (boxOk && maxCount != 0)
+        if (int r = cpf::ledger_respawn_stamps(ctx, false)) return r;
     int r = cpf_respawn_box_dev(ctx, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell, ctx->cloud.cur.gid,
                                 ctx->cloud.n, lower, upper, maxCount, ctx->cloud.respawnEpoch);
     if (r) return r;
@@ -1899,692 +1481,13 @@ int cpf_respawn_source(cpf_context* ctx, int64_t maxCount) {
     CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_respawn_source: call cpf_set_mesh first");
     CPF_REQUIRE(ctx, ctx->mesh.sourceKept > 0, CPF_ERR_STATE, "cpf_respawn_source: call cpf_set_source_triangles first");
     CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_respawn_source: no located particles");
-    if (ctx->age.on && maxCount != 0) {
-        // age tracking: every candidate is born now, as in cpf_respawn_box
-        CPF_HIP(ctx, hipSetDevice(ctx->device));
-        CPF_HIP(ctx, cpf::age_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->age.birth, ctx->cloud.n, ctx->stepCounter));
-    }
-    if (ctx->tags.on && maxCount != 0) {
-        // tagging: every candidate gets the origin of the triangle this call's epoch picks for its id (cpf_tags.hip)
-        CPF_HIP(ctx, hipSetDevice(ctx->device));
-        CPF_HIP(ctx, cpf::tag_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->tags.origin, ctx->cloud.n,
-                                    ctx->mesh.sourceHi, (int32_t)ctx->mesh.sourceKept, ctx->tags.originOfKept, ctx->seed,
-                                    ctx->cloud.respawnEpoch, 0));
-    }
-    if (ctx->exposure.on && maxCount != 0) {
-        // exposure: every candidate starts from dose +0.0, as in cpf_respawn_box
-        CPF_HIP(ctx, hipSetDevice(ctx->device));
-        CPF_HIP(ctx, cpf::exposure_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->exposure.dose, ctx->cloud.n));
-    }
-    if (ctx->zones.on && maxCount != 0) {
-        // zones: every candidate is outside until its next sample, as in cpf_respawn_box
-        CPF_HIP(ctx, hipSetDevice(ctx->device));
-        CPF_HIP(ctx, cpf::zone_stamp(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->zones.last, ctx->cloud.n));
-    }
+    if (maxCount != 0)                              // (the ledger's stamps, as in cpf_respawn_box)
+        if (int r = cpf::ledger_respawn_stamps(ctx, true)) return r;
     int r = cpf_respawn_source_dev(ctx, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell, ctx->cloud.cur.gid,
                                    ctx->cloud.n, maxCount, ctx->cloud.respawnEpoch);
     if (r) return r;
     ctx->cloud.zSettled = false;                    // (as behind cpf_respawn_box)
     ++ctx->cloud.respawnEpoch;
-    return CPF_OK;
-}
-
-// ---- tracer age: birth stamps by particle id, residence times at the sink, the mean-age field (cpf_age.hip) ----------------
-int cpf_age_enable(cpf_context* ctx, int32_t binCycles, int32_t nBins) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_age_enable: call cpf_set_mesh first");
-    CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_age_enable: no located particles");
-    CPF_REQUIRE(ctx, binCycles >= 1 && nBins >= 1 && nBins <= 4096, CPF_ERR_ARG, "cpf_age_enable: binCycles >= 1 and 1 <= nBins <= 4096");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass over the old tables may still be running)
-    ctx->age = Age{};
-    ctx->routes = Routes{};                                 // (nBins may change)
-    Age a;                                                  // moved in whole: a failure part-way leaves tracking off
-    const size_t n = (size_t)ctx->cloud.n, nField = (size_t)ctx->mesh.nParent * 2;
-    CPF_HIP(ctx, a.birth.alloc(n));
-    CPF_HIP(ctx, a.hist.alloc((size_t)nBins));
-    CPF_HIP(ctx, a.field.alloc(nField));
-    CPF_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.birth.get()), (int)ctx->stepCounter, n, ctx->stream));
-    CPF_HIP(ctx, hipMemsetAsync(a.hist, 0, (size_t)nBins * 8, ctx->stream));
-    CPF_HIP(ctx, hipMemsetAsync(a.field, 0, nField * 8, ctx->stream));
-    a.on = true; a.binCycles = binCycles; a.nBins = nBins;
-    ctx->age = std::move(a);
-    return CPF_OK;
-}
-
-int cpf_age_disable(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    return dropAge(ctx);
-}
-
-int cpf_age_sample(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->age.on, CPF_ERR_STATE, "cpf_age_sample: call cpf_age_enable first");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, cpf::age_field(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->age.birth, ctx->cloud.n, ctx->mesh.parentOf,
-                                ctx->mesh.host.nCells, ctx->stepCounter, ctx->age.field));
-    ++ctx->age.samples;
-    return CPF_OK;
-}
-
-int cpf_age_reset(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->age.on, CPF_ERR_STATE, "cpf_age_reset: call cpf_age_enable first");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemsetAsync(ctx->age.hist, 0, (size_t)ctx->age.nBins * 8, ctx->stream));
-    CPF_HIP(ctx, hipMemsetAsync(ctx->age.field, 0, (size_t)ctx->mesh.nParent * 16, ctx->stream));
-    ctx->age.samples = 0;
-    return CPF_OK;
-}
-
-int cpf_get_age_histogram(cpf_context* ctx, uint64_t* bins, int32_t nBins) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->age.on, CPF_ERR_STATE, "cpf_get_age_histogram: call cpf_age_enable first");
-    CPF_REQUIRE(ctx, bins && nBins == ctx->age.nBins, CPF_ERR_ARG, "cpf_get_age_histogram: nBins is not cpf_age_enable's");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(bins, ctx->age.hist, (size_t)nBins * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPF_OK;
-}
-
-int cpf_get_age_field(cpf_context* ctx, uint64_t* ageSum, uint64_t* count, int64_t* nSamples) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->age.on, CPF_ERR_STATE, "cpf_get_age_field: call cpf_age_enable first");
-    if (nSamples) *nSamples = ctx->age.samples;
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t nc = (size_t)ctx->mesh.nParent;
-    std::vector<unsigned long long> h(nc * 2);
-    if (ageSum || count) CPF_HIP(ctx, hipMemcpyAsync(h.data(), ctx->age.field, nc * 16, hipMemcpyDeviceToHost, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (size_t c = 0; c < nc; ++c) {
-        if (ageSum) ageSum[c] = h[2 * c];
-        if (count) count[c] = h[2 * c + 1];
-    }
-    return CPF_OK;
-}
-
-int cpf_age_get_births(cpf_context* ctx, uint32_t* birth) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->age.on, CPF_ERR_STATE, "cpf_age_get_births: call cpf_age_enable first");
-    CPF_REQUIRE(ctx, birth, CPF_ERR_ARG, "cpf_age_get_births: null array");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(birth, ctx->age.birth, (size_t)ctx->cloud.n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPF_OK;
-}
-
-int cpf_age_set_births(cpf_context* ctx, const uint32_t* birth) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->age.on, CPF_ERR_STATE, "cpf_age_set_births: call cpf_age_enable first");
-    CPF_REQUIRE(ctx, birth, CPF_ERR_ARG, "cpf_age_set_births: null array");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(ctx->age.birth, birth, (size_t)ctx->cloud.n * 4, hipMemcpyHostToDevice, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPF_OK;
-}
-
-int cpf_get_ages(cpf_context* ctx, int64_t* age) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->age.on, CPF_ERR_STATE, "cpf_get_ages: call cpf_age_enable first");
-    CPF_REQUIRE(ctx, age, CPF_ERR_ARG, "cpf_get_ages: null array");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    // a read-back for checks and restarts, not a hot path: the cells in id order (cpf_get_particles' pass), the rest on the host
-    const size_t n = (size_t)ctx->cloud.n;
-    int r = ensureScratch(ctx, n * 4);
-    if (r) return r;
-    int32_t* dC = (int32_t*)ctx->scratch.get();
-    CPF_HIP(ctx, cpf::launch_pack_by_gid(ctx->stream, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell,
-                                         ctx->cloud.cur.gid, nullptr, nullptr, dC, nullptr, ctx->cloud.n));
-    std::vector<int32_t> cell(n);
-    std::vector<uint32_t> birth(n);
-    CPF_HIP(ctx, hipMemcpyAsync(cell.data(), dC, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    CPF_HIP(ctx, hipMemcpyAsync(birth.data(), ctx->age.birth, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const uint32_t now = ctx->stepCounter;
-    for (size_t i = 0; i < n; ++i) age[i] = cell[i] >= 0 ? (int64_t)(uint32_t)(now - birth[i]) : -1;
-    return CPF_OK;
-}
-
-// ---- tracer tags: an origin per particle id, grouped sinks, the transfer matrix, the per-origin field (cpf_tags.hip) -------
-int cpf_tag_enable(cpf_context* ctx, int32_t nOrigins, int32_t nSinks) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_tag_enable: call cpf_set_mesh first");
-    CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_tag_enable: no located particles");
-    CPF_REQUIRE(ctx, nOrigins >= 1 && nOrigins <= kTagMax && nSinks >= 1 && nSinks <= kTagMax, CPF_ERR_ARG,
-                "cpf_tag_enable: 1 <= nOrigins <= 16 and 1 <= nSinks <= 16");
-    CPF_REQUIRE(ctx, ctx->mesh.nParent * (int64_t)nOrigins < ((int64_t)1 << 31), CPF_ERR_ARG,
-                "cpf_tag_enable: nCells * nOrigins must stay below 2^31");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass over the old tables may still be running)
-    ctx->tags = Tags{};
-    ctx->routes = Routes{};                                 // (nOrigins and nSinks may change)
-    ctx->exposure = Exposure{};                             // (... and its histogram is shaped by them)
-    Tags t;                                                 // moved in whole: a failure part-way leaves tagging off
-    const size_t n = (size_t)ctx->cloud.n, nDerived = (size_t)ctx->mesh.host.nCells, nField = (size_t)ctx->mesh.nParent * nOrigins;
-    CPF_HIP(ctx, t.origin.alloc(n));
-    CPF_HIP(ctx, t.sinkGroup.alloc(nDerived));
-    CPF_HIP(ctx, t.transfer.alloc((size_t)kTagMax * kTagMax));
-    CPF_HIP(ctx, t.field.alloc(nField));
-    CPF_HIP(ctx, hipMemsetAsync(t.origin, 0, n, ctx->stream));
-    CPF_HIP(ctx, hipMemsetAsync(t.sinkGroup, 0, nDerived, ctx->stream));
-    CPF_HIP(ctx, hipMemsetAsync(t.transfer, 0, (size_t)kTagMax * kTagMax * 8, ctx->stream));
-    CPF_HIP(ctx, hipMemsetAsync(t.field, 0, nField * 8, ctx->stream));
-    if (ctx->mesh.sourceKept > 0) {
-        CPF_HIP(ctx, t.originOfKept.alloc((size_t)ctx->mesh.sourceKept));
-        CPF_HIP(ctx, hipMemsetAsync(t.originOfKept, 0, (size_t)ctx->mesh.sourceKept, ctx->stream));
-    }
-    t.on = true; t.nOrigins = nOrigins; t.nSinks = nSinks;
-    ctx->tags = std::move(t);
-    return CPF_OK;
-}
-
-int cpf_tag_disable(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    return dropTags(ctx);
-}
-
-int cpf_set_sink_groups(cpf_context* ctx, const int32_t* parentCells, const int32_t* group, int64_t n) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_set_sink_groups: call cpf_tag_enable first");
-    CPF_REQUIRE(ctx, n >= 0 && ((parentCells && group) || n == 0), CPF_ERR_ARG, "cpf_set_sink_groups: bad arguments");
-    for (int64_t k = 0; k < n; ++k) {
-        CPF_REQUIRE(ctx, parentCells[k] >= 0 && parentCells[k] < ctx->mesh.nParent, CPF_ERR_ARG,
-                    "cpf_set_sink_groups: cell " + std::to_string(parentCells[k]) + " is not in [0, nCells)");
-        CPF_REQUIRE(ctx, group[k] >= 0 && group[k] < ctx->tags.nSinks, CPF_ERR_ARG,
-                    "cpf_set_sink_groups: group " + std::to_string(group[k]) + " is not in [0, nSinks)");
-    }
-    int r = cpf_set_sink_cells(ctx, parentCells, n);        // (the mask; it waits for the stream and puts everybody in group 0)
-    if (r || n == 0) return r;
-    std::vector<uint8_t> g((size_t)ctx->mesh.host.nCells, (uint8_t)0);
-    const bool derived = !ctx->mesh.first.empty();
-    for (int64_t k = 0; k < n; ++k) {
-        const int64_t c = parentCells[k];
-        const int64_t lo = derived ? ctx->mesh.first[(size_t)c] : c, hi = derived ? ctx->mesh.first[(size_t)c + 1] : c + 1;
-        for (int64_t d = lo; d < hi; ++d) g[(size_t)d] = (uint8_t)group[k];
-    }
-    CPF_HIP(ctx, hipMemcpy(ctx->tags.sinkGroup, g.data(), g.size(), hipMemcpyHostToDevice));
-    return CPF_OK;
-}
-
-int cpf_set_source_origins(cpf_context* ctx, const int32_t* originOfTriangle, int64_t nTriangles) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_set_source_origins: call cpf_tag_enable first");
-    CPF_REQUIRE(ctx, ctx->mesh.sourceKept > 0, CPF_ERR_STATE, "cpf_set_source_origins: call cpf_set_source_triangles first");
-    CPF_REQUIRE(ctx, originOfTriangle && nTriangles > 0, CPF_ERR_ARG, "cpf_set_source_origins: bad arguments");
-    for (int64_t t = 0; t < nTriangles; ++t)
-        CPF_REQUIRE(ctx, originOfTriangle[t] >= 0 && originOfTriangle[t] < ctx->tags.nOrigins, CPF_ERR_ARG,
-                    "cpf_set_source_origins: origin " + std::to_string(originOfTriangle[t]) + " is not in [0, nOrigins)");
-    // a kept record carries the index of the CALLER's triangle (dropped ones have no record)
-    std::vector<uint8_t> o((size_t)ctx->mesh.sourceKept);
-    for (size_t k = 0; k < o.size(); ++k) {
-        const int64_t t = (int64_t)ctx->mesh.sourceRecHost[k * cpf::kSourceDoubles + 14];
-        CPF_REQUIRE(ctx, t >= 0 && t < nTriangles, CPF_ERR_ARG,
-                    "cpf_set_source_origins: the source has a triangle " + std::to_string(t) + ", beyond nTriangles");
-        o[k] = (uint8_t)originOfTriangle[t];
-    }
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a stamp over the old origins may still be running)
-    CPF_HIP(ctx, hipMemcpy(ctx->tags.originOfKept, o.data(), o.size(), hipMemcpyHostToDevice));
-    return CPF_OK;
-}
-
-int cpf_set_box_origin(cpf_context* ctx, int32_t origin) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_set_box_origin: call cpf_tag_enable first");
-    CPF_REQUIRE(ctx, origin >= 0 && origin < ctx->tags.nOrigins, CPF_ERR_ARG,
-                "cpf_set_box_origin: origin " + std::to_string(origin) + " is not in [0, nOrigins)");
-    ctx->tags.boxOrigin = origin;
-    return CPF_OK;
-}
-
-int cpf_tag_sample(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_tag_sample: call cpf_tag_enable first");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, cpf::tag_field(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->tags.origin, ctx->cloud.n, ctx->mesh.parentOf,
-                                ctx->mesh.host.nCells, ctx->mesh.nParent, ctx->tags.nOrigins, ctx->tags.field));
-    ++ctx->tags.samples;
-    return CPF_OK;
-}
-
-int cpf_tag_reset(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_tag_reset: call cpf_tag_enable first");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemsetAsync(ctx->tags.transfer, 0, (size_t)kTagMax * kTagMax * 8, ctx->stream));
-    CPF_HIP(ctx, hipMemsetAsync(ctx->tags.field, 0, (size_t)ctx->mesh.nParent * ctx->tags.nOrigins * 8, ctx->stream));
-    ctx->tags.samples = 0;
-    return CPF_OK;
-}
-
-int cpf_get_transfer(cpf_context* ctx, uint64_t* T) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_get_transfer: call cpf_tag_enable first");
-    CPF_REQUIRE(ctx, T, CPF_ERR_ARG, "cpf_get_transfer: null array");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(T, ctx->tags.transfer, (size_t)ctx->tags.nOrigins * ctx->tags.nSinks * 8, hipMemcpyDeviceToHost,
-                                ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPF_OK;
-}
-
-int cpf_get_tag_field(cpf_context* ctx, uint64_t* counts, int64_t* nSamples) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_get_tag_field: call cpf_tag_enable first");
-    if (nSamples) *nSamples = ctx->tags.samples;
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    if (counts)
-        CPF_HIP(ctx, hipMemcpyAsync(counts, ctx->tags.field, (size_t)ctx->mesh.nParent * ctx->tags.nOrigins * 8, hipMemcpyDeviceToHost,
-                                    ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPF_OK;
-}
-
-int cpf_tag_get_origins(cpf_context* ctx, uint8_t* origin) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_tag_get_origins: call cpf_tag_enable first");
-    CPF_REQUIRE(ctx, origin, CPF_ERR_ARG, "cpf_tag_get_origins: null array");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(origin, ctx->tags.origin, (size_t)ctx->cloud.n, hipMemcpyDeviceToHost, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPF_OK;
-}
-
-int cpf_tag_set_origins(cpf_context* ctx, const uint8_t* origin) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->tags.on, CPF_ERR_STATE, "cpf_tag_set_origins: call cpf_tag_enable first");
-    CPF_REQUIRE(ctx, origin, CPF_ERR_ARG, "cpf_tag_set_origins: null array");
-    for (int64_t i = 0; i < ctx->cloud.n; ++i)
-        CPF_REQUIRE(ctx, (int32_t)origin[i] < ctx->tags.nOrigins, CPF_ERR_ARG,
-                    "cpf_tag_set_origins: origin " + std::to_string((int)origin[i]) + " is not in [0, nOrigins)");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(ctx->tags.origin, origin, (size_t)ctx->cloud.n, hipMemcpyHostToDevice, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPF_OK;
-}
-
-// ---- routes: the residence-time histogram per (origin, sink group), the age field per origin (cpf_routes.hip) ---------------
-int cpf_route_enable(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->age.on && ctx->tags.on, CPF_ERR_STATE, "cpf_route_enable: call cpf_age_enable and cpf_tag_enable first");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass over the old tables may still be running)
-    ctx->routes = Routes{};
-    Routes t;                                               // moved in whole: a failure part-way leaves routes off
-    const size_t nHist = (size_t)ctx->tags.nOrigins * ctx->tags.nSinks * ctx->age.nBins,
-                 nField = (size_t)ctx->mesh.nParent * ctx->tags.nOrigins * 2;
-    CPF_HIP(ctx, t.hist.alloc(nHist));
-    CPF_HIP(ctx, t.field.alloc(nField));
-    CPF_HIP(ctx, hipMemsetAsync(t.hist, 0, nHist * 8, ctx->stream));
-    CPF_HIP(ctx, hipMemsetAsync(t.field, 0, nField * 8, ctx->stream));
-    t.on = true;
-    ctx->routes = std::move(t);
-    return CPF_OK;
-}
-
-int cpf_route_disable(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    return dropRoutes(ctx);
-}
-
-int cpf_route_sample(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->routes.on, CPF_ERR_STATE, "cpf_route_sample: call cpf_route_enable first");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, cpf::route_field(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->age.birth, ctx->tags.origin, ctx->cloud.n,
-                                  ctx->mesh.parentOf, ctx->mesh.host.nCells, ctx->mesh.nParent, ctx->tags.nOrigins, ctx->stepCounter,
-                                  ctx->routes.field));
-    ++ctx->routes.samples;
-    return CPF_OK;
-}
-
-int cpf_route_reset(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->routes.on, CPF_ERR_STATE, "cpf_route_reset: call cpf_route_enable first");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemsetAsync(ctx->routes.hist, 0, (size_t)ctx->tags.nOrigins * ctx->tags.nSinks * ctx->age.nBins * 8, ctx->stream));
-    CPF_HIP(ctx, hipMemsetAsync(ctx->routes.field, 0, (size_t)ctx->mesh.nParent * ctx->tags.nOrigins * 16, ctx->stream));
-    ctx->routes.samples = 0;
-    return CPF_OK;
-}
-
-int cpf_get_route_histogram(cpf_context* ctx, uint64_t* bins) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->routes.on, CPF_ERR_STATE, "cpf_get_route_histogram: call cpf_route_enable first");
-    CPF_REQUIRE(ctx, bins, CPF_ERR_ARG, "cpf_get_route_histogram: null array");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(bins, ctx->routes.hist, (size_t)ctx->tags.nOrigins * ctx->tags.nSinks * ctx->age.nBins * 8,
-                                hipMemcpyDeviceToHost, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPF_OK;
-}
-
-int cpf_get_route_field(cpf_context* ctx, uint64_t* ageSum, uint64_t* count, int64_t* nSamples) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->routes.on, CPF_ERR_STATE, "cpf_get_route_field: call cpf_route_enable first");
-    if (nSamples) *nSamples = ctx->routes.samples;
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t nv = (size_t)ctx->mesh.nParent * ctx->tags.nOrigins;
-    std::vector<unsigned long long> h(nv * 2);
-    if (ageSum || count) CPF_HIP(ctx, hipMemcpyAsync(h.data(), ctx->routes.field, nv * 16, hipMemcpyDeviceToHost, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (size_t c = 0; c < nv; ++c) {
-        if (ageSum) ageSum[c] = h[2 * c];
-        if (count) count[c] = h[2 * c + 1];
-    }
-    return CPF_OK;
-}
-
-// ---- exposure: a dose per particle id summed along the path, the dose histogram at the sink (cpf_exposure.hip) -------------
-int cpf_exposure_enable(cpf_context* ctx, double binWidth, int32_t nBins) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_exposure_enable: call cpf_set_mesh first");
-    CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_exposure_enable: no located particles");
-    CPF_REQUIRE(ctx, std::isfinite(binWidth) && binWidth > 0.0, CPF_ERR_ARG, "cpf_exposure_enable: binWidth must be finite and > 0");
-    const int32_t nOrigins = ctx->tags.on ? ctx->tags.nOrigins : 1, nSinks = ctx->tags.on ? ctx->tags.nSinks : 1;
-    CPF_REQUIRE(ctx, nBins >= 1 && (int64_t)nOrigins * nSinks * nBins <= kExposureWords, CPF_ERR_ARG,
-                "cpf_exposure_enable: nOrigins * nSinks * nBins must be in [1, 4096]");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass over the old tables may still be running)
-    ctx->exposure = Exposure{};
-    Exposure e;                                             // moved in whole: a failure part-way leaves exposure off
-    const size_t n = (size_t)ctx->cloud.n, nDerived = (size_t)ctx->mesh.host.nCells, nHist = (size_t)nOrigins * nSinks * nBins;
-    CPF_HIP(ctx, e.dose.alloc(n));
-    CPF_HIP(ctx, e.rate.alloc(nDerived));
-    CPF_HIP(ctx, e.hist.alloc(nHist));
-    CPF_HIP(ctx, hipMemsetAsync(e.dose, 0, n * 8, ctx->stream));            // (+0.0)
-    CPF_HIP(ctx, hipMemsetAsync(e.rate, 0, nDerived * 8, ctx->stream));
-    CPF_HIP(ctx, hipMemsetAsync(e.hist, 0, nHist * 8, ctx->stream));
-    e.on = true; e.binWidth = binWidth; e.invWidth = 1.0 / binWidth; e.nBins = nBins;
-    e.nOrigins = nOrigins; e.nSinks = nSinks; e.tagged = ctx->tags.on;
-    ctx->exposure = std::move(e);
-    return CPF_OK;
-}
-
-int cpf_exposure_disable(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    return dropExposure(ctx);
-}
-
-int cpf_set_exposure_field(cpf_context* ctx, const double* rate, int64_t nCells) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->exposure.on, CPF_ERR_STATE, "cpf_set_exposure_field: call cpf_exposure_enable first");
-    CPF_REQUIRE(ctx, rate && nCells == ctx->mesh.nParent, CPF_ERR_ARG, "cpf_set_exposure_field: one value per cell of the mesh as given");
-    for (int64_t c = 0; c < nCells; ++c)
-        CPF_REQUIRE(ctx, std::isfinite(rate[c]) && rate[c] >= 0.0, CPF_ERR_ARG,
-                    "cpf_set_exposure_field: the rate of cell " + std::to_string(c) + " is not finite and >= 0");
-    // one value per DERIVED cell: every derived cell of a parent gets the parent's
-    const int64_t nDerived = ctx->mesh.host.nCells;
-    const double* src = rate;
-    std::vector<double> expanded;
-    if (!ctx->mesh.first.empty()) {
-        expanded.resize((size_t)nDerived);
-        for (int64_t c = 0; c < nCells; ++c)
-            for (int64_t d = ctx->mesh.first[(size_t)c]; d < ctx->mesh.first[(size_t)c + 1]; ++d) expanded[(size_t)d] = rate[c];
-        src = expanded.data();
-    }
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(ctx->exposure.rate, src, (size_t)nDerived * 8, hipMemcpyHostToDevice, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (the copy reads the caller's array, or `expanded`)
-    return CPF_OK;
-}
-
-int cpf_exposure_accumulate(cpf_context* ctx, double scale) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->exposure.on, CPF_ERR_STATE, "cpf_exposure_accumulate: call cpf_exposure_enable first");
-    CPF_REQUIRE(ctx, std::isfinite(scale) && scale >= 0.0, CPF_ERR_ARG, "cpf_exposure_accumulate: scale must be finite and >= 0");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, cpf::exposure_accumulate(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, ctx->exposure.rate, ctx->exposure.dose,
-                                          ctx->cloud.n, ctx->mesh.host.nCells, scale));
-    return CPF_OK;
-}
-
-int cpf_exposure_reset(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->exposure.on, CPF_ERR_STATE, "cpf_exposure_reset: call cpf_exposure_enable first");
-    const Exposure& e = ctx->exposure;
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemsetAsync(e.hist, 0, (size_t)e.nOrigins * e.nSinks * e.nBins * 8, ctx->stream));
-    return CPF_OK;
-}
-
-int cpf_get_dose_histogram(cpf_context* ctx, uint64_t* bins) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->exposure.on, CPF_ERR_STATE, "cpf_get_dose_histogram: call cpf_exposure_enable first");
-    CPF_REQUIRE(ctx, bins, CPF_ERR_ARG, "cpf_get_dose_histogram: null array");
-    const Exposure& e = ctx->exposure;
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(bins, e.hist, (size_t)e.nOrigins * e.nSinks * e.nBins * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPF_OK;
-}
-
-int cpf_exposure_get_doses(cpf_context* ctx, double* dose) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->exposure.on, CPF_ERR_STATE, "cpf_exposure_get_doses: call cpf_exposure_enable first");
-    CPF_REQUIRE(ctx, dose, CPF_ERR_ARG, "cpf_exposure_get_doses: null array");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(dose, ctx->exposure.dose, (size_t)ctx->cloud.n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPF_OK;
-}
-
-int cpf_exposure_set_doses(cpf_context* ctx, const double* dose) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->exposure.on, CPF_ERR_STATE, "cpf_exposure_set_doses: call cpf_exposure_enable first");
-    CPF_REQUIRE(ctx, dose, CPF_ERR_ARG, "cpf_exposure_set_doses: null array");
-    for (int64_t i = 0; i < ctx->cloud.n; ++i)              // (what the accumulate rule can produce: no NaN, nothing negative, no -0.0)
-        CPF_REQUIRE(ctx, dose[i] >= 0.0 && !std::signbit(dose[i]), CPF_ERR_ARG,
-                    "cpf_exposure_set_doses: the dose of particle " + std::to_string(i) + " is negative or not a number");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(ctx->exposure.dose, dose, (size_t)ctx->cloud.n * 8, hipMemcpyHostToDevice, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPF_OK;
-}
-
-int cpf_get_doses(cpf_context* ctx, double* dose) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->exposure.on, CPF_ERR_STATE, "cpf_get_doses: call cpf_exposure_enable first");
-    CPF_REQUIRE(ctx, dose, CPF_ERR_ARG, "cpf_get_doses: null array");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    // a read-back for checks and restarts, not a hot path: the cells in id order (cpf_get_ages' pass), the rest on the host
-    const size_t n = (size_t)ctx->cloud.n;
-    int r = ensureScratch(ctx, n * 4);
-    if (r) return r;
-    int32_t* dC = (int32_t*)ctx->scratch.get();
-    CPF_HIP(ctx, cpf::launch_pack_by_gid(ctx->stream, ctx->cloud.cur.x, ctx->cloud.cur.y, ctx->cloud.cur.z, ctx->cloud.cur.cell,
-                                         ctx->cloud.cur.gid, nullptr, nullptr, dC, nullptr, ctx->cloud.n));
-    std::vector<int32_t> cell(n);
-    CPF_HIP(ctx, hipMemcpyAsync(cell.data(), dC, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    CPF_HIP(ctx, hipMemcpyAsync(dose, ctx->exposure.dose, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (size_t i = 0; i < n; ++i)
-        if (cell[i] < 0) dose[i] = -1.0;
-    return CPF_OK;
-}
-
-int cpf_exposure_bins_host(const double* dose, int64_t n, double binWidth, int32_t nBins, int32_t* bin) {
-    if (n < 0 || !std::isfinite(binWidth) || !(binWidth > 0.0) || nBins < 1 || (n > 0 && (!dose || !bin))) return CPF_ERR_ARG;
-    const double invWidth = 1.0 / binWidth;
-    for (int64_t i = 0; i < n; ++i) bin[i] = cpf::exposure_bin(dose[i], invWidth, nBins);
-    return CPF_OK;
-}
-
-// ---- the sink log: one record per absorbed particle, appended on the device (cpf_sinklog.hip) ----------------------------------
-int cpf_sink_log_enable(cpf_context* ctx, int64_t capacity) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_sink_log_enable: call cpf_set_mesh first");
-    CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_sink_log_enable: no located particles");
-    CPF_REQUIRE(ctx, capacity >= 1 && capacity < ((int64_t)1 << 40), CPF_ERR_ARG, "cpf_sink_log_enable: capacity must be in [1, 2^40)");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass may still be appending to the old buffer)
-    ctx->sinkLog = SinkLog{};
-    SinkLog lg;                                             // moved in whole: a failure part-way leaves the log off
-    CPF_HIP(ctx, lg.rec.alloc((size_t)capacity));
-    CPF_HIP(ctx, lg.cursor.alloc(1));
-    CPF_HIP(ctx, hipMemsetAsync(lg.cursor, 0, 8, ctx->stream));
-    lg.on = true; lg.capacity = capacity;
-    ctx->sinkLog = std::move(lg);
-    return CPF_OK;
-}
-
-int cpf_sink_log_disable(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    return dropSinkLog(ctx);
-}
-
-int cpf_sink_log_clear(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->sinkLog.on, CPF_ERR_STATE, "cpf_sink_log_clear: call cpf_sink_log_enable first");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemsetAsync(ctx->sinkLog.cursor, 0, 8, ctx->stream));
-    return CPF_OK;
-}
-
-namespace {
-// the cursor as the device holds it once the stream has drained
-int sinkLogCursor(cpf_context* ctx, uint64_t* cursor) {
-    unsigned long long c = 0;
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(&c, ctx->sinkLog.cursor, 8, hipMemcpyDeviceToHost, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *cursor = (uint64_t)c;
-    return CPF_OK;
-}
-}  // namespace
-
-int cpf_sink_log_counts(cpf_context* ctx, int64_t* stored, int64_t* dropped) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->sinkLog.on, CPF_ERR_STATE, "cpf_sink_log_counts: call cpf_sink_log_enable first");
-    uint64_t cursor = 0;
-    if (int r = sinkLogCursor(ctx, &cursor)) return r;
-    const uint64_t kept = std::min(cursor, (uint64_t)ctx->sinkLog.capacity);
-    if (stored) *stored = (int64_t)kept;
-    if (dropped) *dropped = (int64_t)(cursor - kept);
-    return CPF_OK;
-}
-
-int cpf_sink_log_read(cpf_context* ctx, cpf_sink_record* rec, int64_t maxRecords, int64_t* nRead) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->sinkLog.on, CPF_ERR_STATE, "cpf_sink_log_read: call cpf_sink_log_enable first");
-    CPF_REQUIRE(ctx, maxRecords >= 0 && (rec || maxRecords == 0), CPF_ERR_ARG, "cpf_sink_log_read: bad arguments");
-    uint64_t cursor = 0;
-    if (int r = sinkLogCursor(ctx, &cursor)) return r;
-    const size_t kept = (size_t)std::min(cursor, (uint64_t)ctx->sinkLog.capacity);
-    const size_t take = std::min(kept, (size_t)maxRecords);
-    if (nRead) *nRead = (int64_t)take;
-    if (take == 0) return CPF_OK;
-    // the order on the device is whichever workgroup reserved first: sorted here by the unique key (apply, id)
-    std::vector<cpf_sink_record> all(kept);
-    CPF_HIP(ctx, hipMemcpy(all.data(), ctx->sinkLog.rec, kept * sizeof(cpf_sink_record), hipMemcpyDeviceToHost));
-    std::sort(all.begin(), all.end(), [](const cpf_sink_record& a, const cpf_sink_record& b) {
-        return a.apply != b.apply ? a.apply < b.apply : a.id < b.id;
-    });
-    std::memcpy(rec, all.data(), take * sizeof(cpf_sink_record));
-    return CPF_OK;
-}
-
-// ---- zones: the zone of every particle id at the last sample, the zone-to-zone transition counts (cpf_zones.hip) ------------
-int cpf_zone_enable(cpf_context* ctx, int32_t nZones) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_zone_enable: call cpf_set_mesh first");
-    CPF_REQUIRE(ctx, ctx->cloud.n > 0 && ctx->cloud.located, CPF_ERR_STATE, "cpf_zone_enable: no located particles");
-    CPF_REQUIRE(ctx, nZones >= 1 && nZones <= kZoneMax, CPF_ERR_ARG, "cpf_zone_enable: nZones must be in [1, 63]");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a pass over the old tables may still be running)
-    ctx->zones = Zones{};
-    Zones zn;                                               // moved in whole: a failure part-way leaves zones off
-    const size_t n = (size_t)ctx->cloud.n, nDerived = (size_t)ctx->mesh.host.nCells, nFlow = (size_t)(nZones + 1) * (nZones + 1);
-    CPF_HIP(ctx, zn.zoneOf.alloc(nDerived));
-    CPF_HIP(ctx, zn.last.alloc(n));
-    CPF_HIP(ctx, zn.flow.alloc(nFlow));
-    CPF_HIP(ctx, hipMemsetAsync(zn.zoneOf, 0, nDerived, ctx->stream));
-    CPF_HIP(ctx, hipMemsetAsync(zn.last, kZoneOutside, n, ctx->stream));
-    CPF_HIP(ctx, hipMemsetAsync(zn.flow, 0, nFlow * 8, ctx->stream));
-    zn.on = true; zn.nZones = nZones;
-    ctx->zones = std::move(zn);
-    return CPF_OK;
-}
-
-int cpf_zone_disable(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    return dropZones(ctx);
-}
-
-int cpf_set_zone_map(cpf_context* ctx, const int32_t* zone, int64_t nCells) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->zones.on, CPF_ERR_STATE, "cpf_set_zone_map: call cpf_zone_enable first");
-    CPF_REQUIRE(ctx, zone && nCells == ctx->mesh.nParent, CPF_ERR_ARG, "cpf_set_zone_map: one value per cell of the mesh as given");
-    for (int64_t c = 0; c < nCells; ++c)
-        CPF_REQUIRE(ctx, zone[c] >= 0 && zone[c] < ctx->zones.nZones, CPF_ERR_ARG,
-                    "cpf_set_zone_map: the zone of cell " + std::to_string(c) + " is not in [0, nZones)");
-    // one byte per DERIVED cell: every derived cell of a parent gets the parent's
-    const int64_t nDerived = ctx->mesh.host.nCells;
-    std::vector<uint8_t> expanded((size_t)nDerived);
-    if (!ctx->mesh.first.empty()) {
-        for (int64_t c = 0; c < nCells; ++c)
-            for (int64_t d = ctx->mesh.first[(size_t)c]; d < ctx->mesh.first[(size_t)c + 1]; ++d) expanded[(size_t)d] = (uint8_t)zone[c];
-    } else {
-        for (int64_t c = 0; c < nCells; ++c) expanded[(size_t)c] = (uint8_t)zone[c];
-    }
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(ctx->zones.zoneOf, expanded.data(), (size_t)nDerived, hipMemcpyHostToDevice, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (the copy reads `expanded`)
-    return CPF_OK;
-}
-
-int cpf_zone_sample(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->zones.on, CPF_ERR_STATE, "cpf_zone_sample: call cpf_zone_enable first");
-    Zones& zn = ctx->zones;
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, cpf::zone_sample(ctx->stream, ctx->cloud.cur.cell, ctx->cloud.cur.gid, zn.zoneOf, zn.last, ctx->cloud.n,
-                                  ctx->mesh.host.nCells, zn.nZones, zn.flow));
-    ++zn.samples;
-    return CPF_OK;
-}
-
-int cpf_zone_reset(cpf_context* ctx) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->zones.on, CPF_ERR_STATE, "cpf_zone_reset: call cpf_zone_enable first");
-    Zones& zn = ctx->zones;
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemsetAsync(zn.flow, 0, (size_t)(zn.nZones + 1) * (zn.nZones + 1) * 8, ctx->stream));
-    zn.samples = 0;
-    return CPF_OK;
-}
-
-int cpf_get_zone_flows(cpf_context* ctx, uint64_t* flow, int64_t* nSamples) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->zones.on, CPF_ERR_STATE, "cpf_get_zone_flows: call cpf_zone_enable first");
-    const Zones& zn = ctx->zones;
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    if (flow) CPF_HIP(ctx, hipMemcpyAsync(flow, zn.flow, (size_t)(zn.nZones + 1) * (zn.nZones + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (nSamples) *nSamples = zn.samples;
-    return CPF_OK;
-}
-
-int cpf_zone_get_last(cpf_context* ctx, uint8_t* last) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->zones.on, CPF_ERR_STATE, "cpf_zone_get_last: call cpf_zone_enable first");
-    CPF_REQUIRE(ctx, last, CPF_ERR_ARG, "cpf_zone_get_last: null array");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(last, ctx->zones.last, (size_t)ctx->cloud.n, hipMemcpyDeviceToHost, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CPF_OK;
-}
-
-int cpf_zone_set_last(cpf_context* ctx, const uint8_t* last) {
-    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
-    CPF_REQUIRE(ctx, ctx->zones.on, CPF_ERR_STATE, "cpf_zone_set_last: call cpf_zone_enable first");
-    CPF_REQUIRE(ctx, last, CPF_ERR_ARG, "cpf_zone_set_last: null array");
-    for (int64_t i = 0; i < ctx->cloud.n; ++i)              // (what the sample rule can produce)
-        CPF_REQUIRE(ctx, last[i] < ctx->zones.nZones || last[i] == kZoneOutside, CPF_ERR_ARG,
-                    "cpf_zone_set_last: the byte of particle " + std::to_string(i) + " is neither a zone nor 0xFF");
-    CPF_HIP(ctx, hipSetDevice(ctx->device));
-    CPF_HIP(ctx, hipMemcpyAsync(ctx->zones.last, last, (size_t)ctx->cloud.n, hipMemcpyHostToDevice, ctx->stream));
-    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CPF_OK;
 }
 

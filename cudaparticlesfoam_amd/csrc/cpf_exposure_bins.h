@@ -1,4 +1,4 @@
-// The bin of a dose, written once for exposure_absorb_kernel (cpf_exposure.hip) and for cpf_exposure_bins_host (cpf_api.cpp):
+// The bin of a dose, written once for exposure_absorb_kernel (cpf_exposure.hip) and for cpf_exposure_bins_host (cpf_ledger.cpp):
 //   k = dose * invWidth, invWidth = 1.0 / binWidth computed once on the host; bin = k >= nBins - 1 ? nBins - 1 : (int)k.
 // Each operation is rounded on its own (the library is built with -ffp-contract=off, and there is nothing here to contract).
 // The last bin is open-ended: an infinite dose lands there.  A dose the accumulate rule cannot produce -- negative, or NaN -- has

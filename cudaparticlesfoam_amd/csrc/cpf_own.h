@@ -1,4 +1,4 @@
-// Move-only owners of what the context (cpf_api.cpp) gets from the HIP runtime: device and pinned host memory, events, streams.
+// Move-only owners of what the context (cpf_context.h) gets from the HIP runtime: device and pinned host memory, events, streams.
 // A member of one of these types is released when the struct that holds it dies or is assigned over -- the only calls of
 // hipFree, hipHostFree, hipEventDestroy and hipStreamDestroy on the context's behalf are the four deleters below.  Every owner
 // converts to its raw handle, so kernels' launchers and the runtime take it as they took the pointer.
