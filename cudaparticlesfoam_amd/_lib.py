@@ -168,6 +168,11 @@ SIGNATURES = {
     "cpf_source_positions_host": (_int, [_u32, _vp, _i64, _u32, _vp, _vp, _i64, _vp]),
     "cpf_set_source_triangles": (_int, [_ctx, _vp, _vp, _vp, _dbl, _dbl, _i64]),
     "cpf_get_source_table": (_int, [_ctx, _vp, _vp, C.POINTER(_i64)]),
+    "cpf_source_follow": (_int, [_ctx, _vp, _i64, _dbl]),
+    "cpf_source_unfollow": (_int, [_ctx]),
+    "cpf_source_refresh": (_int, [_ctx]),
+    "cpf_get_source_follow": (_int, [_ctx, _vp]),
+    "cpf_source_flux_host": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _dbl, _vp, _vp, _vp, C.POINTER(_i32)]),
     "cpf_respawn_source": (_int, [_ctx, _i64]),
     "cpf_respawn_source_dev": (_int, [_ctx, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _u32]),
     "cpf_age_enable": (_int, [_ctx, _i32, _i32]),

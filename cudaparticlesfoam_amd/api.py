@@ -307,8 +307,30 @@ class Context:
         t, w, dep, d0, d1 = _source_args(tri, weights, depth)
         self._ck(self.lib.cpf_set_source_triangles(self.h, _ptr(t) if t.size else None, _ptr(w), _ptr(dep), d0, d1, t.shape[0]))
 
+    def source_follow(self, cells, depth_scale: float = 0.0):
+        """The source's bounds -- and, with ``depth_scale`` > 0 (seconds: dt * cycles between respawns), its slab depths -- follow
+        the velocity from now on: every ``set_velocity`` / ``set_velocity_dev`` ends with a refresh on the device (include/cpf.h
+        "flux table").  ``cells``: the owner cell of every triangle of ``set_source_triangles``, ``mesh.owner[face_of_tri]``."""
+        c = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1)
+        self._ck(self.lib.cpf_source_follow(self.h, _ptr(c) if c.size else None, c.size, float(depth_scale)))
+
+    def source_unfollow(self):
+        """Following off: the table stays as last refreshed."""
+        self._ck(self.lib.cpf_source_unfollow(self.h))
+
+    def source_refresh(self):
+        """One refresh of the followed table from the current field, asynchronous on the context's stream."""
+        self._ck(self.lib.cpf_source_refresh(self.h))
+
+    def source_follow_counts(self):
+        """dict(on, refreshes, skipped): skipped counts the refreshes that found no inflow and left the table alone."""
+        out = np.zeros(3, np.int64)
+        self._ck(self.lib.cpf_get_source_follow(self.h, _ptr(out)))
+        return dict(on=bool(out[0]), refreshes=int(out[1]), skipped=int(out[2]))
+
     def source_table(self):
-        """(rec [k][16], hi [k] uint32) of the source as built (cpf_source_table_host's layout); k == 0 without a source."""
+        """(rec [k][16], hi [k] uint32) of the source (cpf_source_table_host's layout): as built, or, while it follows U, the
+        device's current one; k == 0 without a source."""
         k = C.c_int64(0)
         self._ck(self.lib.cpf_get_source_table(self.h, None, None, C.byref(k)))
         rec, hi = np.empty((k.value, 16), np.float64), np.empty(k.value, np.uint32)
@@ -754,6 +776,23 @@ def source_table_host(tri, weights=None, depth=(0.0, 0.0)):
     return rec[:k.value].copy(), hi[:k.value].copy()
 
 
+def source_flux_host(rec, cells, U, depth_scale: float = 0.0):
+    """The flux-table rule on the host alone (cpf_source_flux_host; include/cpf.h "flux table"): what a refresh makes of the table
+    ``rec`` [k][16] under the field ``U`` [nCells][3], ``cells`` the owner cell per input triangle.  Returns (span [k], hi [k] uint32,
+    q [k] uint64, empty); with ``empty`` (no inflow anywhere) a refresh changes nothing and the three arrays are all 0."""
+    lib = L.load()
+    r = np.ascontiguousarray(rec, dtype=np.float64).reshape(-1, 16)
+    c = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1)
+    u = np.ascontiguousarray(U, dtype=np.float64).reshape(-1, 3)
+    k = r.shape[0]
+    span, hi, q, empty = np.zeros(k, np.float64), np.zeros(k, np.uint32), np.zeros(k, np.uint64), C.c_int32(0)
+    st = lib.cpf_source_flux_host(_ptr(r) if k else None, k, _ptr(c) if c.size else None, c.size, _ptr(u) if u.size else None,
+                                  u.shape[0], float(depth_scale), _ptr(span), _ptr(hi), _ptr(q), C.byref(empty))
+    if st != L.CPF_OK:
+        raise L.CpfError(st, "cpf_source_flux_host")
+    return span, hi, q, bool(empty.value)
+
+
 def source_positions_host(seed: int, gid, epoch: int, rec, hi, n: Optional[int] = None) -> np.ndarray:
     """Where ``respawn_source`` puts the particles ``gid`` (None: 0 .. n-1) at ``epoch`` under ``seed`` on the table (rec, hi):
     [n][3], computed on the host alone from the kernel's own text (cpf_source_positions_host)."""
@@ -1011,7 +1050,11 @@ class CudaParticles:
     With ``sourceTriangles`` ([m][3][3]; ``mesh.face_triangles(mesh.patch_faces("inlet"))``) the dead slots are respawned on those
     triangles instead (``Context.respawn_source``) and ``sourceBox`` is unused: ``sourceWeights`` ([m]; default: the areas,
     ``inflow_weights`` gives the flux-weighted ones) chooses the triangle and ``sourceDepth`` ((d0, d1) or [m][2]; default 0)
-    is the range of depths behind it.  The weights do not follow ``advect(U=...)``.
+    is the range of depths behind it.  Those weights are fixed.  With ``sourceFollowU`` (default false; it needs
+    ``recycleInterval`` > 0, ``sourceTriangles`` and ``sourceCells``, one owner cell per triangle, ``mesh.owner[face_of_tri]``, and
+    excludes ``sourceWeights``) the table is built with the areas and then follows the velocity: every ``advect(U=...)`` recomputes
+    the flux weights on the device (``Context.source_follow``), and with ``sourceDepthScale`` (seconds, default 0: the user's
+    dt * recycleInterval) the depth behind each triangle becomes (U . n_in) * sourceDepthScale as well.
 
     Two more, also this library's own: ``ageBins`` (default 0 = off) and ``ageBinCycles`` (default: ``recycleInterval``, else 1).
     When ``ageBins`` is positive, age tracking (``Context.age_enable``) starts once the cloud is located: every absorption adds a
@@ -1065,6 +1108,14 @@ class CudaParticles:
         self.sourceTriangles = d.get("sourceTriangles", None)
         self.sourceWeights = d.get("sourceWeights", None)
         self.sourceDepth = d.get("sourceDepth", (0.0, 0.0))
+        self.sourceCells = d.get("sourceCells", None)
+        self.sourceFollowU = bool(d.get("sourceFollowU", False))
+        self.sourceDepthScale = float(d.get("sourceDepthScale", 0.0))
+        if self.sourceFollowU:
+            if self.recycleInterval <= 0 or self.sourceTriangles is None or self.sourceCells is None:
+                raise ValueError("sourceFollowU needs recycleInterval > 0, sourceTriangles and sourceCells")
+            if self.sourceWeights is not None:
+                raise ValueError("sourceFollowU computes the weights from U: it excludes sourceWeights")
         self.ageBins = int(d.get("ageBins", 0))
         self.ageBinCycles = int(d.get("ageBinCycles", self.recycleInterval if self.recycleInterval > 0 else 1))
         self.sinkGroups = d.get("sinkGroups", None)
@@ -1134,6 +1185,8 @@ class CudaParticles:
             self.ctx.set_sink_cells(self.sinkCells)
         if self.recycleInterval > 0 and self.sourceTriangles is not None:
             self.ctx.set_source_triangles(self.sourceTriangles, self.sourceWeights, self.sourceDepth)
+            if self.sourceFollowU:          # (built with the areas: no triangle with inflow later is dropped now)
+                self.ctx.source_follow(self.sourceCells, self.sourceDepthScale)
         if positions is not None:            # parity runs inject positions
             self.ctx.set_particles(positions)
             self.numParticles = int(np.asarray(positions).shape[0])

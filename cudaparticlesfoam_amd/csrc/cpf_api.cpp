@@ -17,6 +17,7 @@
 #include "cpf.h"
 #include "cpf_context.h"   // cpf_context and its groups, fail, CPF_HIP, CPF_REQUIRE
 #include "cpf_device.h"
+#include "cpf_inflow.h"    // the flux table's arithmetic (cpf_source_flux_host)
 #include "cpf_internal.h"
 #include "cpf_own.h"
 #include "cpf_philox.h"    // respawn_position (cpf_respawn_positions_host)
@@ -310,6 +311,16 @@ hipError_t layOutField(cpf_context* ctx, const double* dU3, int64_t nCells) {
         if (e == hipSuccess) e = hipEventRecord(ctx->evFieldFlag, ctx->stream);
         ctx->fieldFlagPending = e == hipSuccess;
     }
+    return e;
+}
+// The source table follows U (cpf_source_follow): one refresh on the stream from U[.][uStride] -- the array layOutField was given
+// (uStride 3), or the padded field (uStride 4).  Nothing here waits, copies to the host or allocates.
+hipError_t refreshSource(cpf_context* ctx, const double* dU, int uStride) {
+    SourceFollow& f = ctx->mesh.follow;
+    const cpf::InflowView v{ctx->mesh.sourceRec, ctx->mesh.sourceHi, (int32_t)ctx->mesh.sourceKept, f.depthScale,
+                            f.area, f.owner, f.w, f.sums, f.slots};
+    const hipError_t e = cpf::inflow_refresh(ctx->stream, v, dU, uStride);
+    if (e == hipSuccess) ++f.refreshes;
     return e;
 }
 // Sub-cell resolve of cpf_set_particles on a decomposed mesh: parent cell c -> the lowest derived cell of first[c] .. first[c+1]
@@ -670,6 +681,7 @@ int cpf_set_velocity(cpf_context* ctx, const double* U, int64_t nCells) {
         CPF_HIP(ctx, hipMemcpyAsync(ctx->mesh.U3, U, (size_t)nCells * 24, hipMemcpyHostToDevice, ctx->stream));
     }
     CPF_HIP(ctx, layOutField(ctx, ctx->mesh.U3, ctx->mesh.host.nCells));
+    if (ctx->mesh.follow.on) CPF_HIP(ctx, refreshSource(ctx, ctx->mesh.U3, 3));
     CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));   // U may be pageable host memory owned by the caller
     fieldFlagArrived(ctx);
     ctx->mesh.haveU = true;
@@ -686,6 +698,7 @@ int cpf_set_velocity_dev(cpf_context* ctx, const double* dU, int64_t nCells) {
         dU = ctx->mesh.U3;
     }
     CPF_HIP(ctx, layOutField(ctx, dU, ctx->mesh.host.nCells));   // (asynchronous: the flat walk waits until the flag has been seen to arrive)
+    if (ctx->mesh.follow.on) CPF_HIP(ctx, refreshSource(ctx, dU, 3));
     ctx->mesh.haveU = true;
     return CPF_OK;
 }
@@ -1421,6 +1434,7 @@ int cpf_set_source_triangles(cpf_context* ctx, const double* tri, const double* 
     ctx->mesh.sourceKept = 0;
     ctx->mesh.sourceRecHost.clear();
     ctx->mesh.sourceHiHost.clear();
+    ctx->mesh.follow = SourceFollow{};                      // (a new table does not follow U until cpf_source_follow says so)
     ctx->tags.originOfKept = DevBuf<uint8_t>{};
     if (n == 0) return CPF_OK;
     DevBuf<uint8_t> dOrigin;                                // tagging: a new source starts with every triangle in origin 0
@@ -1451,8 +1465,145 @@ int cpf_set_source_triangles(cpf_context* ctx, const double* tri, const double* 
 int cpf_get_source_table(cpf_context* ctx, double* rec, uint32_t* hi, int64_t* nKept) {
     CPF_REQUIRE(ctx, ctx && nKept, CPF_ERR_ARG, "null argument");
     *nKept = ctx->mesh.sourceKept;
+    if (ctx->mesh.follow.on) {                              // the table lives on the device: the host copies are the table as built
+        CPF_HIP(ctx, hipSetDevice(ctx->device));
+        CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const size_t k = (size_t)ctx->mesh.sourceKept;
+        if (rec) CPF_HIP(ctx, hipMemcpy(rec, ctx->mesh.sourceRec, k * cpf::kSourceDoubles * sizeof(double), hipMemcpyDeviceToHost));
+        if (hi) CPF_HIP(ctx, hipMemcpy(hi, ctx->mesh.sourceHi, k * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return CPF_OK;
+    }
     if (rec) std::copy(ctx->mesh.sourceRecHost.begin(), ctx->mesh.sourceRecHost.end(), rec);
     if (hi) std::copy(ctx->mesh.sourceHiHost.begin(), ctx->mesh.sourceHiHost.end(), hi);
+    return CPF_OK;
+}
+
+// ---- flux table: the source's bounds and depths follow U (cpf_inflow.hip; the arithmetic: cpf_inflow.h) ----------------------
+namespace {
+// len of a kept record from its e1, e2, exactly as cpf_source_table_host computes it
+double sourceRecordLen(const double* r) {
+    const double *e1 = r + 3, *e2 = r + 6;
+    double c[3];
+    for (int a = 0; a < 3; ++a) {
+        const int b = (a + 1) % 3, d = (a + 2) % 3;
+        const double p = e1[b] * e2[d], q = e1[d] * e2[b];
+        c[a] = p - q;
+    }
+    const double xx = c[0] * c[0], yy = c[1] * c[1], zz = c[2] * c[2];
+    const double xy = xx + yy;
+    return std::sqrt(xy + zz);
+}
+}  // namespace
+
+int cpf_source_flux_host(const double* rec, int64_t nKept, const int32_t* cellOfTriangle, int64_t nTriangles, const double* U,
+                         int64_t nCells, double depthScale, double* span, uint32_t* hi, uint64_t* q, int32_t* empty) {
+    if (!rec || !cellOfTriangle || !U || !empty || nKept <= 0 || nKept > ((int64_t)1 << 24) || nTriangles <= 0 || nCells <= 0 ||
+        !(std::isfinite(depthScale) && depthScale >= 0.0))
+        return CPF_ERR_ARG;
+    std::vector<cpf::InflowTerm> term((size_t)nKept);
+    uint64_t wmaxBits = 0;                                  // (non-negative doubles order like their bits)
+    for (int64_t k = 0; k < nKept; ++k) {
+        const double* r = rec + cpf::kSourceDoubles * k;
+        if (!(r[14] >= 0.0 && r[14] < (double)nTriangles)) return CPF_ERR_ARG;
+        const int64_t c = cellOfTriangle[(int64_t)r[14]];
+        if (c < 0 || c >= nCells) return CPF_ERR_ARG;
+        const double area = sourceRecordLen(r) / 2.0;
+        term[(size_t)k] = cpf::inflow_term(U[3 * c], U[3 * c + 1], U[3 * c + 2], r[9], r[10], r[11], area, depthScale);
+        wmaxBits = std::max(wmaxBits, cpf::inflow_bits(term[(size_t)k].w));
+    }
+    *empty = wmaxBits == 0 ? 1 : 0;
+    if (wmaxBits == 0) return CPF_OK;
+    double wmax;
+    std::memcpy(&wmax, &wmaxBits, 8);
+    const int E = cpf::inflow_exponent(wmax);
+    uint64_t last = 0;
+    for (int64_t k = 0; k < nKept; ++k) last += cpf::inflow_quantum(term[(size_t)k].w, E);
+    uint64_t Q = 0;
+    for (int64_t k = 0; k < nKept; ++k) {
+        const uint64_t qk = cpf::inflow_quantum(term[(size_t)k].w, E);
+        Q += qk;
+        if (q) q[k] = qk;
+        if (hi) hi[k] = cpf::inflow_bound(Q, last);
+        if (span) span[k] = term[(size_t)k].span;
+    }
+    return CPF_OK;
+}
+
+int cpf_source_follow(cpf_context* ctx, const int32_t* cellOfTriangle, int64_t nTriangles, double depthScale) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.have, CPF_ERR_STATE, "cpf_source_follow: call cpf_set_mesh first");
+    CPF_REQUIRE(ctx, ctx->mesh.sourceKept > 0, CPF_ERR_STATE, "cpf_source_follow: call cpf_set_source_triangles first");
+    CPF_REQUIRE(ctx, cellOfTriangle && nTriangles > 0, CPF_ERR_ARG, "cpf_source_follow: bad arguments");
+    CPF_REQUIRE(ctx, std::isfinite(depthScale) && depthScale >= 0.0, CPF_ERR_ARG,
+                "cpf_source_follow: depthScale must be finite and >= 0");
+    for (int64_t t = 0; t < nTriangles; ++t)
+        CPF_REQUIRE(ctx, cellOfTriangle[t] >= 0 && cellOfTriangle[t] < ctx->mesh.nParent, CPF_ERR_ARG,
+                    "cpf_source_follow: cell " + std::to_string(cellOfTriangle[t]) + " is not in [0, nCells)");
+    // per kept record: the area, and the owner as a cell of the mesh the walk runs on (any derived cell carries its parent's U)
+    const size_t kept = (size_t)ctx->mesh.sourceKept;
+    const bool derived = !ctx->mesh.first.empty();
+    std::vector<double> area(kept);
+    std::vector<int32_t> owner(kept);
+    for (size_t k = 0; k < kept; ++k) {
+        const double* r = &ctx->mesh.sourceRecHost[k * cpf::kSourceDoubles];
+        const int64_t t = (int64_t)r[14];
+        CPF_REQUIRE(ctx, t >= 0 && t < nTriangles, CPF_ERR_ARG,
+                    "cpf_source_follow: the source has a triangle " + std::to_string(t) + ", beyond nTriangles");
+        area[k] = sourceRecordLen(r) / 2.0;
+        const int32_t c = cellOfTriangle[t];
+        owner[k] = derived ? ctx->mesh.first[(size_t)c] : c;
+    }
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a refresh from the old state may still be running)
+    SourceFollow f;
+    const size_t nBlocks = (size_t)cpf::inflow_blocks((int64_t)kept);
+    CPF_HIP(ctx, f.area.alloc(kept));
+    CPF_HIP(ctx, f.owner.alloc(kept));
+    CPF_HIP(ctx, f.w.alloc(2 * kept));
+    CPF_HIP(ctx, f.sums.alloc(2 * nBlocks));
+    CPF_HIP(ctx, f.slots.alloc(4));
+    CPF_HIP(ctx, hipMemcpy(f.area, area.data(), kept * sizeof(double), hipMemcpyHostToDevice));
+    CPF_HIP(ctx, hipMemcpy(f.owner, owner.data(), kept * sizeof(int32_t), hipMemcpyHostToDevice));
+    CPF_HIP(ctx, hipMemset(f.slots, 0, 4 * 8));
+    f.on = true;
+    f.depthScale = depthScale;
+    ctx->mesh.follow = std::move(f);
+    if (ctx->mesh.haveU) CPF_HIP(ctx, refreshSource(ctx, reinterpret_cast<const double*>(ctx->mesh.U.get()), 4));
+    return CPF_OK;
+}
+
+int cpf_source_unfollow(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    if (!ctx->mesh.follow.on) return CPF_OK;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (a refresh may still be running)
+    // the table stays as last refreshed, on the host too from now on
+    const size_t k = (size_t)ctx->mesh.sourceKept;
+    CPF_HIP(ctx, hipMemcpy(ctx->mesh.sourceRecHost.data(), ctx->mesh.sourceRec, k * cpf::kSourceDoubles * sizeof(double), hipMemcpyDeviceToHost));
+    CPF_HIP(ctx, hipMemcpy(ctx->mesh.sourceHiHost.data(), ctx->mesh.sourceHi, k * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    ctx->mesh.follow = SourceFollow{};
+    return CPF_OK;
+}
+
+int cpf_source_refresh(cpf_context* ctx) {
+    CPF_REQUIRE(ctx, ctx, CPF_ERR_ARG, "null context");
+    CPF_REQUIRE(ctx, ctx->mesh.follow.on, CPF_ERR_STATE, "cpf_source_refresh: call cpf_source_follow first");
+    CPF_REQUIRE(ctx, ctx->mesh.haveU, CPF_ERR_STATE, "cpf_source_refresh: call cpf_set_velocity first");
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    CPF_HIP(ctx, refreshSource(ctx, reinterpret_cast<const double*>(ctx->mesh.U.get()), 4));
+    return CPF_OK;
+}
+
+int cpf_get_source_follow(cpf_context* ctx, int64_t out[3]) {
+    CPF_REQUIRE(ctx, ctx && out, CPF_ERR_ARG, "null argument");
+    unsigned long long skipped = 0;
+    CPF_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->mesh.follow.on)
+        CPF_HIP(ctx, hipMemcpyAsync(&skipped, ctx->mesh.follow.slots + 2, 8, hipMemcpyDeviceToHost, ctx->stream));
+    CPF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    out[0] = ctx->mesh.follow.on ? 1 : 0;
+    out[1] = ctx->mesh.follow.refreshes;
+    out[2] = (int64_t)skipped;
     return CPF_OK;
 }
 

@@ -29,6 +29,19 @@ using cpf::DevBuf; using cpf::Event; using cpf::PinnedBuf;
 // What the context owns, grouped by lifetime: each group goes away as a whole -- assigned over with an empty one, or with the
 // context.  The members are owners (cpf_own.h): nothing here is freed by hand.
 
+// Flux table (cpf_source_follow; cpf_inflow.hip): what a refresh of the source table needs, allocated once.  It belongs to the
+// source table it was made for: a new table and a new mesh each replace it with an empty one.
+struct SourceFollow {
+    bool on = false;
+    double depthScale = 0.0;
+    DevBuf<double> area;                    // [sourceKept] len / 2 of every kept record
+    DevBuf<int32_t> owner;                  // [sourceKept] its owner cell, as the id the device's U is indexed by (a DERIVED cell)
+    DevBuf<double> w;                       // [2][sourceKept] scratch of the four-launch path: the weights, the depths
+    DevBuf<unsigned long long> sums;        // [2][inflow_blocks(sourceKept)] ... the tiles' sums, their offsets
+    DevBuf<unsigned long long> slots;       // [4] wmax's bits, Q_last, refreshes skipped for zero inflow, spare
+    int64_t refreshes = 0;                  // refreshes put on the stream since cpf_source_follow
+};
+
 // The mesh: the host tables and every device table made from them.  Replaced by cpf_set_mesh.
 struct Mesh {
     bool have = false, haveU = false;
@@ -62,6 +75,7 @@ struct Mesh {
     int64_t sourceKept = 0;
     std::vector<double> sourceRecHost;      // the table as built (cpf_get_source_table)
     std::vector<uint32_t> sourceHiHost;
+    SourceFollow follow;                    // the table follows U (cpf_source_follow): hi and column 13 live on the device then
 };
 
 // "VertexVelocity" advect only: the tet decomposition and one velocity per tet-mesh vertex.  It belongs to the mesh it was made

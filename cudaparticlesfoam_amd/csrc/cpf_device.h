@@ -301,6 +301,16 @@ struct SourceView { const double* rec; const uint32_t* hi; int32_t nKept; };
 hipError_t respawn_source(hipStream_t st, double* x, double* y, double* z, int32_t* cell, const int64_t* gid, int64_t n,
                           const SourceView& src, int64_t maxCount, uint32_t seed, uint32_t epoch, const MeshView& m,
                           const GridView& g, void* scratch, size_t scratchBytes, unsigned long long* counters);
+// flux table (cpf_inflow.hip; the rule: include/cpf.h "flux table", the arithmetic: cpf_inflow.h).  One refresh of hi[] and, with
+// depthScale > 0, of column 13 of rec from U (uStride doubles a cell, indexed by owner[]), asynchronous on `st`: no allocation, no
+// copy to the host, no wait.  area[nKept], owner[nKept]; w: 2 * nKept doubles; sums: 2 * inflow_blocks(nKept) words; slots: 4 words,
+// [2] counts the refreshes that found no inflow and left the table alone
+struct InflowView {
+    double* rec; uint32_t* hi; int32_t nKept; double depthScale;
+    const double* area; const int32_t* owner; double* w; unsigned long long* sums; unsigned long long* slots;
+};
+int64_t inflow_blocks(int64_t nKept);
+hipError_t inflow_refresh(hipStream_t st, const InflowView& v, const double* U, int uStride);
 // tracer age (cpf_age.hip).  birth[id] (n entries, id = gid[slot]; gid null: the slot) is the cycle count at which particle id last
 // became live, an age is (uint32_t)(now - birth).  age_absorb: sink_apply, and hist[min(age / binCycles, nBins - 1)] += 1 for every
 // particle it absorbs.  age_stamp: birth[id] = now for every slot with cell < 0.  age_field: for every i with 0 <= cell[i] <

@@ -55,7 +55,8 @@ __host__ __device__ __forceinline__ void source_words(uint32_t seed, uint64_t gi
     c[0] = (uint32_t)gid; c[1] = (uint32_t)(gid >> 32); c[2] = epoch; c[3] = 0u;
     philox4x32(c, seed, 0x43504633u);
 }
-// lower bound over the strictly increasing hi[0 .. n-1] (hi[n-1] == 0xFFFFFFFF: there always is one)
+// lower bound over the non-decreasing hi[0 .. n-1] -- strictly increasing as built, with equal neighbours once the table follows U
+// (include/cpf.h "flux table") -- (hi[n-1] == 0xFFFFFFFF: there always is one)
 __host__ __device__ __forceinline__ int source_pick(const uint32_t* __restrict__ hi, int n, uint32_t w0) {
     int lo = 0, len = n;
     while (len > 1) {

@@ -466,8 +466,31 @@ int cpf_respawn_positions_host(uint32_t seed, const int64_t* gid, int64_t n, uin
  * 0x43504633); word 0 picks the first t with w0 <= hi[t]; words 1 and 2, as 64-bit integers, are each replaced by 2^32 - w if
  * w1 + w2 > 2^32, and u = w * 2^-32; d = d0 + (w3 * 2^-32) * (d1 - d0); pos_k = ((A_k + u1 * e1_k) + u2 * e2_k) + d * nIn_k, each
  * product and sum rounded on its own, in that order.
- * The weights are the caller's: a source does not follow cpf_set_velocity -- set it again when U changes.  cpf_shard_* and the
- * compat fragments do not know of it.
+ * The weights are the caller's -- unless the source FOLLOWS U (cpf_source_follow, "flux table" below): then the bounds hi[] and,
+ * with a depth scale, the slab depths are recomputed on the device from the current U each time cpf_set_velocity* runs, with no
+ * wait for the stream.  cpf_shard_* and the compat fragments do not know of the source.
+ *
+ * FLUX TABLE, the rule (cpf_source_flux_host states it; the kernels of cpf_inflow.hip are pinned to it bit for bit).  Inputs: the
+ * kept records k = 0 .. K-1 of the current table (K = nKept <= 2^24), one owner cell per INPUT triangle (cellOfTriangle[rec[k][14]]),
+ * the current U, a depth scale s >= 0.  Every floating-point operation is rounded on its own (-ffp-contract=off):
+ *   un_k   = ((Ux * nIn_x) + (Uy * nIn_y)) + (Uz * nIn_z), nIn = columns 9..11 of the record, U that of the triangle's owner cell;
+ *   v_k    = un_k > 0 ? un_k : 0 (a NaN gives 0);
+ *   area_k = len_k / 2, len_k recomputed from the record's e1, e2 as cpf_source_table_host computes it (column 15 stays 0);
+ *   w_k    = area_k * v_k and span_k = s * v_k, each counted as 0 where it is not finite;
+ *   wmax   = max_k w_k.  wmax == 0 (no inflow anywhere): NOTHING of the table changes, and a "skipped" counter goes up by one.
+ *   Else wmax = f * 2^E with f in [0.5, 1), and q_k = floor(w_k * 2^(32 - E)) as a 64-bit integer, scaled exactly through the
+ *   exponent bits: q_k < 2^32, q_max >= 2^31.  Q_k = q_0 + ... + q_k in 64-bit integers (< 2^56): exact and independent of the
+ *   order, so a parallel scan and a sequential loop give the same bits.
+ *   b_k    = 2^32 if Q_k == Q_last, else min(2^32, (uint64) floor(((double)Q_k / (double)Q_last) * 4294967296.0)), the two
+ *   conversions, the division and the product one IEEE operation each;  hi[k] = (uint32)(max(b_k, 1) - 1).
+ *   s > 0: column 13 of record k becomes span_k; s == 0: the depths stay the table's.  Column 12 and the rest are never touched.
+ * What follows from it: hi is non-decreasing and ends in 0xFFFFFFFF, but is no longer strictly increasing; every search of it
+ * (source_pick, the place kernel's staged search, the tag stamp's) is a lower bound and gives "the first t with w0 <= hi[t]" on
+ * such a table as well, so none of them changed.  A triangle without inflow is never picked, with one exception: such a triangle
+ * AHEAD of the first one with inflow takes the single draw w0 == 0, one in 2^32.  No record is dropped or moved: nKept, the
+ * origins of tagging and the indices in column 14 stay valid across refreshes.
+ * cpf_set_source_triangles (a new table) and cpf_set_mesh* turn following off and free its state; a context that never calls
+ * cpf_source_follow keeps today's tables byte for byte.
  * ------------------------------------------------------------------------------------------- */
 /* NO REFERENCE COUNTERPART.  The table builder -- no context, no GPU.  tri[n][3][3]; weight[n] nullable (the areas); depth[n][2]
  * nullable (then d0, d1 hold for every triangle; otherwise they are ignored).  rec (16 * n doubles) and hi (n words) are nullable
@@ -483,8 +506,31 @@ int cpf_source_positions_host(uint32_t seed, const int64_t* gid, int64_t n, uint
  * n == 0 clears the source.  CPF_ERR_STATE without a mesh.  The source belongs to the mesh: cpf_set_mesh* drops it. */
 int cpf_set_source_triangles(cpf_context* ctx, const double* tri, const double* weight, const double* depth, double d0, double d1,
                              int64_t n);
-/* NO REFERENCE COUNTERPART.  The context's table: rec[nKept][16] and hi[nKept] (each nullable), *nKept (0 without a source). */
+/* NO REFERENCE COUNTERPART.  The context's table: rec[nKept][16] and hi[nKept] (each nullable), *nKept (0 without a source).
+ * While the source follows U it waits for the context's stream and returns the device's current table. */
 int cpf_get_source_table(cpf_context* ctx, double* rec, uint32_t* hi, int64_t* nKept);
+/* NO REFERENCE COUNTERPART.  Turns following on ("flux table" above): cellOfTriangle[nTriangles] (host memory) is the cell of the
+ * mesh AS GIVEN that owns each triangle handed to cpf_set_source_triangles, in the caller's order, dropped triangles included;
+ * depthScale (seconds: dt * cycles between respawns) must be finite and >= 0.  Allocates what a refresh needs and, if the context
+ * has a velocity, refreshes at once.  From then on cpf_set_velocity and cpf_set_velocity_dev end with a refresh on the stream,
+ * behind the field's layout, which adds no wait, no copy to the host and no allocation to either.  CPF_ERR_STATE without a mesh
+ * or a source; CPF_ERR_ARG: a cell outside [0, nCells), fewer entries than the source has triangles, a bad depthScale. */
+int cpf_source_follow(cpf_context* ctx, const int32_t* cellOfTriangle, int64_t nTriangles, double depthScale);
+/* NO REFERENCE COUNTERPART.  Turns following off (no error when it is off already): the table stays as last refreshed. */
+int cpf_source_unfollow(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  One refresh from the context's current field, asynchronous on the context's stream.  CPF_ERR_STATE
+ * unless following is on and a velocity is set. */
+int cpf_source_refresh(cpf_context* ctx);
+/* NO REFERENCE COUNTERPART.  Waits for the context's stream; out = following on (1) or off (0), the refreshes put on the stream since
+ * cpf_source_follow, and those of them that found no inflow and left the table alone (counted on the device). */
+int cpf_get_source_follow(cpf_context* ctx, int64_t out[3]);
+/* NO REFERENCE COUNTERPART.  The flux-table rule on the host alone -- no context, no GPU, sequential.  rec[nKept][16] a table of
+ * cpf_source_table_host's layout, cellOfTriangle[nTriangles], U[nCells][3]; span[nKept], hi[nKept], q[nKept] each nullable.
+ * *empty = 1 when wmax == 0, and then no output is written.  span is the rule's span_k whatever depthScale is (all 0 for 0).
+ * CPF_ERR_ARG: a null input, nKept outside [1, 2^24], a column 14 outside [0, nTriangles), a cell outside [0, nCells), a
+ * depthScale negative or not finite. */
+int cpf_source_flux_host(const double* rec, int64_t nKept, const int32_t* cellOfTriangle, int64_t nTriangles, const double* U,
+                         int64_t nCells, double depthScale, double* span, uint32_t* hi, uint64_t* q, int32_t* empty);
 /* NO REFERENCE COUNTERPART.  Respawns up to maxCount (< 0: all) dead slots of the context-owned cloud on the source, with the
  * cloud's own epoch counter -- the one cpf_respawn_box uses and increments: a run may mix the two, and no (id, epoch) is drawn
  * twice from one stream.  Asynchronous on the context's stream.  The cloud's z no longer counts as settled.  With age tracking

@@ -67,6 +67,13 @@ def collect_inlet():
     return parse(r.stderr, ("inlet_",))
 
 
+def collect_inflow():
+    """The same rows for the flux-table kernels (cpf_inflow.hip: inflow_fused_kernel, inflow_flux_kernel, inflow_sums_kernel,
+    inflow_scan_kernel, inflow_apply_kernel); collect() does not list them.  All their LDS is static."""
+    r = subprocess.run(hipcc_cmd("cpf_inflow.hip") + ["-c", "-o", "/dev/null"], capture_output=True, text=True)
+    return parse(r.stderr, ("inflow_",))
+
+
 def collect_tags():
     """The same rows for the tracer-tag kernels (cpf_tags.hip: tag_transfer_kernel, tag_stamp_kernel, tag_field_kernel); collect()
     does not list them.  All their LDS is static."""
